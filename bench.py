@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- distillation-step images/sec @512x512 (Pi+Pa+Ho) on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,10 +13,14 @@ A step = one NetModel.optimize_parameters() (kd_model.py:167-173): frozen ResNet
 forward + ResNet18-PSPNet student forward/backward (InPlace-ABN at every BN) + CE/Pi/Pa/Ho losses +
 SGD + discriminator step (adv + WGAN-GP) + SGD, fp32, batch 8 per GPU, synthetic 512x512 19-class
 tensors already resident in HBM, Dropout on, logged scalars read back every step like
-train_and_eval.py:26.  N > 1: one process per GPU, weak scaling (8 images per rank), RCCL gradient
+train_and_eval.py:26.  Every step starts from the same seeded state (see build() in main), so what a step computes is the
+same from run to run.  N > 1: one process per GPU, weak scaling (8 images per rank), RCCL gradient
 all-reduce + cross-GPU InPlaceABNSync.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs DIR) and prints the
+line.  --full adds the extra measurements below, which take runs and steps of their own after the timed region.
+
+Extra objects on the line (--full):
   roofline      the dominant hand-written kernel of the step, timed live with HIP events on the launch stream over the
                 timed steps: since round 3 the fused bottleneck-tail GEMM of the frozen teacher (conv1x1_abn_kernel:
                 bn2 + ReLU prologue, 1x1 convolution on fp32 MFMA, bn3 + residual + ReLU epilogue; 2*M*K*N algorithmic
@@ -61,6 +65,12 @@ def parse():
                          "by the test's sitecustomize and refuses to run otherwise; nothing is measured in that mode")
     ap.add_argument("--dsn-ab", action="store_true", help="also re-time the step without the teacher's dead DSN head (informative; opt-in: "
                                                          "the default run stays exactly the measured configuration and nothing else)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements: per-kernel HIP-event rates and the roofline entry (extra untimed steps), the "
+                         "pair-wise Gram sweep and the CPU baseline (each can still be switched off by its --no-* flag).  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -106,6 +116,32 @@ def cpu_baseline(seconds, size):
                       "torch CPU (oracle/step_torch.py); host CPU: %s" % (n, "/".join("%.1f" % t for t in times), B, size, size, model),
             "config1": {"value": round(B / statistics.median(t1), 4), "unit": "images/sec",
                         "sample": "median of 3 steps (+1 warm-up), BASELINE configs[0]: Pi only, batch 2, 256x256"}}
+
+
+DUMP_SAMPLE = 1 << 20          # weights sampled per network for --dump-outputs (4 MB each as float32)
+
+
+def dump_outputs(out_dir, model, losses):
+    """--dump-outputs: what the last timed step computed, as a caller of NetModel.optimize_parameters() receives it.
+      losses.npy                      float64 [G, mc, pi, pa, D], the logged scalars (print_info's reads)
+      student_logits.npy              float32 (B, 19, h, w), NCHW
+      teacher_logits.npy              float32 (B, 19, h, w), NCHW
+      <net>_weights_sample.npy        float32, net = student / discriminator: the updated floating-point state (state_dict order,
+                                      each tensor flattened in logical NCHW order) at DUMP_SAMPLE fixed indices (numpy seed 0)
+    About 13 MB at batch 8.  Every step starts from the same seeded state (main/build), so two runs with the same arguments agree
+    to rounding: MIOpen's split-K solvers add in no fixed order (~1e-5 relative, measured on MI355X)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": np.array([float(v) for v in losses], dtype=np.float64),
+              "student_logits": model.preds_S[0].detach().float().cpu().numpy(),
+              "teacher_logits": model.preds_T[0].detach().float().cpu().numpy()}
+    for name, net in (("student", model.student), ("discriminator", model.D_model)):
+        flat = torch.cat([t.detach().float().cpu().reshape(-1) for t in net.state_dict().values() if t.is_floating_point()]).numpy()
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, size=min(flat.size, DUMP_SAMPLE), replace=False))
+        arrays[name + "_weights_sample"] = flat[idx]
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def pairwise_sweep(dev):
@@ -414,6 +450,8 @@ def self_launch(a):
 
 def main():
     a = parse()
+    if not a.full:
+        a.no_kernel_timing = a.no_pairwise_sweep = a.no_cpu_baseline = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))
     import torch
@@ -460,8 +498,20 @@ def main():
     def build():
         torch.manual_seed(1234)
         model = NetModel(args)
+        # Every step -- warm-up and timed -- starts from the same seeded state: weights, BN statistics, spectral-norm vectors and
+        # zero SGD momentum (buf = 0.9 * 0 + g: the first step's update).  The work of a step is unchanged, but its outputs
+        # become reproducible run to run.  Chained training steps are not: MIOpen's split-K solvers add in no fixed order, and
+        # the step amplifies those rounding differences ~50x per step (order one after ~4 steps, measured on MI355X).
+        for opt in (model.G_solver, model.D_solver):
+            for p in opt.param_groups[0]["params"]:
+                opt.state[p]["momentum_buffer"] = torch.zeros_like(p)
+        live = [t.data for net in (model.student, model.D_model) for t in list(net.parameters()) + list(net.buffers())]
+        live += [opt.state[p]["momentum_buffer"] for opt in (model.G_solver, model.D_solver) for p in opt.param_groups[0]["params"]]
+        seeded = [t.clone() for t in live]
 
         def step(i):
+            with torch.no_grad():
+                torch._foreach_copy_(live, seeded)
             model.adjust_learning_rate(args.lr_g, model.G_solver, i)
             model.adjust_learning_rate(args.lr_d, model.D_solver, i)
             model.set_input(data)
@@ -505,6 +555,8 @@ def main():
     fence()
     el = time.perf_counter() - t0
     recs = _lib.disable_kernel_timing() if (not a.no_kernel_timing and rank == 0 and not teacher_beside) else {}
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, losses)          # before any extra step of --full changes the model
     roofline_steps = None
     if not a.no_kernel_timing and (getattr(model, "_teacher_graph_on", False) or teacher_beside):
         # The roofline kernel lives in the frozen teacher, and in the timed steps the teacher runs on its own stream beside the

@@ -62,7 +62,7 @@ def _private_miopen_db():
             if not _os.path.isdir(dst):
                 _os.makedirs(base, exist_ok=True)
                 tmp = tempfile.mkdtemp(prefix=name + ".", dir=base)
-                shutil.copytree(MIOPEN_DB_DIR, _os.path.join(tmp, "db"))
+                _copy_writable(MIOPEN_DB_DIR, _os.path.join(tmp, "db"))
                 try:
                     _os.rename(_os.path.join(tmp, "db"), dst)      # atomic: concurrent ranks race harmlessly
                 except OSError:
@@ -72,7 +72,7 @@ def _private_miopen_db():
                     path = _os.path.join(base, other)
                     if other.startswith("miopen_db_") and path != dst and _os.path.isdir(path) and _idle_for(path) > 7 * 86400:
                         shutil.rmtree(path, ignore_errors=True)
-            if _os.path.isdir(dst) and _os.access(dst, _os.W_OK):
+            if _os.path.isdir(dst) and _writable(dst):
                 try:
                     _os.utime(dst, None)       # "in use now": a directory's own mtime does not move when MIOpen appends to the files inside
                 except OSError:
@@ -81,6 +81,34 @@ def _private_miopen_db():
         except OSError:
             continue
     return None
+
+
+def _copy_writable(src, dst):
+    """shutil.copytree WITHOUT the source's permission bits: the shipped files may be read-only (a read-only checkout or
+    install), and MIOpen must be able to append to its copy -- a read-only user db / kernel cache fails the first convolution
+    with miopenStatusInternalError."""
+    import shutil
+    for root, _, files in _os.walk(src):
+        out = _os.path.join(dst, _os.path.relpath(root, src))
+        _os.makedirs(out, exist_ok=True)
+        for f in files:
+            shutil.copyfile(_os.path.join(root, f), _os.path.join(out, f))
+    _writable(dst)
+
+
+def _writable(path):
+    """Give the owner write access to everything under ``path`` (a private copy: ours; older versions of this package copied the
+    shipped permission bits); False when that is not possible."""
+    import stat
+    try:
+        for root, dirs, files in _os.walk(path):
+            for p, extra in [(root, stat.S_IRWXU)] + [(_os.path.join(root, f), stat.S_IRUSR | stat.S_IWUSR) for f in files]:
+                mode = _os.stat(p).st_mode
+                if mode & extra != extra:
+                    _os.chmod(p, mode | extra)
+        return all(_os.access(_os.path.join(r, n), _os.W_OK) for r, _, fs in _os.walk(path) for n in fs + [""])
+    except OSError:
+        return False
 
 
 def _idle_for(path):

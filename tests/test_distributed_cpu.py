@@ -738,6 +738,32 @@ def test_bench_solo_rehearsal_prints_a_line_marked_as_rehearsal():
     assert line["comm"]["form"] != "single rank" and line["comm"]["fallback_reason"] is None
 
 
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_run_to_run(tmp_path):
+    """``bench.py --dump-outputs DIR``: the last timed step's losses, both networks' logits and the fixed weight samples as .npy
+    (float32 / float64, at most 64 MB), the same arrays from two runs with the same arguments."""
+    import numpy as np
+    args = ["--gpus", "1", "--device", "cpu", "--size", "256", "--batch", "1", "--losses", "pi,pa", "--steps", "2", "--warmup", "1"]
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p, lines = _launch_bench(args + ["--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert len(lines) == 1 and lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrays) == {"losses", "student_logits", "teacher_logits", "student_weights_sample", "discriminator_weights_sample"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        # (not the weights: at batch 1 the pyramid's 1 x 1 stage has one value per channel, its unbiased running_var is not finite)
+        assert all(np.isfinite(arrays[k]).all() for k in ("losses", "student_logits", "teacher_logits"))
+        assert arrays["student_logits"].shape == arrays["teacher_logits"].shape == (1, 19, 33, 33)
+        logged = lines[0]["config"]["losses_last_step"]
+        assert np.allclose(arrays["losses"], [logged[k] for k in ("G", "mc", "pi", "pa", "D")], rtol=0, atol=1e-6)
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True), k
+
+
 # ---------------------------------------------------------------------------------------------------
 # GradientAllReducer, round 6: a bucket segment has its parameter's strides and BECOMES p.grad after finish() (no unpack copy).
 def _reducer_views(rank, world):

@@ -823,7 +823,7 @@ def test_bench_under_torchrun_two_ranks_over_gloo():
     env = dict(os.environ, SKD_DIST_BACKEND="gloo", MIOPEN_LOG_LEVEL="3")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--no-cpu-baseline"]
+           "--batch", "2", "--full", "--no-cpu-baseline"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

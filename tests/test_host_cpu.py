@@ -437,6 +437,41 @@ def test_miopen_db_is_private_writable_copy_and_version_guard(tmp_path, monkeypa
     assert any("find-db" in str(x.message) for x in w)
 
 
+def test_miopen_db_copy_is_writable_when_the_shipped_db_is_read_only(tmp_path, monkeypatch):
+    """A read-only checkout: the private copy MIOpen appends to must still be writable by its owner (copying the shipped
+    permission bits left MIOpen a read-only user db and kernel cache: miopenStatusInternalError at the first convolution)."""
+    import importlib
+    import shutil
+    import stat
+    import structure_knowledge_distillation_amd as S
+    shipped = tmp_path / "shipped"
+    shutil.copytree(S.MIOPEN_DB_DIR, shipped)
+    for root, dirs, files in os.walk(shipped, topdown=False):
+        for p in [os.path.join(root, f) for f in files] + [root]:
+            os.chmod(p, os.stat(p).st_mode & ~(stat.S_IWUSR | stat.S_IWGRP | stat.S_IWOTH))
+    try:
+        for k in ("MIOPEN_USER_DB_PATH", "MIOPEN_CUSTOM_CACHE_DIR", "MASTER_PORT", "LOCAL_RANK"):
+            monkeypatch.delenv(k, raising=False)
+        monkeypatch.setenv("SKD_MIOPEN_CACHE", str(tmp_path / "cache"))
+        S = importlib.reload(S)
+        monkeypatch.setattr(S, "MIOPEN_DB_DIR", str(shipped))
+        dst = S.configure_miopen(force=True)
+        assert dst.startswith(str(tmp_path / "cache")) and os.path.isdir(os.path.join(dst, "cache"))
+        copied = [os.path.join(r, n) for r, _, fs in os.walk(dst) for n in fs + [""]]
+        assert len(copied) == len([1 for r, _, fs in os.walk(shipped) for n in fs + [""]])
+        assert all(os.stat(p).st_mode & stat.S_IWUSR for p in copied), [oct(os.stat(p).st_mode) for p in copied]
+        # a copy left read-only by an earlier version of the package is made writable again, not handed to MIOpen as it is
+        for p in copied:
+            os.chmod(p, os.stat(p).st_mode & ~stat.S_IWUSR)
+        monkeypatch.delenv("MIOPEN_USER_DB_PATH")
+        monkeypatch.delenv("MIOPEN_CUSTOM_CACHE_DIR")
+        assert S.configure_miopen(force=True) == dst
+        assert all(os.stat(p).st_mode & stat.S_IWUSR for p in copied)
+    finally:
+        for root, dirs, files in os.walk(shipped):
+            os.chmod(root, os.stat(root).st_mode | stat.S_IWUSR)
+
+
 @pytest.mark.parametrize("shape", [(2, 16, 8, 9, 11), (2, 8, 4, 6, 6), (3, 12, 4, 13, 7)])
 def test_psp_fold_equals_concat_then_convolution(shape, monkeypatch):
     """PSPModule's folded bottleneck (conv3x3(feats) + fold(priors x W), csrc/ppm.hip) against the reference sequence

@@ -25,14 +25,14 @@ for sec in "$@"; do
       (timeout 300 python -c "import __graft_entry__ as g; g.smoke()") > $O/smoke.log 2>&1
       stamp "smoke rc=$?"; tail -7 $O/smoke.log | tee -a $O/session.log ;;
     bench)
-      (timeout 600 python bench.py) > $O/bench.json 2> $O/bench.err
+      (timeout 600 python bench.py --full) > $O/bench.json 2> $O/bench.err
       stamp "bench rc=$?"; cut -c1-1500 $O/bench.json | tee -a $O/session.log ;;
     bench_quick)
-      (timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pairwise-sweep) > $O/bench_quick.json 2> $O/bench_quick.err
+      (timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pairwise-sweep) > $O/bench_quick.json 2> $O/bench_quick.err
       stamp "bench_quick rc=$?"; cut -c1-1200 $O/bench_quick.json | tee -a $O/session.log ;;
     bench_prof)
       (cd /tmp && timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o bench -- \
-        python $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-pairwise-sweep > $O/prof_bench.log 2>&1)
+        python $R/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline --no-pairwise-sweep > $O/prof_bench.log 2>&1)
       stamp "bench_prof rc=$?"
       # the roofline kernel per hardware queue: its launches beside the student's forward (teacher stream, timed steps) against its
       # launches on the main stream (the steps bench.py brackets with HIP events)
@@ -101,7 +101,7 @@ EOF
       stamp "dstep rc=$?"; cut -c1-420 $O/d_step_error.jsonl | tee -a $O/session.log ;;
     fused_ab)
       for v in "SKD_ABN_FUSED=1" "SKD_ABN_FUSED=0"; do
-        (env $v timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pairwise-sweep) > "$O/bench_ab_$(echo $v | tr ' =' '__').json" 2>> $O/bench_ab.err
+        (env $v timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pairwise-sweep) > "$O/bench_ab_$(echo $v | tr ' =' '__').json" 2>> $O/bench_ab.err
         stamp "fused_ab $v rc=$?"; cut -c1-260 "$O/bench_ab_$(echo $v | tr ' =' '__').json" | tee -a $O/session.log
       done ;;
     det)
@@ -112,7 +112,7 @@ EOF
       # the three-launch form
       for v in "SKD_ABN_SYNC_FUSED=1" "SKD_ABN_SYNC_FUSED=0"; do
         (env $v SKD_DIST_BACKEND=gloo timeout 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-          --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --batch 4 --no-cpu-baseline) > "$O/bench_2ranks_$(echo $v | tr ' =' '__').json" 2>> $O/bench_2ranks.err
+          --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --batch 4 --no-cpu-baseline) > "$O/bench_2ranks_$(echo $v | tr ' =' '__').json" 2>> $O/bench_2ranks.err
         stamp "dist_ab $v rc=$?"; cut -c1-300 "$O/bench_2ranks_$(echo $v | tr ' =' '__').json" | tee -a $O/session.log
         python - "$O/bench_2ranks_$(echo $v | tr ' =' '__').json" <<'PYEOF' | tee -a $O/session.log
 import json, sys
@@ -200,10 +200,10 @@ PYEOF
         [ "$n" -le "$NG" ] || continue
         port=$((port+1))
         if [ "$n" -eq 1 ]; then
-          (timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pairwise-sweep) > $O/scale_n$n.json 2> $O/scale_n$n.err
+          (timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pairwise-sweep) > $O/scale_n$n.json 2> $O/scale_n$n.err
         else
           (timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-            bench.py --gpus $n --steps 20 --warmup 5) > $O/scale_n$n.json 2> $O/scale_n$n.err
+            bench.py --full --gpus $n --steps 20 --warmup 5) > $O/scale_n$n.json 2> $O/scale_n$n.err
         fi
         stamp "scale8 N=$n rc=$?"; grep '^{' $O/scale_n$n.json | python -c "
 import json, sys
@@ -215,7 +215,7 @@ for l in sys.stdin:
         for v in "SKD_ABN_SYNC_FUSED=1" "SKD_ABN_SYNC_FUSED=1 SKD_ABN_RCCL_RESERVE_CUS=0" "SKD_SYNC_IPC=0" "SKD_TEACHER_GRAPH=force" "SKD_D_GRAPH=1" "SKD_TEACHER_STREAM=1"; do
           port=$((port+1)); f="$O/scale_ab_n${n}_$(echo $v | tr ' =' '__').json"
           (env $v timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $port \
-            bench.py --gpus $n --steps 10 --warmup 3) > "$f" 2>> $O/scale_ab.err
+            bench.py --full --gpus $n --steps 10 --warmup 3) > "$f" 2>> $O/scale_ab.err
           stamp "scale8 A/B $v N=$n rc=$?"; grep '^{' "$f" | python -c "
 import json, sys
 for l in sys.stdin:
@@ -229,7 +229,7 @@ for l in sys.stdin:
       (timeout 200 python tools/rccl_probe.py) > $O/rccl_probe.json 2> $O/rccl_probe.err
       stamp "rccl_probe rc=$?"; cat $O/rccl_probe.json | tee -a $O/session.log
       (SKD_DIST_SOLO=1 timeout 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-        bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-pairwise-sweep) > $O/bench_solo_rccl.json 2> $O/bench_solo_rccl.err
+        bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --no-pairwise-sweep) > $O/bench_solo_rccl.json 2> $O/bench_solo_rccl.err
       stamp "bench solo (torchrun, RCCL, one rank) rc=$?"; cut -c1-900 $O/bench_solo_rccl.json | tee -a $O/session.log
       python - $O/bench_solo_rccl.json <<'EOF' | tee -a $O/session.log
 import json, sys
@@ -279,7 +279,7 @@ EOF
       # round 6: `python bench.py --gpus 2` WITHOUT torchrun (the driver's command form): bench.self_launch starts the ranks itself.
       # On a 1-GPU box the two ranks share the device over gloo (SKD_DIST_BACKEND=gloo); without that switch the same command must
       # print the device-count error line and exit 2.
-      (SKD_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 3 --warmup 2 --batch 4 --no-cpu-baseline) > $O/bench_selflaunch.json 2> $O/bench_selflaunch.err
+      (SKD_DIST_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 3 --warmup 2 --batch 4 --no-cpu-baseline) > $O/bench_selflaunch.json 2> $O/bench_selflaunch.err
       stamp "selflaunch (gloo, shared device) rc=$?"; cut -c1-700 $O/bench_selflaunch.json | tee -a $O/session.log
       (timeout 100 python bench.py --gpus 8 --steps 20 --warmup 5) > $O/bench_selflaunch_8.json 2> $O/bench_selflaunch_8.err
       stamp "selflaunch --gpus 8 on this box rc=$? (2 expected on a 1-GPU box)"; cut -c1-400 $O/bench_selflaunch_8.json | tee -a $O/session.log ;;
@@ -348,7 +348,7 @@ d=json.loads([l for l in open('$O/ab_${t}_$i.json') if l.startswith('{')][0]); p
       stamp "ce_lab rc=$?"; cat $O/ce_lab.jsonl | tee -a $O/session.log ;;
     dist)
       SKD_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 2 --batch 4 --no-cpu-baseline > $O/bench_dist.json 2> $O/bench_dist.err
+        --master-port 29517 bench.py --full --gpus 2 --steps 3 --warmup 2 --batch 4 --no-cpu-baseline > $O/bench_dist.json 2> $O/bench_dist.err
       stamp "dist rc=$?"; cut -c1-600 $O/bench_dist.json | tee -a $O/session.log ;;
     tests_r5b)
       # round 5, kernels rewritten this round: fused CE + upsample (cell formulation), channels-last pair-wise pooling, stem max-pool

@@ -60,7 +60,7 @@ def main():
             agg[category(r["Name"])] += int(r["TotalDurationNs"])
             calls[category(r["Name"])] += int(r["Calls"])
         with open(os.path.join(P, tag + "_step_breakdown.md"), "w") as fh:
-            fh.write("# %s: kernel time per step by category\n\n`rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 3 --no-cpu-baseline "
+            fh.write("# %s: kernel time per step by category\n\n`rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 3 --no-cpu-baseline "
                      "--no-pairwise-sweep` (%d steps in the trace: 3 warm-up + 5 timed + -- with the teacher hipGraph on -- 1 + 5 eager-teacher steps for the roofline kernel + 3 kernel-timing steps; "
                      "kernels replayed from the teacher's hipGraph appear as ordinary dispatches)\n\n| category | ms / step | %% | launches / step |\n|---|---|---|---|\n" % (tag, steps))
             for k, v in agg.most_common():
