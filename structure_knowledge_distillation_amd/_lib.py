@@ -12,6 +12,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libskd_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd.h"))
+EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -134,6 +135,13 @@ SIGNATURES = {
     "skd_abn_sync_form_counts": (_I, [_P]),
 }
 
+# Entry points of libskd_hip.so declared in include/skd_eval.h, outside the core ABI above: the plain-C oracle is typed
+# from SIGNATURES alone and does not have them, so an op that needs one asks has_entry() first (tests/test_sliding_eval_cpu.py
+# checks header <-> table <-> exported symbols the way tests/test_abi.py does for the core).
+EXT_SIGNATURES = {
+    "skd_seg_sliding": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -163,13 +171,14 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise SkdLibraryError("libskd_hip.so does not export %s (stale build?)" % name)
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES, EXT_SIGNATURES):
+        for name, (res, args) in table.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise SkdLibraryError("libskd_hip.so does not export %s (stale build?)" % name)
+            fn.restype = res
+            fn.argtypes = args
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -182,6 +191,11 @@ def get():
     if _timing is not None:
         return _TimedLib(load())
     return load()
+
+
+def has_entry(name):
+    """Whether the active back-end (the HIP library, or a test double) provides the extension entry ``name``."""
+    return hasattr(get(), name)
 
 
 # ---- optional per-entry HIP-event timing (bench.py's roofline leg) ---------------------------------

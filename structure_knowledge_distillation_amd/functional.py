@@ -587,6 +587,65 @@ def seg_confusion(logits, target=None, ignore_index=255, confusion=None, want_pr
     return pred, confusion
 
 
+SEG_SLIDING_MAX_CLASSES = 32   # csrc/evaluate_sliding.hip keeps 2 VGPRs per class; the entry point refuses more
+
+
+def seg_sliding(logits, tiles, tile_size, out_size, target=None, ignore_index=255, confusion=None, remap=None, want_pred=True,
+                want_probs=False):
+    """Sliding-window evaluation tail (networks/evaluate.py:70-104, 187-198) as one fused kernel: tile ``t``'s ``logits``
+    (T, C, h, w) are up-sampled (bilinear, align_corners) to ``tile_size``, cropped and accumulated in float64 over the
+    window ``tiles[t] = (y1, x1, y2, x2)`` of the ``out_size`` = (H, W) image in table order; mean over the covering tiles,
+    argmax (first maximum), optional 256-entry uint8 ``remap`` of the written prediction, (C, C) int64 ``confusion``
+    accumulated with the un-remapped prediction over the pixels of ``target`` (H, W) int64 that are not ``ignore_index``.
+    ``tiles``: a host sequence of 4-tuples (checked, then uploaded) or a (T, 4) int32 tensor on the logits' device.
+    Returns (pred (H, W) uint8 or None, probs (H, W, C) float64 or None, confusion [None without target and confusion])."""
+    _lib.require_device(logits, target, confusion, remap)
+    if not _lib.has_entry("skd_seg_sliding"):
+        raise NotImplementedError("the active back-end does not provide skd_seg_sliding (include/skd_eval.h)")
+    lg = _f32c(logits.detach(), "seg_sliding")
+    if lg.dim() != 4:
+        raise ValueError("seg_sliding: logits (T, C, h, w) expected (got %s)" % (tuple(lg.shape),))
+    nt, c, h, w = lg.shape
+    if not 1 <= c <= SEG_SLIDING_MAX_CLASSES:
+        raise ValueError("seg_sliding: 1 <= classes <= %d (got %d)" % (SEG_SLIDING_MAX_CLASSES, c))
+    (th, tw), (H, W) = (int(v) for v in tile_size), (int(v) for v in out_size)
+    if min(th, tw, H, W) <= 0:
+        raise ValueError("seg_sliding: tile_size and out_size must be positive")
+    if torch.is_tensor(tiles):
+        if tiles.dtype != torch.int32 or tiles.device != lg.device or tuple(tiles.shape) != (nt, 4):
+            raise TypeError("seg_sliding: tiles tensor must be (%d, 4) int32 on %s" % (nt, lg.device))
+        tl = tiles if tiles.is_contiguous() else tiles.contiguous()
+    else:
+        rows = [tuple(int(v) for v in t) for t in tiles]
+        if len(rows) != nt:
+            raise ValueError("seg_sliding: %d tiles for %d logit maps" % (len(rows), nt))
+        for y1, x1, y2, x2 in rows:
+            if not (0 <= y1 < y2 <= H and 0 <= x1 < x2 <= W and y2 - y1 <= th and x2 - x1 <= tw):
+                raise ValueError("seg_sliding: tile (%d, %d, %d, %d) does not fit a %d x %d image with %d x %d tiles"
+                                 % (y1, x1, y2, x2, H, W, th, tw))
+        tl = torch.tensor(rows, dtype=torch.int32).reshape(nt, 4).to(lg.device)
+    if target is not None:
+        if target.dtype != torch.int64:
+            raise TypeError("seg_sliding: int64 target expected (got %s)" % target.dtype)
+        if tuple(target.shape[-2:]) != (H, W) or target.numel() != H * W:
+            raise ValueError("seg_sliding: target %s does not match out_size %s" % (tuple(target.shape), (H, W)))
+        tg = target if target.is_contiguous() else target.contiguous()
+        if confusion is None:
+            confusion = torch.zeros((c, c), dtype=torch.int64, device=lg.device)
+    else:
+        tg = None
+    if confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != (c, c) or not confusion.is_contiguous()):
+        raise TypeError("seg_sliding: confusion must be a contiguous (%d, %d) int64 tensor" % (c, c))
+    if remap is not None and (remap.dtype != torch.uint8 or remap.numel() != 256 or not remap.is_contiguous()):
+        raise TypeError("seg_sliding: remap must be 256 contiguous uint8 entries")
+    pred = torch.empty((H, W), dtype=torch.uint8, device=lg.device) if want_pred else None
+    probs = torch.empty((H, W, c), dtype=torch.float64, device=lg.device) if want_probs else None
+    _lib.check(_lib.get().skd_seg_sliding(nt, c, h, w, th, tw, H, W, lg.data_ptr(), tl.data_ptr(), _lib.ptr(tg), int(ignore_index),
+                                          _lib.ptr(remap), _lib.ptr(pred), _lib.ptr(probs), _lib.ptr(confusion), _lib.stream_of(lg)),
+               "skd_seg_sliding")
+    return pred, probs, confusion
+
+
 def pool_out_size(n, k):
     """ceil_mode=True, stride = kernel, no padding."""
     return -(-n // k)
