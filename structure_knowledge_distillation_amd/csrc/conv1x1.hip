@@ -1,4 +1,5 @@
-// conv1x1.hip -- 1x1 convolution + eval-mode InPlace-ABN (+ residual) + activation as ONE fp32-MFMA GEMM for gfx950.
+// conv1x1.hip -- 1x1 convolution + eval-mode InPlace-ABN (+ residual) + activation as ONE GEMM for gfx950: fp32 in, fp32 out,
+// the products on the bf16 MFMA through a three-piece operand split.
 //
 // The frozen teacher (ResNet101, eval, no grad) spends 3.9 ms per step in its BatchNorm passes although every one of
 // them follows a convolution whose output it merely rescales (networks/pspnet_combine.py:65-84: conv1 -> bn1 -> relu,
@@ -6,25 +7,40 @@
 //     Y[M][N] = act( ((X[M][K] . W[N][K]^T - mean[n]) * invstd[n]) * gamma[n] + beta[n]  [+ R[M][N]] ),   M = B*H*W
 // -- the normalisation, the residual add and the ReLU move into the epilogue here: the convolution output is written
 // once, already activated, and the separate 8 / 12 byte-per-element ABN pass disappears.  The
-// epilogue evaluates exactly the formula of abn_apply (bn.cu:146-159 + ReLU) on the accumulator, so nothing is folded
+// epilogue evaluates exactly the formula of abn_apply (bn.cu:146-159 + ReLU) on the fp32 accumulator, so nothing is folded
 // into the weights and checkpoints / state-dict semantics are untouched.
 //
-// Kernel: 128 x 128 output tile per 256-thread workgroup (4 waves, each 64 x 64 = 2 x 2 v_mfma_f32_32x32x2_f32 blocks:
-// exact fp32, 64 accumulator registers), K streamed in tiles of 16 through a double-buffered LDS ring.  Both operands are
-// K-contiguous in memory (activations channels-last, weights (N, K, 1, 1)), and they stay K-contiguous in LDS: rows of
-// 16 + 4 floats, so a lane fetches FOUR consecutive k of its row with one conflict-free ds_read_b128 (row stride 20
-// floats puts the 16 lanes of each of the instruction's four lane groups on 16 distinct 4-bank slots) and feeds four MFMAs
-// from it -- the MFMA's two k-slots (lanes 0-31 / 32-63) are simply assigned k = 0..3 and k = 4..7 of each group of eight,
-// identically for A and B.  Per 8 k: 4 ds_read_b128 -> 16 MFMAs (1024 matrix-pipe cycles), the reads of the next group issued
-// after the first four MFMAs of the current one (sched_group_barrier); per K-tile and thread 4 global float4 loads and 4
-// ds_write_b128.  41 KB of LDS per workgroup, <= 168 VGPRs -> 3 workgroups (3 waves per SIMD) per CU.
-// Measured decomposition of the main loop (tools/gemm_lab variants, profiles/r03f/g_*): LDS reads cost nothing, LDS writes +
-// barrier 4 %, the global loads 13 % (two tiles of look-ahead do not help: not latency); an MFMA-only loop with this tile
-// shape and epilogue reaches 0.60-0.86 of the nominal 157.3 TFLOP/s depending on how well M x N / (128 x 128) divides the
-// 256 CUs and on the sustained clock.
-// Bound: fp32 MFMA (157.3 TFLOP/s); algorithmic flops 2*M*N*K; epilogue traffic 4*M*N (+ 4*M*N residual) bytes.
+// Matrix core.  gfx950 runs v_mfma_f32_32x32x2_f32 at 1/16 of the bf16 MFMA rate and has no xf32, so the fp32 product is built
+// from bf16 MFMAs.  Every fp32 operand a (after the prologue, where there is one) is written as a0 + a1 + a2 on its way from
+// the global-load staging registers into LDS:
+//     a0 = bf16(a),  a1 = bf16(a - a0),  a2 = bf16(a - a0 - a1)        round to nearest even (v_cvt_pk_bf16_f32),
+// both residuals exact in fp32 -- three pieces of 8 significant bits carry the 24 of an fp32 value.  The product is the six
+// terms with i + j <= 2 (a0 b2, a1 b1, a2 b0, a0 b1, a1 b0, a0 b0: the smallest first), each one
+// v_mfma_f32_32x32x16_bf16 per 32 x 32 block and 16 k, all into ONE fp32 accumulator.  The dropped terms a1 b2, a2 b1, a2 b2
+// are below 2^-23 |a b|; measured against the double-precision oracle the result is within 4 x of the exact fp32 fma chain
+// the fp32 MFMA gave (tests/test_conv1x1_split_gpu.py, profiles/r11_conv1x1_split_accuracy.md) and exact on integer data whose
+// sums fit fp32.  Six bf16 MFMAs of 32 cycles replace eight fp32 MFMAs of 64 per 16 k of a block: 2.67 x less matrix-pipe time.
+// Outside the normal range: a finite |a| above the largest bf16 (about 3.39e38) rounds a0 to infinity and an infinite a has
+// an undefined residual, so in both cases the affected outputs are NaN where the fp32 chain would have given +-inf or a finite
+// value (a * 0); a NaN input gives NaN outputs as before.  Pieces below the fp32 normal range (|a| < 2^-102 or so) may be
+// flushed: an absolute error below 2^-126 |b|.  The teacher's activations and weights are nowhere near either end.
+//
+// Kernel: 128 x 128 output tile per 256-thread workgroup (4 waves, each 64 x 64 = 2 x 2 blocks of 32 x 32, 64 accumulator
+// registers), K streamed in tiles of 16 through a double-buffered LDS ring.  Both operands are K-contiguous in memory
+// (activations channels-last, weights (N, K, 1, 1)).  LDS holds three bf16 planes per operand; a lane's fragment for one piece
+// and block is the 8 consecutive k of its row = one ds_read_b128 (lanes 0-31: k 0-7, lanes 32-63: k 8-15), laid out so that a
+// lane half reads 512 contiguous bytes (see kPlaneChunks).  Per K-tile and wave: 12 ds_read_b128 -> 24 MFMAs (768 matrix-pipe
+// cycles); per K-tile and thread 4 global float4 loads, the split (about 5.5 VALU instructions per element) and 12
+// ds_write_b64.  48 KB of LDS per workgroup (+ 16 bytes per input channel for the prologue's table), 136-140 VGPRs, no scratch
+// -> 3 workgroups (3 waves per SIMD) per CU up to K = 256 with the prologue, 2 at K = 512.
+// The fp32-MFMA core this replaces lives on as variant 0 of tools/gemm_lab_kernels.hip for comparison.
+// Bound: per launch the larger of the HBM traffic (4*M*K + 4*N*K + 4*M*N (+ 4*M*N residual) bytes) and 6 bf16 products
+// (12*M*N*K flops at the bf16-MFMA peak); algorithmic flops stay 2*M*N*K, which is what bench.py's roofline leg reports against
+// the fp32-MFMA peak of 157.3 TFLOP/s (its fraction may therefore exceed 1).
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <atomic>
 
 #include "skd_common.hpp"
 
@@ -32,23 +48,32 @@ namespace skd {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// K-tile 16 (round 3, tools/gemm_lab variants 0 / 5, profiles/r03f_gemm_lab_variants.jsonl): the same speed as 32 on the long-K
-// problems and +7 % at K = 256 -- half the LDS per workgroup, so THREE workgroups (12 waves) share a CU and the prologue /
-// epilogue of one tile hides behind two neighbours' MFMAs instead of one.
-constexpr int kTM = 128, kTN = 128, kBK = 16, kLDK = kBK + 4, kMinWG = 3;
+// K-tile 16 = ONE k-step of the bf16 MFMA.  A stage of the LDS ring holds, per operand, three bf16 planes (the pieces of the
+// split) of 128 rows x 16 k: 24,576 bytes, so that THREE workgroups (12 waves) still share a CU at K <= 256 (with the prologue's
+// parameter table: 53,248 bytes each) and the split / prologue / epilogue of one tile hides behind two neighbours' MFMAs.
+constexpr int kTM = 128, kTN = 128, kBK = 16, kMinWG = 3;
 constexpr int kQK = kBK / 4;                               // float4 per panel row
 constexpr int kRPP = kThreads / kQK;                       // panel rows covered by one pass of the workgroup (64)
 constexpr int kRB = kTN / kRPP;                            // float4 of the B panel per thread and K-tile (2); A: TM / kRPP (2 or 1)
-constexpr int kStageFloats = (kTM + kTN) * kLDK;           // 5120 floats = 20,480 bytes
-constexpr size_t kConvLds = sizeof(float) * 2 * kStageFloats;
+// LDS image of one piece of one operand, in 16-byte chunks (8 consecutive k of one row in bf16 = one lane's MFMA fragment):
+//   chunk(h, row) = h * 128 + (row ^ 4 h),   h = k / 8
+// so the 32 lanes of a fragment read's lane half fetch 512 contiguous bytes (ds_read_b128, conflict-free), and the XOR puts the
+// 8-byte stores of the four threads that own one row's 16 k (two per h) on distinct banks within a store's 16-lane group.
+constexpr int kPlaneChunks = 2 * 128;                      // one piece of one operand: 4 KB
+constexpr int kOperandChunks = 3 * kPlaneChunks;           // a0 | a1 | a2
+constexpr int kStageChunks = 2 * kOperandChunks;           // A | B: 1536 chunks = 24,576 bytes
+constexpr size_t kConvLds = sizeof(uint4) * 2 * kStageChunks;
 constexpr int kProMaxK = 512;                             // prologue form: the (4, K) parameter table rides in LDS (<= 8 KB)
 
 __device__ __forceinline__ float inv_std_of(float var, float eps) { return (var != 0.f || eps != 0.f) ? 1.f / sqrtf(var + eps) : 0.f; }
 
-// Per K-tile a thread moves four float4 of the A panel (rows t/8 + 32h, k quad t%8) and four of the B panel from global memory
-// to LDS.  The loads are issued at the top of a trip, the LDS stores after the trip's MFMAs (a whole K-tile of matrix-pipe
-// time for them to land), the staging registers are not loop-carried (nothing for the compiler to copy).
+// Per K-tile a thread moves two (TM = 64: one) float4 of the A panel (rows t/4 + 64h, k quad t%4) and two of the B panel from
+// global memory to LDS.  The loads are issued at the top of a trip, the split and the LDS stores after the trip's MFMAs (a whole K-tile of
+// matrix-pipe time for them to land), the staging registers are not loop-carried (nothing for the compiler to copy).
 template <int TM>          // TM = rows of the output tile: 128, or 64 for the tiles of a launch's last, partial round (see the kernel)
 struct Staging {
   float4 a[TM / kRPP], b[kRB];
@@ -73,10 +98,36 @@ __device__ __forceinline__ float pro_one(float x, float m, float is, float g, fl
   return z < 0.f ? 0.f : z;
 }
 
+// Two fp32 -> two bf16 in one dword, round to nearest even (v_cvt_pk_bf16_f32), and back (exact).
+__device__ __forceinline__ uint32_t pack_bf16(float x, float y) {
+  const f32x2 v = {x, y};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+
+// The three-piece split of four consecutive k of one row: v = p0 + p1 + p2 with p0 = bf16(v), p1 = bf16(v - p0),
+// p2 = bf16(v - p0 - p1); both residuals are exact in fp32 (Sterbenz-like: p0 agrees with v in its leading 8 bits).
+__device__ __forceinline__ void split_store(float4 v, uint2 *dst) {
+  uint2 p0, p1, p2;
+  p0.x = pack_bf16(v.x, v.y);
+  p0.y = pack_bf16(v.z, v.w);
+  v.x -= bf16_lo(p0.x); v.y -= bf16_hi(p0.x); v.z -= bf16_lo(p0.y); v.w -= bf16_hi(p0.y);
+  p1.x = pack_bf16(v.x, v.y);
+  p1.y = pack_bf16(v.z, v.w);
+  v.x -= bf16_lo(p1.x); v.y -= bf16_hi(p1.x); v.z -= bf16_lo(p1.y); v.w -= bf16_hi(p1.y);
+  p2.x = pack_bf16(v.x, v.y);
+  p2.y = pack_bf16(v.z, v.w);
+  dst[0] = p0;
+  dst[2 * kPlaneChunks] = p1;
+  dst[4 * kPlaneChunks] = p2;
+}
+
+// `srow`: this thread's 8-byte slot inside a plane, in uint2 units (see conv1x1_tile); rows 64 apart are 128 slots apart.
 template <bool PRO, int TM>
-__device__ __forceinline__ void stage_store(const Staging<TM> s, float *stage, int srow, const float *ptab, int K, int kq) {
+__device__ __forceinline__ void stage_store(const Staging<TM> s, uint4 *stage, int srow, const float *ptab, int K, int kq) {
   constexpr int kRA = TM / kRPP;
-  float *sa = stage + srow, *sb = stage + TM * kLDK + srow;
+  uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow, *sb = reinterpret_cast<uint2 *>(stage + kOperandChunks) + srow;
   if (PRO) {   // ptab (LDS copy of ppack): mean | invstd | gamma | beta, each K floats; kq = first of this thread's four k
     ProParams pp;
     pp.pm = *reinterpret_cast<const float4 *>(ptab + kq);
@@ -90,61 +141,44 @@ __device__ __forceinline__ void stage_store(const Staging<TM> s, float *stage, i
       v.y = pro_one(v.y, pp.pm.y, pp.pi.y, pp.pg.y, pp.pb.y);
       v.z = pro_one(v.z, pp.pm.z, pp.pi.z, pp.pg.z, pp.pb.z);
       v.w = pro_one(v.w, pp.pm.w, pp.pi.w, pp.pg.w, pp.pb.w);
-      *reinterpret_cast<float4 *>(sa + kRPP * h * kLDK) = v;
+      split_store(v, sa + 2 * kRPP * h);
     }
   } else {
 #pragma unroll
-    for (int h = 0; h < kRA; ++h) *reinterpret_cast<float4 *>(sa + kRPP * h * kLDK) = s.a[h];
+    for (int h = 0; h < kRA; ++h) split_store(s.a[h], sa + 2 * kRPP * h);
   }
 #pragma unroll
-  for (int h = 0; h < kRB; ++h) *reinterpret_cast<float4 *>(sb + kRPP * h * kLDK) = s.b[h];
+  for (int h = 0; h < kRB; ++h) split_store(s.b[h], sb + 2 * kRPP * h);
 }
 
-// One K-tile out of LDS: per group of 8 k conflict-free ds_read_b128 (a0 [, a1], b0, b1: FOUR consecutive k of the lane's row) feed
-// 8 * WM MFMAs; the reads of group g + 1 are issued before the MFMAs of group g (software pipelining in registers).
+// One K-tile out of LDS: 3 (WM + 2) conflict-free ds_read_b128 (the lane's 8 k of its row, per piece and 32-row block) feed
+// 6 * 2 WM bf16 MFMAs: the six products a_i b_j with i + j <= 2, the three smallest first, the four accumulator blocks of the
+// wave in turn inside every product (no MFMA waits for its predecessor's result).
 // Waves 2 x 2, wave tile (TM / 2) x 64 = WM x 2 blocks of 32 x 32 (WM = TM / 64).
 template <int TM>
-__device__ __forceinline__ void tile_mma(const float *stage, f32x16 (&acc)[TM / 64][2]) {
+__device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 64][2]) {
   constexpr int WM = TM / 64;
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
   const int half = lane >> 5, r = lane & 31;
-  const float *pa = stage + (wi + r) * kLDK + half * 4;
-  const float *pb = stage + (TM + wj + r) * kLDK + half * 4;
-  float4 a[WM], b0 = *reinterpret_cast<const float4 *>(pb), b1 = *reinterpret_cast<const float4 *>(pb + 32 * kLDK);
+  const uint4 *pa = stage + half * 128 + ((wi + r) ^ (half * 4));
+  const uint4 *pb = stage + kOperandChunks + half * 128 + ((wj + r) ^ (half * 4));
+  bf16x8 a[WM][3], b[2][3];
 #pragma unroll
-  for (int i = 0; i < WM; ++i) a[i] = *reinterpret_cast<const float4 *>(pa + 32 * i * kLDK);
-  __builtin_amdgcn_sched_group_barrier(0x100, WM + 2, 0);  // the reads of group 0 (the pipeline below is matched in order)
+  for (int p = 0; p < 3; ++p) {
 #pragma unroll
-  for (int g = 0; g < kBK / 8; ++g) {
-    float4 na[WM], nb0 = b0, nb1 = b1;
+    for (int i = 0; i < WM; ++i) a[i][p] = __builtin_bit_cast(bf16x8, pa[p * kPlaneChunks + 32 * i]);
 #pragma unroll
-    for (int i = 0; i < WM; ++i) na[i] = a[i];
-    if (g + 1 < kBK / 8) {
-#pragma unroll
-      for (int i = 0; i < WM; ++i) na[i] = *reinterpret_cast<const float4 *>(pa + 32 * i * kLDK + (g + 1) * 8);
-      nb0 = *reinterpret_cast<const float4 *>(pb + (g + 1) * 8);
-      nb1 = *reinterpret_cast<const float4 *>(pb + 32 * kLDK + (g + 1) * 8);
-    }
-    const float B0[4] = {b0.x, b0.y, b0.z, b0.w}, B1[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int i = 0; i < WM; ++i) {
-        const float av = t == 0 ? a[i].x : t == 1 ? a[i].y : t == 2 ? a[i].z : a[i].w;
-        acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, B0[t], acc[i][0], 0, 0, 0);
-        acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, B1[t], acc[i][1], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < WM; ++i) a[i] = na[i];
-    b0 = nb0; b1 = nb1;
-    // pin the issue order (left alone the scheduler sinks the reads to just before their first use and every group starts
-    // with an exposed LDS round trip): the first k's MFMAs, the next group's reads, the other MFMAs (their matrix-pipe cycles cover them)
-    __builtin_amdgcn_sched_group_barrier(0x008, 2 * WM, 0);
-    if (g + 1 < kBK / 8) __builtin_amdgcn_sched_group_barrier(0x100, WM + 2, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 6 * WM, 0);
+    for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(bf16x8, pb[p * kPlaneChunks + 32 * j]);
   }
+  constexpr int kPA[6] = {0, 1, 2, 0, 1, 0}, kPB[6] = {2, 1, 0, 1, 0, 0};
+#pragma unroll
+  for (int t = 0; t < 6; ++t)
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][kPA[t]], b[j][kPB[t]], acc[i][j], 0, 0, 0);
 }
 
 // Epilogue of one 32 x 32 accumulator block: rows row0 + frag_row(q), column col.  FULL: every row of the tile exists (all
@@ -187,7 +221,7 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
                                              float *__restrict__ Y, const float *__restrict__ mean, const float *__restrict__ var,
                                              const float *__restrict__ weight, const float *__restrict__ bias,
                                              const float *__restrict__ ppack, float eps, float slope, int64_t M, int K, int N,
-                                             int64_t m0, int n0, float *lds) {
+                                             int64_t m0, int n0, uint4 *lds) {
   constexpr int WM = TM / 64, kRA = TM / kRPP;
   f32x16 acc[WM][2];
 #pragma unroll
@@ -198,7 +232,8 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
   const int nk = K / kBK;
   const int gt = threadIdx.x, grow = gt / kQK, gkq = (gt % kQK) * 4;
-  const int srow = grow * kLDK + gkq;
+  const int kh = gkq >> 3;                          // which 8-k half of the K-tile this thread's quad belongs to
+  const int srow = 2 * (kh * 128 + (grow ^ (kh * 4))) + ((gkq >> 2) & 1);   // 8-byte slot of (row grow, k quad) inside a plane
   int64_t arow[kRA];   // rows beyond the matrix are clamped (loaded, multiplied, never stored)
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
@@ -206,7 +241,7 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
     arow[h] = (m > M - 1 ? M - 1 : m) * K;
   }
   const int64_t wrow0 = (int64_t)(n0 + grow) * K;
-  float *ptab = lds + 2 * kStageFloats;             // PRO: the (4, K) parameter table, K <= kProMaxK
+  float *ptab = reinterpret_cast<float *>(lds + 2 * kStageChunks);   // PRO: the (4, K) parameter table, K <= kProMaxK
   if (PRO) {
     for (int i = gt * 4; i < 4 * K; i += kThreads * 4) *reinterpret_cast<float4 *>(ptab + i) = *reinterpret_cast<const float4 *>(ppack + i);
     __syncthreads();
@@ -219,8 +254,8 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
   for (int kt = 0; kt < nk; ++kt) {
     const bool more = kt + 1 < nk;
     if (more) stage_load<PRO, TM>(st, X, Wt, (kt + 1) * kBK, gkq, arow, wrow0, K);
-    tile_mma<TM>(lds + stage * kStageFloats, acc);
-    if (more) stage_store<PRO, TM>(st, lds + (stage ^ 1) * kStageFloats, srow, ptab, K, (kt + 1) * kBK + gkq);
+    tile_mma<TM>(lds + stage * kStageChunks, acc);
+    if (more) stage_store<PRO, TM>(st, lds + (stage ^ 1) * kStageChunks, srow, ptab, K, (kt + 1) * kBK + gkq);
     __syncthreads();
     stage ^= 1;
   }
@@ -251,7 +286,7 @@ __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
     const float *__restrict__ bias, const float *__restrict__ ppack, float eps, float slope, int64_t M, int K, int N,
     int tiles_n, int pm, int ct, int p_full) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+  extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   // XCD-aware tile order.  Workgroup b runs on XCD b % 8 (observed placement, MI355X_MICROARCH.md; used for traffic only, any
   // placement is correct) and every XCD has its own L2: the tiles_n workgroups that share one 128 x K activation panel are
   // therefore given to ONE XCD, back to back in its dispatch order -- the panel is fetched into one L2 instead of eight.
@@ -304,6 +339,22 @@ __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, c
   pack[3 * (int64_t)K + k] = bias != nullptr ? bias[k] : 0.f;
 }
 
+// Compute units of the device that `st` belongs to (0: unknown).  Queried once per device; the table is atomic because the
+// teacher stream and the main stream may reach their first launch from different host threads (a second query stores the same value).
+static int cu_count(hipStream_t st) {
+  static std::atomic<int> cus[64];
+  int dev = -1;
+  if (hipStreamGetDevice(st, &dev) != hipSuccess) {
+    (void)hipGetLastError();             // not an error of the launch that follows
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+  }
+  if (dev < 0 || dev >= 64) return 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0 && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+    cus[dev].store(n, std::memory_order_relaxed);
+  return n > 0 ? n : 0;
+}
+
 template <int ACT, bool HAS_RES, bool PRO, bool NT = false>
 static int launch(const float *X, const float *Wt, const float *R, float *Y, const float *mean, const float *var,
                   const float *weight, const float *bias, const float *ppack, float eps, float slope, int64_t M, int K, int N,
@@ -332,23 +383,12 @@ static int launch(const float *X, const float *Wt, const float *R, float *Y, con
   // half-height panels for the last, partial round; slots = 3 workgroups per compute unit
   int64_t p_full = tiles_m, panels = tiles_m;
   {
-    static PerDeviceFlag cu_known;
-    static int cus[64] = {};
-    bool *known = cu_known.get();
-    int dev = 0;
-    if (known != nullptr && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-      if (!*known) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus[dev] = n;
-        *known = true;
-      }
-      const int64_t slots = (int64_t)kMinWG * cus[dev];
-      const int64_t tiles = tiles_m * tiles_n;
-      if (slots > 0 && tiles > slots && tiles % slots != 0) {
-        p_full = (tiles / slots) * slots / tiles_n / 8 * 8;            // whole rounds, whole XCD rows of panels
-        const int64_t rest_rows = M - p_full * kTM;
-        panels = p_full + cdiv(rest_rows, kTM / 2);
-      }
+    const int64_t slots = (int64_t)kMinWG * cu_count(st);
+    const int64_t tiles = tiles_m * tiles_n;
+    if (slots > 0 && tiles > slots && tiles % slots != 0) {
+      p_full = (tiles / slots) * slots / tiles_n / 8 * 8;            // whole rounds, whole XCD rows of panels
+      const int64_t rest_rows = M - p_full * kTM;
+      panels = p_full + cdiv(rest_rows, kTM / 2);
     }
   }
   const int64_t panels_per_xcd = cdiv(cdiv(panels, 8), pm) * pm;   // row panels padded to whole groups on each of the 8 XCDs

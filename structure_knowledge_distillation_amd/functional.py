@@ -477,7 +477,9 @@ def conv1x1_bn_blas(x, conv, bn, relu):
     eval-mode normalisation folds into it -- W' = W * s, b' = beta - mean * s, s = (|gamma| + eps) / sqrt(var + eps) -- and
     rocBLAS / hipBLASLt run that GEMM faster than MIOpen's implicit-GEMM convolution on the teacher's reduce layers
     (1024 -> 256 at 65 x 65, batch 8: 144 us with the epilogue vs 175 us convolution + 27 us ABN pass;
-    profiles/r02d_conv1x1_blas.jsonl), exact fp32 (no xf32 on gfx950).  The folded operands are cached on the BN module."""
+    profiles/r02d_conv1x1_blas.jsonl), exact fp32 (no xf32 on gfx950).  The folded operands are cached on the BN module.
+    In isolation the split-operand kernel behind conv1x1_abn_eval is now faster on most of these shapes (1024 -> 256 at
+    65 x 65: 130 us against 146-155, profiles/r11_stage2_isolated.md); routing them there waits for an A/B on the step."""
     key = tuple((t.data_ptr(), t._version) for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None)
     fold = getattr(bn, "_blas_fold", None)
     if fold is None or fold[0] != key:
@@ -529,9 +531,12 @@ def abn_pack_eval_params(bn):
 
 def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
                      residual=None, pro=None):
-    """act(bn_running(conv1x1(x)) [+ residual]) as ONE fp32-MFMA GEMM with the normalisation in its epilogue (inference
-    only; networks/pspnet_combine.py:65-84 for the frozen teacher).  x (B, Cin, H, W) and residual / result
-    (B, Cout, H, W) in channels-last memory; conv_weight (Cout, Cin, 1, 1).
+    """act(bn_running(conv1x1(x)) [+ residual]) as ONE GEMM with the normalisation in its epilogue (inference only;
+    networks/pspnet_combine.py:65-84 for the frozen teacher).  fp32 in and out; the products run on the bf16 MFMA with both
+    operands split into three bf16 pieces and the six leading products accumulated in fp32 (csrc/conv1x1.hip): within 4 x of
+    an fp32 fma chain's error against a double-precision product, at most 2e-6 of the output's largest magnitude
+    (tests/test_conv1x1_split_gpu.py), exact on integer data; inputs beyond +-3.39e38 or infinite give NaN.  x (B, Cin, H, W)
+    and residual / result (B, Cout, H, W) in channels-last memory; conv_weight (Cout, Cin, 1, 1).
     ``pro`` = ``abn_pack_eval_params(bn)`` of an eval-mode BatchNorm + ReLU that PRECEDES the convolution
     (bn2 -> relu -> conv3, pspnet_combine.py:71-75): applied to x on its way into the GEMM, x itself is left untouched."""
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
