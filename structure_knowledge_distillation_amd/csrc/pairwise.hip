@@ -531,25 +531,25 @@ __device__ __forceinline__ void tile_gemm(const Seg s0, const Seg s1, float *lds
 // C/D fragment coordinates of v_mfma_f32_32x32x2_f32: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 __device__ __forceinline__ int frag_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
-// gram + loss.  G is symmetric, so only the nt*(nt+1)/2 tiles with ti <= tj are computed: an off-diagonal
+// gram + loss.  G is symmetric, so only the ntiles*(ntiles+1)/2 tiles with ti <= tj are computed: an off-diagonal
 // tile counts twice in the loss and is stored twice (as is, and transposed into the mirror position, 16 bytes
 // per lane per store: the C/D fragment holds 4 consecutive rows per register quad).
-// grid = (nt*(nt+1)/2 * (128 / TI), B): blockIdx.x -> (ti, tj) by walking the rows of the upper triangle; TI = 64: two workgroups
+// grid = (ntiles*(ntiles+1)/2 * (128 / TI), B): blockIdx.x -> (ti, tj) by walking the rows of the upper triangle; TI = 64: two workgroups
 // per 128 x 128 tile (its upper and its lower 64 rows), twice the workgroups of half the size for graphs that do not fill the chip.
 template <int TI>
 __global__ __launch_bounds__(kThreads, TI == kTile ? 2 : 3) void gram_loss_kernel(const float *__restrict__ fs,
                                                                 const float *__restrict__ ft,
                                                                 float *__restrict__ G,
                                                                 float *__restrict__ part, int Cs,
-                                                                int Ct, int ldm, int nt) {
+                                                                int Ct, int ldm, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // Panels<TI>::lds_bytes
   __shared__ float red[2 * kWavesPerWG];
   constexpr int HALVES = kTile / TI, WM = TI / 64;
   const int b = blockIdx.y;
   const int half = HALVES == 1 ? 0 : (int)(blockIdx.x % HALVES);
   int ti = 0, rem = blockIdx.x / HALVES;
-  while (rem >= nt - ti) {
-    rem -= nt - ti;
+  while (rem >= ntiles - ti) {
+    rem -= ntiles - ti;
     ++ti;
   }
   const int tj = ti + rem;
@@ -945,8 +945,8 @@ int skd_channel_l2_normalise(int B, int C, int M, const float *pooled, float *fh
 
 int64_t skd_pairwise_workspace_floats(int B, int M) {
   if (B <= 0 || M <= 0) return 1;
-  const int64_t nt = cdiv(M, kTile);
-  return nt * (nt + 1) / 2 * B * 2;          // (x 2: the half-height tiles of small graphs write one partial each)
+  const int64_t ntiles = cdiv(M, kTile);
+  return ntiles * (ntiles + 1) / 2 * B * 2;          // (x 2: the half-height tiles of small graphs write one partial each)
 }
 
 static bool gemm_lds_ready() {
@@ -975,17 +975,17 @@ int skd_pairwise_gram_loss(int B, int Cs, int Ct, int M, int ldm, const float *f
   if (ldm != skd_pairwise_ldm(M) || B > 65535) return 0;
   if ((reinterpret_cast<uintptr_t>(fhat_s) | reinterpret_cast<uintptr_t>(fhat_t)) & 15) return 0;
   hipStream_t st = as_stream(stream);
-  const int nt = ldm / kTile;
-  const int ntri = nt * (nt + 1) / 2;
+  const int ntiles = ldm / kTile;
+  const int ntri = ntiles * (ntiles + 1) / 2;
   if (!gemm_lds_ready()) return 0;
   // fewer 128 x 128 tiles than two rounds of the chip's 512 slots: half-height tiles, twice the workgroups (M = 1089: 720 instead of 360)
   const int halves = (int64_t)ntri * B < 1024 ? 2 : 1;
   if (halves == 2)
     gram_loss_kernel<64><<<dim3((unsigned)ntri * 2, B), dim3(kThreads), Panels<64>::lds_bytes, st>>>(fhat_s, fhat_t, G, workspace, Cs,
-                                                                                                     Ct, ldm, nt);
+                                                                                                     Ct, ldm, ntiles);
   else
     gram_loss_kernel<kTile><<<dim3((unsigned)ntri, B), dim3(kThreads), Panels<kTile>::lds_bytes, st>>>(fhat_s, fhat_t, G, workspace,
-                                                                                                         Cs, Ct, ldm, nt);
+                                                                                                         Cs, Ct, ldm, ntiles);
   if (!ok()) return 0;
   // utils.py:181: / (M*M) / B
   return launch_final_sum(workspace, (int64_t)ntri * halves * B, loss, 1.0 / ((double)M * (double)M) / (double)B, st);

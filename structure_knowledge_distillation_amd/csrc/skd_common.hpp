@@ -17,7 +17,7 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- device-raised error words (status.hip; include/skd.h section 13) -------------------------------------------
 constexpr int kStatusWords = 4;
-constexpr int kStatusSyncTimeout = 0;    // a cross-replica mailbox exchange gave up waiting for a peer (sync.hip, abn.hip)
+constexpr int kStatusSyncTimeout = 0;    // a cross-replica mailbox exchange gave up waiting for a peer (sync.hip, abn_fused.hip)
 constexpr int kStatusFusedTimeout = 1;   // the grid barrier of a one-launch InPlace-ABN pass timed out: grid not co-resident
 // host-mapped, system-coherent buffer of kStatusWords words as a DEVICE pointer (nullptr: allocation failed -> not reported)
 unsigned *status_words();

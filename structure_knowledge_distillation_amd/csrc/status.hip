@@ -1,7 +1,7 @@
 // status.hip -- device-raised error words the host reads WITHOUT synchronising the device (include/skd.h section 13).
 //
 // Two kernels of this library wait inside a launch: the cross-replica mailbox exchange (sync.hip: for the peers' flags)
-// and the register-resident one-launch InPlace-ABN passes (abn.hip: a grid barrier per channel block).  Both waits are
+// and the register-resident one-launch InPlace-ABN passes (abn_fused.hip: a grid barrier per channel block).  Both waits are
 // bounded, and a wait that runs out used to poison its outputs with NaN and nothing else: the fast rank got
 // NaN statistics, the late rank finished normally, and the gradient all-reduce then spread the NaN to every replica with
 // no host-visible cause.  Now the kernel that gives up ALSO stores a code into a small host-mapped, system-coherent buffer

@@ -6,7 +6,7 @@
 // message).  Per-channel statistics are tiny; what matters is latency.  On an 8 x MI355X node every GPU reaches every other
 // GPU in ONE xGMI hop and can store into its memory directly, so the exchange is a single small kernel:
 //
-// (Device side: sync_dev.hpp, shared with the fused forms in abn.hip.)
+// (Device side: sync_dev.hpp, shared with the fused forms in abn_fused.hip.)
 //   mailbox   every rank owns one device buffer (uncached / fine-grained: hipDeviceMallocUncached, the allocation type RCCL
 //             uses for its own flags) and exports it with hipIpcGetMemHandle; every rank opens all the others'.
 //             Layout: [parity 2][writer G][ 4 flag words (one per channel block) | pad to 64 B | payload kSyncMaxFloats floats ].

@@ -1,5 +1,5 @@
 // sync_dev.hpp -- device side of the one-hop mailbox exchange (sync.hip), shared with the one-launch InPlace-ABN passes of
-// abn.hip that perform the exchange INSIDE the statistics kernel (round 4).
+// abn_fused.hip that perform the exchange INSIDE the statistics kernel (round 4).
 //
 //   mailbox   [parity 2][writer G][ 16-word header | payload kSyncMaxFloats floats ]; header word k (k < 4) is the flag
 //             of CHANNEL BLOCK k of that writer's payload (a plain all-gather uses word 0 only).
@@ -8,7 +8,7 @@
 //             same words of all G writers in its OWN mailbox, system-scope acquire.
 // Flags are per channel block so that the two forms of an exchange interoperate: the stand-alone kernel (one workgroup,
 // all channel blocks: sync.hip) and the fused form in which the last-arriving workgroup of EACH channel block of a
-// register-resident ABN launch exchanges its own block (abn.hip).  Which form a rank takes depends on whether ITS tensor
+// register-resident ABN launch exchanges its own block (abn_fused.hip).  Which form a rank takes depends on whether ITS tensor
 // fits the register file -- with ragged shards that differs between ranks -- and must not matter to the protocol: one
 // exchange = one sequence number on every rank, one flag word per (writer, channel block), the same payload layout.
 #pragma once
@@ -19,7 +19,7 @@ namespace skd {
 constexpr int kSyncMaxWorld = 16;
 constexpr int kSyncMaxFloats = 4096;                 // payload floats per slot (2 * C for C <= 2048)
 constexpr int kSlotHeaderFloats = 16;                // flag words + padding: the payload starts 64 bytes into the slot
-constexpr int kSyncFlagWords = 4;                    // one per channel block (kRedMaxCB of abn.hip)
+constexpr int kSyncFlagWords = 4;                    // one per channel block (kRedMaxCB of abn_dev.hpp)
 constexpr int kSlotFloats = kSlotHeaderFloats + kSyncMaxFloats;
 constexpr uint64_t kSyncTicksPerSecond = 100000000ull;   // wall_clock64(): 100 MHz
 
@@ -36,7 +36,7 @@ struct SyncArgs {
   unsigned *status;        // device-raised error words (status.hip) or nullptr
 };
 
-// channel blocks of a C-channel statistics vector: the split of abn.hip's channels-last reductions (make_red_geom)
+// channel blocks of a C-channel statistics vector: the split of the channels-last reductions (abn_dev.hpp: make_red_geom)
 __host__ __device__ __forceinline__ int sync_channel_blocks(int C) {
   if (C < 4 || (C & (C - 1)) || C > 1024) return 1;       // shapes the channels-last kernels do not take: one block
   return C >= 256 ? 4 : (C >= 128 ? 2 : 1);
@@ -123,7 +123,7 @@ __device__ __forceinline__ float sync_weighted_sum(const SyncDev &d, unsigned se
 }  // namespace skd
 
 // sync.hip: the launch arguments of the NEXT exchange of a context (bumps its sequence number); false when ctx is not a
-// connected context.  Host side of the fused forms in abn.hip.
+// connected context.  Host side of the fused forms in abn_fused.hip.
 namespace skd {
 bool sync_next(void *ctx, SyncArgs &out);
 }

@@ -2,7 +2,7 @@
 
 Mirrors the *contract* of the reference's libs/functions.py:70-309 (in-place on the conv output,
 forward output saved for backward, not double-differentiable, ValueError on non-contiguous input,
-RuntimeError when a native call reports failure) on top of the fused kernels of csrc/abn.hip:
+RuntimeError when a native call reports failure) on top of the fused kernels of csrc/abn*.hip:
 
     reference (per layer, training)                  here
     ---------------------------------------------    -------------------------------------------
@@ -375,7 +375,7 @@ class _InPlaceABN(autograd.Function):
         if dx is None and geo.nhwc:
             dx = torch.empty_like(z)        # the channels-last dx entry always writes dx
         if ctx.training and ctx.group is None and geo.nhwc:
-            # reduce + dx in one call: one register-resident launch when the tensor fits (csrc/abn.hip), else two
+            # reduce + dx in one call: one register-resident launch when the tensor fits (csrc/abn_fused.hip), else two
             ws = geo.workspace(lib, z)
             _lib.check(lib.skd_abn_backward_nhwc(geo.rows, c, z.data_ptr(), dz.data_ptr(), var.data_ptr(), _lib.ptr(weight),
                                                  _lib.ptr(bias), edz.data_ptr(), eydz.data_ptr(), dx.data_ptr(),
@@ -404,7 +404,7 @@ class _InPlaceABN(autograd.Function):
 
 
 class _ABNRelu(autograd.Function):
-    """Training-time ``relu(bn(x) [+ residual])`` as one op (csrc/abn.hip, "out of place" sections).
+    """Training-time ``relu(bn(x) [+ residual])`` as one op (csrc/abn.hip "out of place" section, csrc/abn_nhwc.hip, csrc/abn_fused.hip).
 
     The reference runs InPlace-ABN(activation='none') and then nn.ReLU -- at the tail of a residual block
     ``out + residual`` in between (networks/pspnet_combine.py:36-43, 68-82) -- keeping z and relu(z) alive.  Here the
@@ -553,7 +553,7 @@ def abn_relu_train(x, weight, bias, running_mean, running_var, residual=None, mo
 
 class _ABNReluMaxPool(autograd.Function):
     """Training-time ``maxpool3x3s2(relu(bn_batch(x)))`` of the student's stem (networks/pspnet_combine.py:176-180: bn3 -> relu3 ->
-    maxpool on the (B, 128, 256, 256) conv3 output) WITHOUT the normalised tensor (csrc/abn.hip, "student stem"): forward =
+    maxpool on the (B, 128, 256, 256) conv3 output) WITHOUT the normalised tensor (csrc/abn_stem.hip): forward =
     statistics + ONE kernel that normalises, rectifies and pools on the fly (68 MB written instead of 268 + 68, argmax as one byte
     per element); backward = the edz / eydz reduction and the dx pass, both gathering the pooled gradient through the argmax bytes
     and recomputing the ReLU mask from x.  Values, indices and gradients are those of abn_relu_train followed by the stem pool

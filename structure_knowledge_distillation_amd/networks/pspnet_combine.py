@@ -4,7 +4,7 @@ Same public surface, module names and state-dict keys as the reference's
 networks/pspnet_combine.py:114-197 (150 tensors student / 565 teacher), so its checkpoints load
 and ``forward`` returns the same 7-element list ``[logits, dsn, feat_after_psp, x4, x3, x2, x1]``
 (pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm; every normalisation is
-the hand-written InPlace-ABN of csrc/abn.hip (``libs``), applied in place on the conv output.
+the hand-written InPlace-ABN of csrc/abn*.hip (``libs``), applied in place on the conv output.
 """
 import functools
 
@@ -295,7 +295,7 @@ class ResNet(nn.Module):
             if _fused(self, x):
                 x = self.bn1.forward_relu(self.conv1(x))
                 x = self.bn2.forward_relu(self.conv2(x))
-                # training: bn3 -> relu3 -> maxpool in two fused passes per direction (csrc/abn.hip "student stem", round 6): the
+                # training: bn3 -> relu3 -> maxpool in two fused passes per direction (csrc/abn_stem.hip, round 6): the
                 # 268 MB normalised conv3 output is never written, its gradient never un-pooled into memory; STEM_FUSED = False or an
                 # input the fused kernels do not take: forward_relu, then csrc/maxpool.hip (channels-last) / the stock pool
                 x = (self.bn3.forward_relu_maxpool(self.conv3(x), self.maxpool) if STEM_FUSED

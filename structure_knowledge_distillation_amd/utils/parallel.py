@@ -108,7 +108,7 @@ def comm_form(group=None):
         return "torch.distributed all_gather / all_reduce per exchange (SKD_SYNC_IPC=0 or the mailbox self-test failed)"
     from .. import _lib
     if sync_fused() and _lib.get().skd_abn_get_fused():
-        return "ipc mailboxes, exchange inside the one-launch ABN kernels where the tensor fits (csrc/abn.hip, sync_dev.hpp)"
+        return "ipc mailboxes, exchange inside the one-launch ABN kernels where the tensor fits (csrc/abn_fused.hip, sync_dev.hpp)"
     return "ipc mailboxes, three launches per pass: statistics / one-workgroup exchange kernel / normalise (csrc/sync.hip)"
 
 

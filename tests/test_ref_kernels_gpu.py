@@ -125,7 +125,7 @@ def test_mean_var_with_an_outlier_where_the_old_pivot_sat(libs, shape):
     """K1 robustness: the product's statistics are ONE pass around a per-channel pivot; the reference
     is two-pass (bn.cu:125-138).  One element 300 sigma off the channel mean at (n, h, w) = (0, 0, 0) -- the element the
     single-sample pivot of rounds 1-2 used -- cost 6e-4 of relative accuracy on the variance; the median-of-three pivot
-    (csrc/abn.hip: median3) keeps it at the fp32 level, for the NCHW entry and the channels-last entry alike."""
+    (csrc/abn_dev.hpp: median3) keeps it at the fp32 level, for the NCHW entry and the channels-last entry alike."""
     nat, ref, hip = libs
     N, C, S = shape
     g = torch.Generator().manual_seed(N * 1000 + C)

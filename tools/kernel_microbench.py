@@ -172,7 +172,7 @@ def build_cases(lib, torch, dev, st):
         4 * B_ * C_ * Hh * Ww + 5 * B_ * C_ * OH * OW, keep=(mx, my, mdy, mdx, marg))
     add("maxpool3x3s2_backward_nhwc", [B_, C_, Hh, Ww], lambda: lib.skd_maxpool3x3s2_backward_nhwc(B_, C_, Hh, Ww, OH, OW, p(mdy), p(marg), p(mdx), st),
         4 * B_ * C_ * Hh * Ww + 5 * B_ * C_ * OH * OW)
-    # round 6, the training stem fused (csrc/abn.hip "student stem"): forward = read x once, write pooled + argmax; backward reduce =
+    # round 6, the training stem fused (csrc/abn_stem.hip): forward = read x once, write pooled + argmax; backward reduce =
     # read x + (pooled gradient, argmax); backward dx = the same + write dx
     smean, svar = torch.zeros(C_, device=dev), torch.ones(C_, device=dev)
     sgam, sbet = torch.ones(C_, device=dev), torch.zeros(C_, device=dev)
