@@ -33,6 +33,29 @@ int skd_seg_sliding(int T, int C, int h, int w, int tile_h, int tile_w, int H, i
                     const int *tiles, const int64_t *target, int ignore_index, const uint8_t *remap, uint8_t *pred,
                     double *probs, int64_t *confusion, skd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * 3x3 stride-1 "same" convolution of a FROZEN network as an implicit GEMM on the split-operand bf16-MFMA core
+ * (csrc/conv3x3.hip; the core and its numerics: csrc/conv1x1.hip), inference only:
+ *   out[b][h][w][n] = act( ((sum_{ty,tx,c} x[b][h + (ty-1) d][w + (tx-1) d][c] * w[n][c][ty][tx] + conv_bias[n] - mean[n])
+ *                           * invstd[n]) * (|weight[n]| + eps) + bias[n] ),     taps outside the image are exact zeros;
+ *   x (B, H, W, Cin) and out (B, H, W, Cout) channels-last fp32, x 16-byte aligned; any H, W >= 1 and dilation d >= 1.
+ *   conv_bias NULL: none.  mean / var NULL (both): no normalisation (weight / bias ignored); with them, weight / bias may be
+ *   NULL (gamma 1, beta 0) -- the eval-mode InPlace-ABN formula of skd_conv1x1_abn_nhwc.  activation: SKD_ACT_*.
+ * skd_conv3x3_split_supported(): Cin % 16 == 0, Cout % 128 == 0, stride 1, padding == dilation >= 1, groups 1.
+ * The weight is split ONCE into three bf16 planes laid out as the kernel's LDS image: skd_conv3x3_split_pack_bytes() bytes
+ * (6 per weight), 16-byte aligned, written by skd_conv3x3_split_pack_weights() from a (Cout, Cin, 3, 3) fp32 tensor of ANY
+ * memory format -- stride_* are its strides in elements.  A frozen network packs once; re-pack when the weight changes.
+ * geometry: 0 = the shipped choice per problem size; for measurements 1 = 128-pixel x 128-channel tiles, 2 = 64-pixel tiles,
+ * 3 = 128-pixel tiles for the launch's whole rounds and 64 for the rest.  Same result for every geometry.
+ * ---------------------------------------------------------------------------------- */
+int skd_conv3x3_split_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups);
+int64_t skd_conv3x3_split_pack_bytes(int Cin, int Cout);
+int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                   int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream);
+int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                           const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                           float eps, int activation, float slope, int geometry, skd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

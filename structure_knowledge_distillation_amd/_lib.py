@@ -140,6 +140,10 @@ SIGNATURES = {
 # checks header <-> table <-> exported symbols the way tests/test_abi.py does for the core).
 EXT_SIGNATURES = {
     "skd_seg_sliding": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "skd_conv3x3_split_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "skd_conv3x3_split_pack_bytes": (_L, [_I, _I]),
+    "skd_conv3x3_split_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
+    "skd_conv3x3_split_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
 }
 
 _lib = None

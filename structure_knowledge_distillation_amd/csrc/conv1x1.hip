@@ -40,36 +40,13 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <atomic>
-
-#include "skd_common.hpp"
+#include "conv_split_dev.hpp"
 
 namespace skd {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// K-tile 16 = ONE k-step of the bf16 MFMA.  A stage of the LDS ring holds, per operand, three bf16 planes (the pieces of the
-// split) of 128 rows x 16 k: 24,576 bytes, so that THREE workgroups (12 waves) still share a CU at K <= 256 (with the prologue's
-// parameter table: 53,248 bytes each) and the split / prologue / epilogue of one tile hides behind two neighbours' MFMAs.
-constexpr int kTM = 128, kTN = 128, kBK = 16, kMinWG = 3;
-constexpr int kQK = kBK / 4;                               // float4 per panel row
-constexpr int kRPP = kThreads / kQK;                       // panel rows covered by one pass of the workgroup (64)
-constexpr int kRB = kTN / kRPP;                            // float4 of the B panel per thread and K-tile (2); A: TM / kRPP (2 or 1)
-// LDS image of one piece of one operand, in 16-byte chunks (8 consecutive k of one row in bf16 = one lane's MFMA fragment):
-//   chunk(h, row) = h * 128 + (row ^ 4 h),   h = k / 8
-// so the 32 lanes of a fragment read's lane half fetch 512 contiguous bytes (ds_read_b128, conflict-free), and the XOR puts the
-// 8-byte stores of the four threads that own one row's 16 k (two per h) on distinct banks within a store's 16-lane group.
-constexpr int kPlaneChunks = 2 * 128;                      // one piece of one operand: 4 KB
-constexpr int kOperandChunks = 3 * kPlaneChunks;           // a0 | a1 | a2
-constexpr int kStageChunks = 2 * kOperandChunks;           // A | B: 1536 chunks = 24,576 bytes
-constexpr size_t kConvLds = sizeof(uint4) * 2 * kStageChunks;
+// The core (split, LDS image, MFMA tile, block epilogue) is conv_split_dev.hpp, shared with conv3x3.hip.
 constexpr int kProMaxK = 512;                             // prologue form: the (4, K) parameter table rides in LDS (<= 8 KB)
-
-__device__ __forceinline__ float inv_std_of(float var, float eps) { return (var != 0.f || eps != 0.f) ? 1.f / sqrtf(var + eps) : 0.f; }
 
 // Per K-tile a thread moves two (TM = 64: one) float4 of the A panel (rows t/4 + 64h, k quad t%4) and two of the B panel from
 // global memory to LDS.  The loads are issued at the top of a trip, the split and the LDS stores after the trip's MFMAs (a whole K-tile of
@@ -96,31 +73,6 @@ __device__ __forceinline__ void stage_load(Staging<TM> &s, const float *__restri
 __device__ __forceinline__ float pro_one(float x, float m, float is, float g, float b) {
   const float z = __builtin_fmaf((x - m) * is, g, b);
   return z < 0.f ? 0.f : z;
-}
-
-// Two fp32 -> two bf16 in one dword, round to nearest even (v_cvt_pk_bf16_f32), and back (exact).
-__device__ __forceinline__ uint32_t pack_bf16(float x, float y) {
-  const f32x2 v = {x, y};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-
-// The three-piece split of four consecutive k of one row: v = p0 + p1 + p2 with p0 = bf16(v), p1 = bf16(v - p0),
-// p2 = bf16(v - p0 - p1); both residuals are exact in fp32 (Sterbenz-like: p0 agrees with v in its leading 8 bits).
-__device__ __forceinline__ void split_store(float4 v, uint2 *dst) {
-  uint2 p0, p1, p2;
-  p0.x = pack_bf16(v.x, v.y);
-  p0.y = pack_bf16(v.z, v.w);
-  v.x -= bf16_lo(p0.x); v.y -= bf16_hi(p0.x); v.z -= bf16_lo(p0.y); v.w -= bf16_hi(p0.y);
-  p1.x = pack_bf16(v.x, v.y);
-  p1.y = pack_bf16(v.z, v.w);
-  v.x -= bf16_lo(p1.x); v.y -= bf16_hi(p1.x); v.z -= bf16_lo(p1.y); v.w -= bf16_hi(p1.y);
-  p2.x = pack_bf16(v.x, v.y);
-  p2.y = pack_bf16(v.z, v.w);
-  dst[0] = p0;
-  dst[2 * kPlaneChunks] = p1;
-  dst[4 * kPlaneChunks] = p2;
 }
 
 // `srow`: this thread's 8-byte slot inside a plane, in uint2 units (see conv1x1_tile); rows 64 apart are 128 slots apart.
@@ -151,70 +103,6 @@ __device__ __forceinline__ void stage_store(const Staging<TM> s, uint4 *stage, i
   for (int h = 0; h < kRB; ++h) split_store(s.b[h], sb + 2 * kRPP * h);
 }
 
-// One K-tile out of LDS: 3 (WM + 2) conflict-free ds_read_b128 (the lane's 8 k of its row, per piece and 32-row block) feed
-// 6 * 2 WM bf16 MFMAs: the six products a_i b_j with i + j <= 2, the three smallest first, the four accumulator blocks of the
-// wave in turn inside every product (no MFMA waits for its predecessor's result).
-// Waves 2 x 2, wave tile (TM / 2) x 64 = WM x 2 blocks of 32 x 32 (WM = TM / 64).
-template <int TM>
-__device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 64][2]) {
-  constexpr int WM = TM / 64;
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
-  const int half = lane >> 5, r = lane & 31;
-  const uint4 *pa = stage + half * 128 + ((wi + r) ^ (half * 4));
-  const uint4 *pb = stage + kOperandChunks + half * 128 + ((wj + r) ^ (half * 4));
-  bf16x8 a[WM][3], b[2][3];
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-#pragma unroll
-    for (int i = 0; i < WM; ++i) a[i][p] = __builtin_bit_cast(bf16x8, pa[p * kPlaneChunks + 32 * i]);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(bf16x8, pb[p * kPlaneChunks + 32 * j]);
-  }
-  constexpr int kPA[6] = {0, 1, 2, 0, 1, 0}, kPB[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-  for (int t = 0; t < 6; ++t)
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][kPA[t]], b[j][kPB[t]], acc[i][j], 0, 0, 0);
-}
-
-// Epilogue of one 32 x 32 accumulator block: rows row0 + frag_row(q), column col.  FULL: every row of the tile exists (all
-// but the last row tile) -- no per-element branches, and the sixteen residual loads are issued together before the first
-// use (round 2 interleaved load -> wait -> store per element behind a branch: 64 serialised HBM round trips per lane).
-// NT: the residual is read and the output written with the non-temporal hint (round 6).  For WIDE outputs (the super-tile order,
-// K = 512 / N = 2048) the 554 MB residual + output stream of a launch shares each XCD's 4 MB L2 with the operands it is trying to
-// keep (2 MB of activations per panel group, 1 MB of weights per chunk) and evicts them: counters showed the activations fetched
-// ~4 x (617 MB read for 350 MB algorithmic, profiles/r05j_pmc.json case 135).  Neither stream is read again by this kernel.
-template <int ACT, bool HAS_RES, bool FULL, bool NT>
-__device__ __forceinline__ void store_block(const f32x16 &acc, const float *__restrict__ R, float *__restrict__ Y, int64_t row0,
-                                            int col, int64_t M, int N, float mu, float is, float ga, float be, float slope) {
-  const int lane = threadIdx.x & (kWave - 1);
-  float rv[16];
-  int64_t off[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-    off[q] = row * N + col;
-    rv[q] = 0.f;
-    if (HAS_RES && (FULL || row < M)) rv[q] = NT ? __builtin_nontemporal_load(R + off[q]) : R[off[q]];
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int64_t row = row0 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-    float z = ((acc[q] - mu) * is) * ga + be;                 // bn.cu:158-159
-    if (HAS_RES) z += rv[q];
-    if (ACT == SKD_ACT_RELU) z = z < 0.f ? 0.f : z;
-    if (ACT == SKD_ACT_LEAKY_RELU) z = z < 0.f ? z * slope : z;
-    if (FULL || row < M) {
-      if (NT) __builtin_nontemporal_store(z, Y + off[q]);
-      else Y[off[q]] = z;
-    }
-  }
-}
-
 // One output tile of TM x 128: K loop through the double-buffered LDS ring, then the epilogue.
 template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT>
 __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R,
@@ -232,8 +120,7 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
   const int nk = K / kBK;
   const int gt = threadIdx.x, grow = gt / kQK, gkq = (gt % kQK) * 4;
-  const int kh = gkq >> 3;                          // which 8-k half of the K-tile this thread's quad belongs to
-  const int srow = 2 * (kh * 128 + (grow ^ (kh * 4))) + ((gkq >> 2) & 1);   // 8-byte slot of (row grow, k quad) inside a plane
+  const int srow = plane_slot(grow, gkq);           // 8-byte slot of (row grow, k quad) inside a plane
   int64_t arow[kRA];   // rows beyond the matrix are clamped (loaded, multiplied, never stored)
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
@@ -337,22 +224,6 @@ __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, c
   pack[K + k] = inv_std_of(var[k], eps);
   pack[2 * (int64_t)K + k] = weight != nullptr ? fabsf(weight[k]) + eps : 1.f;   // bn.cu:153
   pack[3 * (int64_t)K + k] = bias != nullptr ? bias[k] : 0.f;
-}
-
-// Compute units of the device that `st` belongs to (0: unknown).  Queried once per device; the table is atomic because the
-// teacher stream and the main stream may reach their first launch from different host threads (a second query stores the same value).
-static int cu_count(hipStream_t st) {
-  static std::atomic<int> cus[64];
-  int dev = -1;
-  if (hipStreamGetDevice(st, &dev) != hipSuccess) {
-    (void)hipGetLastError();             // not an error of the launch that follows
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-  }
-  if (dev < 0 || dev >= 64) return 0;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (n == 0 && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-    cus[dev].store(n, std::memory_order_relaxed);
-  return n > 0 ? n : 0;
 }
 
 template <int ACT, bool HAS_RES, bool PRO, bool NT = false>

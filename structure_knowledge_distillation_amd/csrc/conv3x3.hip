@@ -1,0 +1,309 @@
+// conv3x3.hip -- 3x3, stride-1, "same" (padding = dilation) convolution of a frozen network as an IMPLICIT GEMM on the
+// split-operand bf16-MFMA core of conv_split_dev.hpp (see conv1x1.hip for the core): fp32 in, fp32 out.
+//
+//     Y[m][n] = epi( sum_{tap, c} X[pixel(m) + shift(tap)][c] * W[n][c][tap] ),   M = B*H*W output pixels (channels-last),
+//     N = Cout, K = 9 * Cin with k = tap * Cin + c, tap = 3 ty + tx, shift = ((ty - 1) * W + (tx - 1)) * dilation pixels.
+// A tap that falls outside the image contributes an exact zero: the load is not issued, the staging register is set to 0.
+// M is the flattened pixel index, so a tile's rows cross image rows and images freely; every thread works out (h, w) of the
+// one or two panel rows it owns once per tile and keeps a 9-bit validity mask per row.
+//
+// Why: the teacher's 3x3 convolutions were MIOpen implicit-GEMM kernels on v_mfma_f32_32x32x2_f32 at 0.79-0.87 of that pipe's
+// peak (profiles/r06w_conv_shapes.md); the pipe is the limit, and six bf16 MFMAs per 16 k take 2.67 x less matrix-pipe time than
+// eight fp32 ones (conv1x1.hip).
+//
+// Weights are split ONCE (the network is frozen): conv3x3_pack_kernel writes, per column tile of 128 output channels and
+// per K-tile of 16 k, the three bf16 planes in exactly the LDS image of the core (kPlaneChunks layout) -- 768 chunks of 16
+// bytes.  The main loop's B stage is then three 16-byte global loads and three ds_write_b128 per thread: no VALU work.  The split
+// is a pure function of the fp32 value, so the result equals splitting in the loop bit for bit.  Activations are split on
+// their way into LDS as in the 1x1 kernel (each element nine times, once per tap).
+//
+// Epilogue (store_block): out = act( ((acc + conv_bias - mean) * invstd) * (|weight| + eps) + bias ), every term optional:
+// the identity (raw convolution output: the PSP bottleneck's `feats` half, the bottleneck blocks' conv2), conv bias + eval-mode
+// InPlace-ABN + leaky ReLU (the deep-supervision head), eval-mode BN + ReLU.
+//
+// Grid: XCD-aware panel-major order as in conv1x1.hip -- row panel p lives on XCD p % 8, its column tiles run back to back --
+// so the workgroups resident on an XCD together started together and walk the same K-tiles of the same (at most Cout / 128)
+// weight panels at about the same time: a weight slice is fetched into that L2 once per wave of workgroups, not once per tile.
+// Two accumulator sets (tile_mma).  Two kernels, chosen per launch by launch3g: the TALL one runs 128 x 128 output tiles for the
+// launch's whole rounds and 64 x 128 tiles for the last, partial round, all at two workgroups per CU (one kernel, one register
+// budget); the other runs 64 x 128 tiles throughout at three workgroups per CU and takes the problems that do not fill the
+// chip's two-per-CU slots once.  48 KB of LDS either way.
+#include "conv_split_dev.hpp"
+
+namespace skd {
+namespace {
+
+constexpr int kTileChunks = kOperandChunks;           // one (column tile, K-tile) of packed weights: 768 chunks = 12,288 bytes
+constexpr int kBChunksPerThread = kTileChunks / kThreads;   // 3: thread t copies chunk t of each plane
+
+template <int TM>
+struct Staging3 {
+  float4 a[TM / kRPP];
+  uint4 b[kBChunksPerThread];
+};
+
+struct TapCursor {      // the K-tile being staged: tap 0..8, first channel c0, and the tap's address shift in floats
+  int tap, c0;
+  int64_t shift;
+};
+
+__device__ __forceinline__ int64_t tap_shift(int tap, int W, int dil, int Cin) {
+  const int ty = tap / 3, tx = tap - 3 * ty;
+  return ((int64_t)(ty - 1) * W + (tx - 1)) * dil * Cin;
+}
+
+template <int TM>
+__device__ __forceinline__ void stage_load3(Staging3<TM> &s, const float *__restrict__ X, const uint4 *__restrict__ bsrc,
+                                            const TapCursor &cur, const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP]) {
+#pragma unroll
+  for (int h = 0; h < TM / kRPP; ++h) {
+    s.a[h] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if ((mask[h] >> cur.tap) & 1u) s.a[h] = *reinterpret_cast<const float4 *>(X + abase[h] + cur.shift + cur.c0);
+  }
+#pragma unroll
+  for (int p = 0; p < kBChunksPerThread; ++p) s.b[p] = bsrc[p * kPlaneChunks];
+}
+
+template <int TM>
+__device__ __forceinline__ void stage_store3(const Staging3<TM> s, uint4 *stage, int srow) {
+  uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
+#pragma unroll
+  for (int h = 0; h < TM / kRPP; ++h) split_store(s.a[h], sa + 2 * kRPP * h);
+  uint4 *sb = stage + kOperandChunks + threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < kBChunksPerThread; ++p) sb[p * kPlaneChunks] = s.b[p];
+}
+
+// One output tile of TM x 128 pixels x channels.
+template <int TM, int ACT>
+__device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
+                                             const float *__restrict__ cbias, const float *__restrict__ mean,
+                                             const float *__restrict__ var, const float *__restrict__ weight,
+                                             const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W,
+                                             int Cin, int N, int dil, int64_t m0, int tn, uint4 *lds) {
+  constexpr int WM = TM / 64, kRA = TM / kRPP;
+  f32x16 acc[WM][2], low[WM][2];      // a0 b0 | the five smaller products (tile_mma): added in the epilogue
+#pragma unroll
+  for (int i = 0; i < WM; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[i][j][q] = low[i][j][q] = 0.f;
+  const int nk = 9 * (Cin / kBK);
+  const int gt = threadIdx.x, grow = gt / kQK, gkq = (gt % kQK) * 4;
+  const int srow = plane_slot(grow, gkq);
+  // this thread's panel rows: address of (pixel, channel quad) and the taps that stay inside the image; a row beyond M has none
+  int64_t abase[kRA];
+  unsigned mask[kRA];
+  const int64_t hw = (int64_t)H * W;
+#pragma unroll
+  for (int h = 0; h < kRA; ++h) {
+    const int64_t m = m0 + grow + kRPP * h;
+    const bool live = m < M;
+    const int64_t mm = live ? m : 0;
+    const int pix = (int)(mm % hw);
+    const int py = pix / W, px = pix - py * W;
+    unsigned bits = 0;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int64_t y = py + (int64_t)(tap / 3 - 1) * dil, x = px + (int64_t)(tap % 3 - 1) * dil;
+      if (live && y >= 0 && y < H && x >= 0 && x < W) bits |= 1u << tap;
+    }
+    mask[h] = bits;
+    abase[h] = mm * Cin + gkq;
+  }
+  const uint4 *bsrc = Bp + (int64_t)tn * nk * kTileChunks + gt;
+  TapCursor cur = {0, 0, tap_shift(0, W, dil, Cin)};
+  Staging3<TM> st;
+  stage_load3<TM>(st, X, bsrc, cur, abase, mask);
+  stage_store3<TM>(st, lds, srow);
+  __syncthreads();
+  int stage = 0;
+  for (int kt = 0; kt < nk; ++kt) {
+    const bool more = kt + 1 < nk;
+    if (more) {
+      cur.c0 += kBK;
+      if (cur.c0 == Cin) {
+        cur.c0 = 0;
+        ++cur.tap;
+        cur.shift = tap_shift(cur.tap, W, dil, Cin);
+      }
+      stage_load3<TM>(st, X, bsrc + (int64_t)(kt + 1) * kTileChunks, cur, abase, mask);
+    }
+    tile_mma<TM>(lds + stage * kStageChunks, low, acc);
+    if (more) stage_store3<TM>(st, lds + (stage ^ 1) * kStageChunks, srow);
+    __syncthreads();
+    stage ^= 1;
+  }
+  // ---- epilogue: (+ conv bias) -> eval-mode InPlace-ABN formula (when there are statistics) -> activation ----
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
+  const bool full = m0 + TM <= M;
+#pragma unroll
+  for (int bj = 0; bj < 2; ++bj) {
+    const int col = tn * kTN + wj + bj * 32 + (lane & 31);
+    const bool bn = mean != nullptr;
+    const float mu = bn ? mean[col] : 0.f, is = bn ? inv_std_of(var[col], eps) : 1.f;
+    const float ga = bn && weight != nullptr ? fabsf(weight[col]) + eps : 1.f;     // bn.cu:153
+    const float be = bn && bias != nullptr ? bias[col] : 0.f;
+    const float cb = cbias != nullptr ? cbias[col] : 0.f;
+#pragma unroll
+    for (int bi = 0; bi < WM; ++bi) {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[bi][bj][q] += low[bi][bj][q];
+      if (cbias != nullptr) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[bi][bj][q] += cb;
+      }
+      const int64_t row0 = m0 + wi + bi * 32;
+      if (full)
+        store_block<ACT, false, true, false>(acc[bi][bj], nullptr, Y, row0, col, M, N, mu, is, ga, be, slope);
+      else
+        store_block<ACT, false, false, false>(acc[bi][bj], nullptr, Y, row0, col, M, N, mu, is, ga, be, slope);
+    }
+  }
+}
+
+// TALL: row panels p < p_full are 128 pixels high, the panels behind them 64 (conv1x1.hip, round 6: the half-height mechanism);
+// the two accumulator sets of a 128 x 128 tile take 128 VGPRs and the kernel 206, so that form runs two workgroups per CU -- its
+// 64-row panels too: they are the same kernel.  !TALL: every panel is 64 pixels high (p_full = 0), 64 accumulator registers,
+// 124-128 VGPRs; three workgroups per CU, which is what 48 KB of LDS per workgroup admits (the registers would admit four).
+// The waves-per-SIMD range states those residencies (2, 3) so that the register budget follows from them and not from the
+// launch bound alone; with this compiler the !TALL form needs no more than 128 registers either way
+// (profiles/r12_kernel_resources.md).
+template <int ACT, bool TALL>
+__global__ __launch_bounds__(kThreads, TALL ? 2 : kMinWG) __attribute__((amdgpu_waves_per_eu(TALL ? 2 : kMinWG, TALL ? 2 : kMinWG)))
+void conv3x3_split_kernel(
+    const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y, const float *__restrict__ cbias,
+    const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
+    const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil, int tiles_n,
+    int p_full) {
+  extern __shared__ __attribute__((aligned(16))) uint4 lds[];
+  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+  const int pl = j / tiles_n, tn = j - pl * tiles_n;
+  const int64_t tm = (int64_t)pl * 8 + xcd;
+  if (TALL && tm < p_full) {
+    const int64_t m0 = tm * kTM;
+    if (m0 >= M) return;
+    conv3x3_tile<kTM, ACT>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+  } else {
+    const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
+    if (m0 >= M) return;
+    conv3x3_tile<kTM / 2, ACT>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+  }
+}
+
+// One thread per 16-byte chunk of the image: the 8 consecutive k (one tap, 8 channels) of one output channel, three pieces.
+// The weight is read through its strides (elements), so contiguous and channels-last tensors give the same pack.
+__global__ void conv3x3_pack_kernel(const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int nk,
+                                    int64_t chunks, uint4 *__restrict__ pack) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= chunks) return;
+  const int chunk = (int)(idx % kPlaneChunks);
+  const int64_t tile = idx / kPlaneChunks;                // = tn * nk + kt
+  const int kt = (int)(tile % nk), tn = (int)(tile / nk);
+  const int kh = chunk >> 7, row = (chunk & 127) ^ (kh * 4);
+  const int k0 = kt * kBK + kh * 8, tap = k0 / Cin, c0 = k0 - tap * Cin;
+  const int ty = tap / 3, tx = tap - 3 * ty;
+  const float *src = Wt + (int64_t)(tn * kTN + row) * sn + ty * sy + tx * sx;
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = src[(c0 + i) * sc];
+  uint2 lo[3], hi[3];
+  split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
+  split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
+#pragma unroll
+  for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * kPlaneChunks + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
+}
+
+template <int ACT, bool TALL>
+static int launch3(const float *X, const uint4 *Bp, float *Y, const float *cbias, const float *mean, const float *var,
+                   const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
+                   int geometry, hipStream_t st) {
+  static PerDeviceFlag ready;          // per instantiation AND per device
+  bool *rdy = ready.get();
+  if (rdy == nullptr) return 0;
+  if (!*rdy) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<ACT, TALL>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvLds) != hipSuccess) return 0;
+    *rdy = true;
+  }
+  const int tiles_n = N / kTN;
+  const int64_t tiles_m = cdiv(M, kTM);
+  // TALL: 128-row panels p < p_full, 64-row panels behind them.  geometry 1: all 128; geometry 3: 128 for the launch's whole
+  // rounds (two workgroups per CU) and 64 for the rest
+  int64_t p_full = TALL ? tiles_m : 0;
+  if (TALL && geometry == 3) {
+    const int64_t slots = 2 * (int64_t)cu_count(st), tiles = tiles_m * tiles_n;
+    if (slots > 0 && tiles % slots != 0) p_full = (tiles / slots) * slots / tiles_n / 8 * 8;
+  }
+  const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
+  const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
+  if (grid > 2147483647) return 0;
+  conv3x3_split_kernel<ACT, TALL><<<dim3((unsigned)grid), dim3(kThreads), kConvLds, st>>>(
+      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full);
+  return ok();
+}
+
+// geometry (see skd_eval.h): 1 and 3 = the TALL forms, 2 = 64-row tiles; 0 = the shipped choice: 3 once the 128-row tiles fill the
+// chip's two-per-CU slots at least once (every routed shape of the teacher at batch 8), 64-row tiles below that.
+// profiles/r12_conv3x3_isolated.md (tools/conv3x3_bench.py) has every geometry per shape: on the four routed shapes 3 is 6-14 %
+// ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
+// round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
+template <int ACT>
+static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *cbias, const float *mean, const float *var,
+                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
+                    int geometry, hipStream_t st) {
+  if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
+  if (geometry == 1 || geometry == 3)
+    return launch3<ACT, true>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+  return launch3<ACT, false>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+}
+
+}  // namespace
+}  // namespace skd
+
+using namespace skd;
+
+extern "C" {
+
+int skd_conv3x3_split_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return Cin > 0 && Cout > 0 && Cin % kBK == 0 && Cout % kTN == 0 && stride == 1 && dilation >= 1 && padding == dilation && groups == 1;
+}
+
+int64_t skd_conv3x3_split_pack_bytes(int Cin, int Cout) {
+  if (!skd_conv3x3_split_supported(Cin, Cout, 1, 1, 1, 1)) return 0;
+  return (int64_t)(Cout / kTN) * (9 * (Cin / kBK)) * kTileChunks * (int64_t)sizeof(uint4);
+}
+
+int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                   int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
+  const int64_t need = skd_conv3x3_split_pack_bytes(Cin, Cout);
+  if (need == 0 || !w || !pack || pack_bytes < need || (reinterpret_cast<uintptr_t>(pack) & 15)) return 0;
+  if (stride_n < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0) return 0;
+  const int nk = 9 * (Cin / kBK);
+  const int64_t chunks = (int64_t)(Cout / kTN) * nk * kPlaneChunks;
+  conv3x3_pack_kernel<<<dim3((unsigned)cdiv(chunks, 256)), dim3(256), 0, as_stream(stream)>>>(
+      w, stride_n, stride_c, stride_y, stride_x, Cin, nk, chunks, static_cast<uint4 *>(pack));
+  return ok();
+}
+
+int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                           const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                           float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+  if (!skd_conv3x3_split_supported(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
+  if (!x || !wpack || !out || (mean == nullptr) != (var == nullptr) || geometry < 0 || geometry > 3) return 0;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack)) & 15) return 0;
+  if ((int64_t)H * W > 2147483647 || dilation > (1 << 24)) return 0;
+  const int64_t M = (int64_t)B * H * W;
+  hipStream_t st = as_stream(stream);
+  const uint4 *bp = static_cast<const uint4 *>(wpack);
+  switch (activation) {
+    case SKD_ACT_NONE: return launch3g<SKD_ACT_NONE>(x, bp, out, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);
+    case SKD_ACT_RELU: return launch3g<SKD_ACT_RELU>(x, bp, out, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);
+    case SKD_ACT_LEAKY_RELU: return launch3g<SKD_ACT_LEAKY_RELU>(x, bp, out, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);
+    default: return 0;
+  }
+}
+
+}  // extern "C"

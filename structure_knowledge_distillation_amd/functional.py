@@ -18,6 +18,7 @@ derivatives of the discriminator's stock convolutions; the spectral-norm node is
 by the final ``d_loss.backward()``.
 """
 import ctypes
+import types
 
 import torch
 from torch.autograd import Function
@@ -319,12 +320,13 @@ def ppm_fold_supported(feats, sizes):
         and _is_cl(feats) and 3 * sum(sizes) <= 64 and len(sizes) <= 4
 
 
-def ppm_fold_bottleneck(priors, feats, weight, cache=None):
+def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False):
     """conv3x3(cat([upsample(p) for p in priors] + [feats], 1), weight, padding=1) (pspnet_combine.py:104-111) without
     the concatenated tensor and without convolving the priors' channels: the feature-map slice of the weight goes through
     the convolution, the priors through a (B s^2) x Cm x 9 Cout GEMM each and the fold kernel (csrc/ppm.hip).
     priors: (B, Cm, s, s) channels-last; feats: (B, Cf, H, W) channels-last; weight: (Cout, L*Cm + Cf, 3, 3).
-    `cache` (a dict) keeps the rearranged weight slices of a frozen network between calls."""
+    `cache` (a dict) keeps the rearranged weight slices of a frozen network between calls.  `split3x3`: run the feature-map
+    convolution on csrc/conv3x3.hip when conv3x3_split_supported-style conditions hold (no grad; weights packed once in `cache`)."""
     import torch.nn.functional as F
     cm = priors[0].shape[1]
     n_prior = len(priors) * cm
@@ -340,7 +342,11 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None):
         if cache is not None and not (torch.is_grad_enabled() and weight.requires_grad):
             cache["key"], cache["mats"] = key, mats
     wf, w_all = mats
-    base = F.conv2d(feats, wf, None, 1, 1)
+    if split3x3 and cache is not None and _conv3x3_split_ok(feats, weight[:, n_prior:], 1, 1, 1, 1):
+        owner = cache.setdefault("pack3x3", types.SimpleNamespace())
+        base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], owner), cout)
+    else:
+        base = F.conv2d(feats, wf, None, 1, 1)
     # ONE GEMM of all levels' priors against all levels' weight blocks (only the diagonal blocks are used: 4x the
     # necessary flops of a 2 GFLOP product, but a single well-shaped library call instead of four skinny ones)
     p_all = torch.cat([_cl(p).permute(0, 2, 3, 1).reshape(-1, cm) for p in priors], 0)
@@ -479,7 +485,8 @@ def conv1x1_bn_blas(x, conv, bn, relu):
     (1024 -> 256 at 65 x 65, batch 8: 144 us with the epilogue vs 175 us convolution + 27 us ABN pass;
     profiles/r02d_conv1x1_blas.jsonl), exact fp32 (no xf32 on gfx950).  The folded operands are cached on the BN module.
     In isolation the split-operand kernel behind conv1x1_abn_eval is now faster on most of these shapes (1024 -> 256 at
-    65 x 65: 130 us against 146-155, profiles/r11_stage2_isolated.md); routing them there waits for an A/B on the step."""
+    65 x 65: 130 us against 146-155, profiles/r11_stage2_isolated.md); which of the two a frozen network's layer takes is
+    networks.pspnet_combine.SPLIT_REDUCE, set by the step A/B of profiles/r12_step_ab.md (the kernel, except 512 -> 128)."""
     key = tuple((t.data_ptr(), t._version) for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None)
     fold = getattr(bn, "_blas_fold", None)
     if fold is None or fold[0] != key:
@@ -565,6 +572,88 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
     _lib.check(_lib.get().skd_conv1x1_abn_nhwc(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
                                                running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
                                                float(eps), act, float(slope), _lib.stream_of(x)), "skd_conv1x1_abn_nhwc")
+    return out
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _conv3x3_split_ok(x, weight, stride, padding, dilation, groups):
+    if torch.is_grad_enabled() or not _lib.has_entry("skd_conv3x3_split_nhwc"):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0):
+        return False
+    if not (weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and weight.dtype == torch.float32
+            and weight.device == x.device and x.shape[1] == weight.shape[1] * groups):
+        return False
+    return bool(_lib.get().skd_conv3x3_split_supported(int(weight.shape[1]), int(weight.shape[0]), stride, padding, dilation, groups))
+
+
+def conv3x3_split_supported(x, conv):
+    """True when the implicit-GEMM 3x3 convolution of csrc/conv3x3.hip takes ``conv(x)``: a back-end that has the entry (the
+    tests' C double does not: callers then run ``F.conv2d`` as before), no grad, an fp32 channels-last input, a plain 3x3 /
+    stride-1 / padding == dilation / ungrouped convolution with Cin a multiple of 16 and Cout of 128."""
+    if not (isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
+        return False
+    s, p, d = _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation)
+    if s[0] != s[1] or p[0] != p[1] or d[0] != d[1]:
+        return False
+    return _conv3x3_split_ok(x, conv.weight, s[0], p[0], d[0], conv.groups)
+
+
+def conv3x3_pack_weights(conv, weight=None, owner=None):
+    """The three bf16 planes of a frozen 3x3 convolution's weight in the layout csrc/conv3x3.hip streams into LDS (6 bytes per
+    weight), cached on ``owner`` (default: the conv module) under ``(data_ptr, _version)`` like abn_pack_eval_params and rebuilt
+    when the weight is written or moved.  ``weight`` (default ``conv.weight``) may be any strided (Cout, Cin, 3, 3) view -- the
+    PSP bottleneck packs the feature-map slice of its weight -- and either memory format gives the same pack.  The first call
+    allocates: a frozen network makes it in its eager warm-up steps, before any graph capture."""
+    w = conv.weight if weight is None else weight
+    owner = conv if owner is None else owner
+    if torch.is_grad_enabled() and w.requires_grad:
+        raise RuntimeError("conv3x3_pack_weights is for frozen (no-grad) convolutions")
+    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()))
+    cached = getattr(owner, "_skd_conv3x3_pack", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    _lib.require_device(w)
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    lib = _lib.get()
+    nbytes = int(lib.skd_conv3x3_split_pack_bytes(cin, cout))
+    if nbytes <= 0 or tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32:
+        raise ValueError("conv3x3_pack_weights: unsupported weight %s" % (tuple(w.shape),))
+    pack = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+    sn, sc, sy, sx = (int(v) for v in w.stride())
+    _lib.check(lib.skd_conv3x3_split_pack_weights(cin, cout, w.data_ptr(), sn, sc, sy, sx, pack.data_ptr(), nbytes,
+                                                  _lib.stream_of(pack)), "skd_conv3x3_split_pack_weights")
+    # the weight's storage is held with the pack: while it is alive no other tensor can take its address, so a weight moved
+    # to new storage (``.to()``) can never be mistaken for the packed one
+    owner._skd_conv3x3_pack = (key, pack, w.untyped_storage())
+    return pack
+
+
+def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0):
+    """act(bn_running(conv3x3(x) + conv_bias)) with ``pack = conv3x3_pack_weights(...)`` (inference only; conv3x3_split_supported
+    says when).  fp32 in and out, channels-last; the products run on the bf16 MFMA through the three-piece split (csrc/conv3x3.hip):
+    within 4 x of the fp32 convolution's error against a float64 result and never above 2e-5 of the output's largest magnitude
+    (tests/test_conv3x3_split_gpu.py), exact on integer data.  ``bn``: an eval-mode InPlace-ABN module (or None) whose running
+    statistics and affine parameters go into the epilogue; ``activation``: 'none' / 'relu' / 'leaky_relu' (slope: ``bn.slope``)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("conv3x3_split_eval is inference-only")
+    _lib.require_device(x, pack, conv_bias)
+    act = {"none": 0, "leaky_relu": 1, "relu": 3}[activation]
+    b, cin, h, w = x.shape
+    if pack.numel() != _lib.get().skd_conv3x3_split_pack_bytes(cin, cout):
+        raise ValueError("conv3x3_split_eval: the pack is not that of a (%d, %d, 3, 3) weight" % (cout, cin))
+    out = _new_cl(x, b, cout, h, w)
+    mean = var = gamma = beta = None
+    eps, slope = 0.0, 0.01
+    if bn is not None:
+        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
+    _lib.check(_lib.get().skd_conv3x3_split_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                                 _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                                 eps, act, slope, int(geometry), _lib.stream_of(x)), "skd_conv3x3_split_nhwc")
     return out
 
 

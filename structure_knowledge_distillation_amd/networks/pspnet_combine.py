@@ -3,8 +3,9 @@
 Same public surface, module names and state-dict keys as the reference's
 networks/pspnet_combine.py:114-197 (150 tensors student / 565 teacher), so its checkpoints load
 and ``forward`` returns the same 7-element list ``[logits, dsn, feat_after_psp, x4, x3, x2, x1]``
-(pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm; every normalisation is
-the hand-written InPlace-ABN of csrc/abn*.hip (``libs``), applied in place on the conv output.
+(pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm -- except the frozen teacher's 1x1 GEMMs (csrc/conv1x1.hip) and its wide
+stride-1 3x3 convolutions (csrc/conv3x3.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation
+is the hand-written InPlace-ABN of csrc/abn*.hip (``libs``), applied in place on the conv output.
 """
 import functools
 
@@ -42,6 +43,14 @@ HEAD_KERNEL = True    # the 19-class 1x1 heads as the skinny HBM-bound kernels o
                       # gradient back) instead of 41 + 123 us convolutions per student head (round 6)
 STEM_FUSED = True     # training stem: bn3 -> relu3 -> maxpool without the normalised tensor (libs.modules.forward_relu_maxpool, round 6)
 PSP_FOLD = True       # conv3x3(cat(up(priors), feats)) = conv3x3(feats) + fold(priors x W) (csrc/ppm.hip); profiles/r02d: 77.4 -> 72.2 ms
+CONV3X3_SPLIT = True  # the frozen network's stride-1 3x3 convolutions with >= CONV3X3_SPLIT_MIN_CIN input channels (layer3 / layer4 conv2,
+                      # the PSP bottleneck's feature half, the deep-supervision head) as implicit GEMMs on the bf16 MFMA with the
+                      # three-piece operand split (csrc/conv3x3.hip) instead of MIOpen's fp32-MFMA kernels; profiles/r12_conv3x3_isolated.md
+                      # (1.16-1.30 x per launch), profiles/r12_step_ab.md (59.38-59.71 -> 55.40-55.67 ms per step)
+CONV3X3_SPLIT_MIN_CIN = 256   # the 64- / 128-channel 3x3s (stem, layer1, layer2: narrow N, ~1.6 ms together) stay on MIOpen
+SPLIT_REDUCE = True   # the reduce / stride-1 down-sample 1x1 GEMMs on csrc/conv1x1.hip's split core instead of the library GEMM wherever
+                      # profiles/r11_stage2_isolated.md shows the kernel ahead (every shape but 512 -> 128); profiles/r12_step_ab.md:
+                      # 55.40-55.67 ms per step off, 54.61-55.07 on, five interleaved runs each, the sets do not overlap
 
 
 def _fused_tail(x):
@@ -50,6 +59,21 @@ def _fused_tail(x):
 
 def _blas_tail(module, x):
     return BLAS_TAILS and not module.training and not torch.is_grad_enabled()
+
+
+def _conv1x1_bn_eval(x, conv, bn, relu):
+    """relu?(bn(conv1x1(x))) of the frozen network for a call blas_1x1_bn_supported accepted: the split-core GEMM of csrc/conv1x1.hip
+    where SPLIT_REDUCE routes it there, the library GEMM with the folded BN otherwise."""
+    if (SPLIT_REDUCE and not (conv.in_channels == 512 and conv.out_channels == 128)      # the library wins 512 -> 128 (r11)
+            and getattr(bn, "activation", None) == "none" and SF.conv1x1_abn_supported(x, conv)):
+        return SF.conv1x1_abn_eval(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps,
+                                   "relu" if relu else "none")
+    return SF.conv1x1_bn_blas(x, conv, bn, relu=relu)
+
+
+def _conv3x3_split(x, conv):
+    return (CONV3X3_SPLIT and conv.in_channels >= CONV3X3_SPLIT_MIN_CIN and not conv.training
+            and SF.conv3x3_split_supported(x, conv))
 
 
 class _ClassifierConvFn(torch.autograd.Function):
@@ -144,10 +168,13 @@ class Bottleneck(nn.Module):
         if _fused(self, x):
             blas = _blas_tail(self, x)
             if blas and SF.blas_1x1_bn_supported(x, self.conv1):
-                out = SF.conv1x1_bn_blas(x, self.conv1, self.bn1, relu=True)
+                out = _conv1x1_bn_eval(x, self.conv1, self.bn1, relu=True)
             else:
                 out = self.bn1.forward_relu(self.conv1(x))
-            c2 = self.conv2(out)
+            if _conv3x3_split(out, self.conv2):    # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
+                c2 = SF.conv3x3_split_eval(out, SF.conv3x3_pack_weights(self.conv2), self.conv2.out_channels, self.conv2.dilation[0])
+            else:
+                c2 = self.conv2(out)
             tail = (not self.training and _fused_tail(x) and SF.conv1x1_abn_supported(c2, self.conv3) and self.conv3.in_channels <= 512
                     and getattr(self.bn2, "activation", None) == "none" and getattr(self.bn3, "activation", None) == "none")
             if not tail:
@@ -156,7 +183,7 @@ class Bottleneck(nn.Module):
                 residual = x
             elif (blas and len(self.downsample) == 2 and SF.blas_1x1_bn_supported(x, self.downsample[0])
                   and getattr(self.downsample[1], "activation", None) == "none"):
-                residual = SF.conv1x1_bn_blas(x, self.downsample[0], self.downsample[1], relu=False)
+                residual = _conv1x1_bn_eval(x, self.downsample[0], self.downsample[1], relu=False)
             else:
                 residual = self.downsample(x)
             if tail:
@@ -226,7 +253,8 @@ class PSPModule(nn.Module):
                 # the priors never meet the convolution: conv3x3(cat) = conv3x3(feats) + fold(priors x W) by linearity
                 if not hasattr(self, "_fold_cache"):
                     self._fold_cache = {}
-                out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache)
+                out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache,
+                                             split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN)
                 return self.bottleneck[2](self.bottleneck[1](out))
             return self.bottleneck(SF.ppm_concat(priors, feats))
         h, w = feats.size(2), feats.size(3)
@@ -282,6 +310,17 @@ class ResNet(nn.Module):
             mods.append(block(self.inplanes, planes, dilation=dilation, multi_grid=grid(i)))
         return nn.Sequential(*mods)
 
+    def _dsn_head(self, x3):
+        """``self.dsn(x3)``; for the frozen network its 3x3 convolution, bias, eval-mode ABN and activation are one launch of
+        csrc/conv3x3.hip (the Dropout2d between them and the classifier is the identity in eval mode)."""
+        conv, bn = self.dsn[0], self.dsn[1]
+        if (not self.training and not torch.is_grad_enabled() and getattr(bn, "activation", None) in ("none", "relu", "leaky_relu")
+                and hasattr(bn, "running_mean") and _conv3x3_split(x3, conv)):
+            y = SF.conv3x3_split_eval(x3, SF.conv3x3_pack_weights(conv), conv.out_channels, conv.dilation[0], conv.bias, bn,
+                                      bn.activation)
+            return self.dsn[3](y)
+        return self.dsn(x3)
+
     def forward(self, x):
         if _fused(self, x) and not self.training and getattr(self.bn3, "activation", None) == "none":
             # Frozen network: eval-mode BN + ReLU is a non-decreasing map per channel (its scale (|gamma| + eps) / sqrt(var + eps) is
@@ -322,10 +361,10 @@ class ResNet(nn.Module):
             x_feat_after_psp = self.pspmodule(x4)
             x = self.head(x_feat_after_psp)
             self.dsn_last(x, x_feat_after_psp)
-            x_dsn = self.dsn(x3)
+            x_dsn = self._dsn_head(x3)
             return [x, x_dsn, x_feat_after_psp, x4, x3, x2, x1]
         else:
-            x_dsn = self.dsn(x3)
+            x_dsn = self._dsn_head(x3)
         x4 = self.layer4(x3)
         x_feat_after_psp = self.pspmodule(x4)
         x = self.head(x_feat_after_psp)

@@ -1,0 +1,109 @@
+"""Host-side checks of the split-core 3x3 convolution's plumbing on a box without a GPU: the fall-through to ``F.conv2d`` under
+the C double, the weight-pack cache key, and header <-> table <-> library agreement on the new names."""
+import ctypes
+import re
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
+from oracle import cref
+from structure_knowledge_distillation_amd import _lib, build, functional as SF
+
+NAMES = ["skd_conv3x3_split_nhwc", "skd_conv3x3_split_pack_bytes", "skd_conv3x3_split_pack_weights", "skd_conv3x3_split_supported"]
+
+
+@pytest.fixture
+def c_double():
+    _lib.install_test_backend(cref.load(_lib.SIGNATURES))
+    yield
+    _lib.install_test_backend(None)
+
+
+def test_c_double_takes_the_conv2d_path(c_double, monkeypatch):
+    """The plain-C double has no 3x3 entry: conv3x3_split_supported is False and the teacher's three call sites run F.conv2d."""
+    assert PC.CONV3X3_SPLIT and not _lib.has_entry("skd_conv3x3_split_nhwc")
+    torch.manual_seed(3)
+    net = PC.Res_pspnet(PC.Bottleneck, [3, 4, 23, 3], 19).eval().to(memory_format=torch.channels_last)
+    seen = []
+    real = F.conv2d
+
+    def spy(x, w, *a, **k):
+        if tuple(w.shape[2:]) == (3, 3) and w.shape[1] >= PC.CONV3X3_SPLIT_MIN_CIN:
+            seen.append((w.shape[1], w.shape[0]))
+        return real(x, w, *a, **k)
+    monkeypatch.setattr(F, "conv2d", spy)
+    monkeypatch.setattr(SF, "conv3x3_split_eval", lambda *a, **k: pytest.fail("the split kernel was called without its entry"))
+    with torch.no_grad():
+        x = torch.randn(1, 256, 9, 9).contiguous(memory_format=torch.channels_last)
+        assert not SF.conv3x3_split_supported(x, net.layer3[1].conv2)
+        out = net(torch.randn(1, 3, 65, 49).contiguous(memory_format=torch.channels_last))
+    assert all(bool(torch.isfinite(o).all()) for o in out)
+    # layer3 conv2 x 23, layer4 conv2 x 3, the PSP bottleneck's feature half, the deep-supervision head
+    assert seen.count((256, 256)) == 23 and seen.count((512, 512)) == 3 and (2048, 512) in seen and (1024, 512) in seen
+
+
+class _PackDouble:
+    """Back-end double for the pack entries alone: records calls, writes nothing."""
+
+    def __init__(self):
+        self.calls = 0
+
+    def skd_conv3x3_split_pack_bytes(self, cin, cout):
+        return cout * cin * 54
+
+    def skd_conv3x3_split_pack_weights(self, *args):
+        self.calls += 1
+        return 1
+
+
+def test_pack_cache_follows_the_weight():
+    b = _PackDouble()
+    _lib.install_test_backend(b)
+    try:
+        conv = torch.nn.Conv2d(16, 128, 3, 1, 2, 2, bias=False)
+        with torch.no_grad():
+            p1 = SF.conv3x3_pack_weights(conv)
+            key1 = conv._skd_conv3x3_pack[0]
+            assert SF.conv3x3_pack_weights(conv) is p1 and b.calls == 1
+            assert p1.numel() == 128 * 16 * 9 * 6 and p1.dtype == torch.uint8
+            conv.weight.mul_(0.5)                                   # in-place update: the version counter moves
+            p2 = SF.conv3x3_pack_weights(conv)
+            key2 = conv._skd_conv3x3_pack[0]
+            assert b.calls == 2 and key2 != key1 and p2 is not p1
+            conv.to(torch.float64).to(torch.float32)                # .to(): new storage
+            SF.conv3x3_pack_weights(conv)
+            assert b.calls == 3 and conv._skd_conv3x3_pack[0] != key2
+            conv.to(memory_format=torch.channels_last)              # same values, other strides: re-packed through the strides
+            SF.conv3x3_pack_weights(conv)
+            assert conv._skd_conv3x3_pack[0][3] == tuple(conv.weight.stride())
+        conv.weight.requires_grad_(True)
+        with pytest.raises(RuntimeError, match="frozen"):
+            SF.conv3x3_pack_weights(conv)
+    finally:
+        _lib.install_test_backend(None)
+
+
+def test_header_table_and_library_agree_on_the_new_names():
+    protos = _lib.header_prototypes(_lib.EXT_HEADER_PATH)
+    for name in NAMES:
+        assert name in protos and name in _lib.EXT_SIGNATURES and name not in _lib.SIGNATURES
+        assert name not in _lib.header_prototypes(_lib.HEADER_PATH)
+    with open(_lib.EXT_HEADER_PATH) as fh:
+        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
+    for m in re.finditer(r"\b(skd_conv3x3_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        assert m.group(2).count(",") + 1 == len(_lib.EXT_SIGNATURES[m.group(1)][1]), m.group(1)
+    raw = ctypes.CDLL(build.build())
+    for name in NAMES:
+        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
+    typed = _lib.load()
+    # host-side refusals need no device
+    assert typed.skd_conv3x3_split_supported(256, 256, 1, 2, 2, 1) == 1
+    assert typed.skd_conv3x3_split_supported(24, 256, 1, 1, 1, 1) == 0
+    assert typed.skd_conv3x3_split_supported(256, 64, 1, 1, 1, 1) == 0
+    assert typed.skd_conv3x3_split_supported(256, 256, 2, 1, 1, 1) == 0
+    assert typed.skd_conv3x3_split_supported(256, 256, 1, 1, 2, 1) == 0
+    assert typed.skd_conv3x3_split_supported(256, 256, 1, 1, 1, 2) == 0
+    assert typed.skd_conv3x3_split_pack_bytes(256, 256) == 256 * 256 * 54
+    assert typed.skd_conv3x3_split_nhwc(1, 4, 4, 32, 128, 1, None, None, None, None, None, None, None, None, 0.0, 0, 0.01, 0, None) == 0

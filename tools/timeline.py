@@ -165,6 +165,20 @@ def main():
     out.append("\n## D stream, kernel time per step by category\n\n| category | ms / step |\n|---|---|")
     for c, v in cat_d.most_common():
         out.append("| %s | %.2f |" % (c, v / n / 1e6))
+    # every other queue (the frozen teacher's stream is the one with the most kernel time among them): busy time per step, when its
+    # first kernel of the step started and its last one ended (ms after the step's start), and what the main stream ran next
+    out.append("\n## Other queues per step (the teacher's stream)\n\n| queue | step | kernels | busy ms | first start ms | last end ms | "
+               "main stream's first kernel after that end: start ms, name |\n|---|---|---|---|---|---|---|")
+    for q in sorted((q for q in byq if q not in (main_q, d_q)), key=lambda q: -busy[q]):
+        for k, (b0, b1) in enumerate(sel):
+            iv = [(s, e) for s, e, _, _ in byq[q] if s >= b0 and e <= b1 + 1]
+            if not iv:
+                continue
+            tq, _ = union(iv)
+            q_end = max(e for _, e in iv)
+            nxt = next(((s, n) for s, e, qq, n in rows if qq == main_q and s >= q_end and s <= b1), None)
+            out.append("| %s | %d | %d | %.2f | %.2f | %.2f | %s |" % (q, lo + k, len(iv), tq / 1e6, (min(s for s, _ in iv) - b0) / 1e6, (q_end - b0) / 1e6,
+                                                                     "%.2f, `%s`" % ((nxt[0] - b0) / 1e6, short(nxt[1])[:60]) if nxt else "-"))
     tot_gap = sum(g[0] for g in gaps_all)
     host_gap = sum(g[0] - g[1] for g in gaps_all)
     out.append("\n## Main-stream gaps > %.0f us\n\n%d gaps per step, %.2f ms per step in total, of which %.2f ms with the D stream idle as well (nothing running: the host "
