@@ -56,6 +56,21 @@ int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation,
                            const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
                            float eps, int activation, float slope, int geometry, skd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Launch geometry of skd_conv1x1_abn_nhwc / skd_conv1x1_abn_pro_nhwc (csrc/conv1x1.hip) for an (M, K, N) problem on a device of
+ * `cus` compute units: HOST arithmetic only, no device is touched, so a test can check on any machine that the workgroups of
+ * a launch cover the M x N output exactly once.  Both return 0 for a problem skd_conv1x1_abn_supported() refuses, cus < 0 or
+ * a grid beyond 2^31 - 1 workgroups.
+ *   geometry: out[7] = tiles_n (column tiles of 128), ct (column tiles per weight chunk), pm (row panels per panel group),
+ *     p_full (row panels of 128 rows; the panels behind them are 64 rows high), panels (all row panels), grid (workgroups),
+ *     nt (1: wide output -- super-tile order and non-temporal stores; 0: panel-major order).
+ *   tile_of: out[3 i ...] = m0, rows, n0 of workgroup block + i for 0 <= i < count (all inside [0, grid), else 0 is returned):
+ *     the workgroup writes rows [m0, min(m0 + rows, M)) x columns [n0, n0 + 128); rows = 128 or 64, or 0 for a padding
+ *     workgroup that exits.  The same inline function decodes blockIdx.x in the kernel.
+ * ---------------------------------------------------------------------------------- */
+int skd_conv1x1_abn_geometry(int64_t M, int K, int N, int cus, int64_t *out);
+int skd_conv1x1_abn_tile_of(int64_t M, int K, int N, int cus, int64_t block, int64_t count, int64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,8 @@ EXT_SIGNATURES = {
     "skd_conv3x3_split_pack_bytes": (_L, [_I, _I]),
     "skd_conv3x3_split_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
     "skd_conv3x3_split_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+    "skd_conv1x1_abn_geometry": (_I, [_L, _I, _I, _I, _P]),
+    "skd_conv1x1_abn_tile_of": (_I, [_L, _I, _I, _I, _L, _L, _P]),
 }
 
 _lib = None

@@ -19,7 +19,9 @@
 // v_mfma_f32_32x32x16_bf16 per 32 x 32 block and 16 k, all into ONE fp32 accumulator.  The dropped terms a1 b2, a2 b1, a2 b2
 // are below 2^-23 |a b|; measured against the double-precision oracle the result is within 4 x of the exact fp32 fma chain
 // the fp32 MFMA gave (tests/test_conv1x1_split_gpu.py, profiles/r11_conv1x1_split_accuracy.md) and exact on integer data whose
-// sums fit fp32.  Six bf16 MFMAs of 32 cycles replace eight fp32 MFMAs of 64 per 16 k of a block: 2.67 x less matrix-pipe time.
+// sums fit fp32.  At the reduce / down-sample shapes (K up to 2048, and 4096) it is within 1.5 x of the library fp32 GEMM's error and
+// below 2e-6 of the output's largest magnitude (1.55e-6 at K = 4096: profiles/r13_conv1x1_reduce_accuracy.md) -- one accumulator
+// is enough here, unlike conv3x3.hip.  Six bf16 MFMAs of 32 cycles replace eight fp32 MFMAs of 64 per 16 k of a block: 2.67 x less matrix-pipe time.
 // Outside the normal range: a finite |a| above the largest bf16 (about 3.39e38) rounds a0 to infinity and an infinite a has
 // an undefined residual, so in both cases the affected outputs are NaN where the fp32 chain would have given +-inf or a finite
 // value (a * 0); a NaN input gives NaN outputs as before.  Pieces below the fp32 normal range (|a| < 2^-102 or so) may be
@@ -167,6 +169,68 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
   }
 }
 
+// Launch geometry of an (M, K, N) problem on a device of `cus` compute units (0: unknown): everything launch() decides and the
+// kernel decodes, as plain host arithmetic (exported for the tests as skd_conv1x1_abn_geometry).  The comments in the kernel say
+// what the numbers mean.
+struct Geometry {
+  int tiles_n, ct, pm;          // column tiles; column tiles per chunk and row panels per group of the super-tile order
+  int64_t p_full, panels, grid; // row panels of 128 rows; all row panels (those behind p_full: 64 rows); workgroups
+  bool nt;                      // wide output (ct < tiles_n): super-tile order, non-temporal epilogue
+};
+inline bool conv1x1_geometry(int64_t M, int K, int N, int cus, Geometry &g) {
+  g.tiles_n = N / kTN;
+  const int64_t tiles_m = cdiv(M, kTM);
+  // super-tile geometry (see the kernel): column-tile chunks of <= 1 MB of weights, panel groups of <= 2 MB of activations
+  const int64_t tile_bytes = (int64_t)kTN * K * sizeof(float);
+  // (ten geometries were swept with the counters: profiles/r04g_pmc.json, profiles/r04h_two_ranks_one_gpu_bisect.txt; this is the
+  // one that minimised L2 -> fabric reads at K = 512 / N = 2048: 851 -> 617 MB per launch)
+  g.ct = (int)((1 << 20) / tile_bytes);
+  g.pm = (int)((2 << 20) / tile_bytes);
+  if (g.ct < 1) g.ct = 1;
+  if (g.pm < 1) g.pm = 1;
+  g.nt = g.ct < g.tiles_n;                                  // wide: NT epilogue
+  if (!g.nt) { g.ct = g.tiles_n; g.pm = 1; }                // narrow output: plain panel-major order
+  while (g.tiles_n % g.ct) --g.ct;                          // chunks of equal width (tiles_n is a power of two in this network)
+  // half-height panels for the last, partial round; slots = 3 workgroups per compute unit
+  g.p_full = g.panels = tiles_m;
+  const int64_t slots = (int64_t)kMinWG * cus;
+  const int64_t tiles = tiles_m * g.tiles_n;
+  if (slots > 0 && tiles > slots && tiles % slots != 0) {
+    g.p_full = (tiles / slots) * slots / g.tiles_n / 8 * 8;          // whole rounds, whole XCD rows of panels
+    const int64_t rest_rows = M - g.p_full * kTM;
+    g.panels = g.p_full + cdiv(rest_rows, kTM / 2);
+  }
+  const int64_t panels_per_xcd = cdiv(cdiv(g.panels, 8), g.pm) * g.pm;   // row panels padded to whole groups on each of the 8 XCDs
+  g.grid = panels_per_xcd * 8 * g.tiles_n;
+  return g.grid <= 2147483647;
+}
+
+// Workgroup `block` of that grid -> its output tile: rows [m0, m0 + rows) (rows = 128 or 64; 0: padding, the workgroup exits)
+// and columns [n0, n0 + 128).  The order is explained in the kernel, its only caller on the device.
+struct TileOf {
+  int64_t m0;
+  int rows, n0;
+};
+__host__ __device__ __forceinline__ TileOf conv1x1_tile_of(unsigned block, int64_t M, int tiles_n, int pm, int ct, int p_full) {
+  const int xcd = block & 7, j = block >> 3;
+  const int per_group = pm * tiles_n;
+  const int group = j / per_group, r = j - group * per_group;
+  const int per_chunk = pm * ct;
+  const int chunk = r / per_chunk, r2 = r - chunk * per_chunk;
+  const int pl = r2 / ct;
+  const int tn = chunk * ct + (r2 - pl * ct);
+  const int64_t tm = ((int64_t)group * pm + pl) * 8 + xcd;
+  if (tn >= tiles_n) return TileOf{0, 0, 0};
+  if (tm < p_full) {
+    const int64_t m0 = tm * kTM;
+    if (m0 >= M) return TileOf{0, 0, 0};
+    return TileOf{m0, kTM, tn * kTN};
+  }
+  const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
+  if (m0 >= M) return TileOf{0, 0, 0};
+  return TileOf{m0, kTM / 2, tn * kTN};
+}
+
 template <int ACT, bool HAS_RES, bool PRO, bool NT>
 __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
     const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R, float *__restrict__ Y,
@@ -194,25 +258,11 @@ __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
   // peak on a tile count that divides the chip and 0.63-0.69 on this one (profiles/r06t_gemm_lab_quantisation.jsonl).  The row
   // panels p < p_full are 128 rows high, the panels behind them (the rows a whole number of rounds does not cover) 64: twice the
   // workgroups of half the duration fill the last round's slots (p_full is a multiple of 8: whole XCD rows).
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-  const int per_group = pm * tiles_n;
-  const int group = j / per_group, r = j - group * per_group;
-  const int per_chunk = pm * ct;
-  const int chunk = r / per_chunk, r2 = r - chunk * per_chunk;
-  const int pl = r2 / ct;
-  const int tn = chunk * ct + (r2 - pl * ct);
-  const int64_t tm = ((int64_t)group * pm + pl) * 8 + xcd;
-  if (tn >= tiles_n) return;
-  const int n0 = tn * kTN;
-  if (tm < p_full) {
-    const int64_t m0 = tm * kTM;
-    if (m0 >= M) return;
-    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, m0, n0, lds);
-  } else {
-    const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
-    if (m0 >= M) return;
-    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, m0, n0, lds);
-  }
+  const TileOf t = conv1x1_tile_of(blockIdx.x, M, tiles_n, pm, ct, p_full);
+  if (t.rows == kTM)
+    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+  else if (t.rows == kTM / 2)
+    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
 }
 
 __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, const float *__restrict__ var,
@@ -239,34 +289,11 @@ static int launch(const float *X, const float *Wt, const float *R, float *Y, con
     *rdy = true;
   }
   const size_t lds_bytes = kConvLds + (PRO ? sizeof(float) * 4 * (size_t)K : 0);
-  const int tiles_n = N / kTN;
-  const int64_t tiles_m = cdiv(M, kTM);
-  // super-tile geometry (see the kernel): column-tile chunks of <= 1 MB of weights, panel groups of <= 2 MB of activations
-  const int64_t tile_bytes = (int64_t)kTN * K * sizeof(float);
-  // (ten geometries were swept with the counters: profiles/r04g_pmc.json, profiles/r04h_two_ranks_one_gpu_bisect.txt; this is the
-  // one that minimised L2 -> fabric reads at K = 512 / N = 2048: 851 -> 617 MB per launch)
-  int ct = (int)((1 << 20) / tile_bytes), pm = (int)((2 << 20) / tile_bytes);
-  if (ct < 1) ct = 1;
-  if (pm < 1) pm = 1;
-  if (ct >= tiles_n) { ct = tiles_n; pm = 1; }              // narrow output: plain panel-major order
-  else if (!NT) return launch<ACT, HAS_RES, PRO, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);   // wide: NT epilogue
-  while (tiles_n % ct) --ct;                                // chunks of equal width (tiles_n is a power of two in this network)
-  // half-height panels for the last, partial round; slots = 3 workgroups per compute unit
-  int64_t p_full = tiles_m, panels = tiles_m;
-  {
-    const int64_t slots = (int64_t)kMinWG * cu_count(st);
-    const int64_t tiles = tiles_m * tiles_n;
-    if (slots > 0 && tiles > slots && tiles % slots != 0) {
-      p_full = (tiles / slots) * slots / tiles_n / 8 * 8;            // whole rounds, whole XCD rows of panels
-      const int64_t rest_rows = M - p_full * kTM;
-      panels = p_full + cdiv(rest_rows, kTM / 2);
-    }
-  }
-  const int64_t panels_per_xcd = cdiv(cdiv(panels, 8), pm) * pm;   // row panels padded to whole groups on each of the 8 XCDs
-  if (panels_per_xcd * 8 * tiles_n > 2147483647) return 0;
-  const int64_t grid = panels_per_xcd * 8 * tiles_n;
-  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT><<<dim3((unsigned)grid), dim3(kThreads), lds_bytes, st>>>(
-      X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, tiles_n, pm, ct, (int)p_full);
+  Geometry g;
+  if (!conv1x1_geometry(M, K, N, cu_count(st), g)) return 0;
+  if (g.nt && !NT) return launch<ACT, HAS_RES, PRO, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
+  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
+      X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, g.tiles_n, g.pm, g.ct, (int)g.p_full);
   return ok();
 }
 
@@ -280,6 +307,28 @@ extern "C" {
 // 1 when the fused kernel takes the problem (K a multiple of 16, N a multiple of 128), 0 when the caller must run
 // the convolution and the ABN pass separately.
 int skd_conv1x1_abn_supported(int64_t M, int K, int N) { return M > 0 && K > 0 && N > 0 && K % kBK == 0 && N % kTN == 0; }
+
+// Host only, no device needed: the launch geometry of an (M, K, N) problem on `cus` compute units,
+//   out[7] = tiles_n, ct, pm, p_full, panels, grid, nt (see Geometry); 0 when the kernel does not take the problem.
+int skd_conv1x1_abn_geometry(int64_t M, int K, int N, int cus, int64_t *out) {
+  Geometry g;
+  if (!skd_conv1x1_abn_supported(M, K, N) || cus < 0 || !out || !conv1x1_geometry(M, K, N, cus, g)) return 0;
+  out[0] = g.tiles_n; out[1] = g.ct; out[2] = g.pm; out[3] = g.p_full; out[4] = g.panels; out[5] = g.grid; out[6] = g.nt;
+  return 1;
+}
+
+// ... and the output tiles of the `count` workgroups from `block` on, by the kernel's own decode: out[3 i ...] = m0, rows, n0 of
+// workgroup block + i (rows = 0: the workgroup is padding and exits); 0 when a workgroup is outside the grid.
+int skd_conv1x1_abn_tile_of(int64_t M, int K, int N, int cus, int64_t block, int64_t count, int64_t *out) {
+  Geometry g;
+  if (!skd_conv1x1_abn_supported(M, K, N) || cus < 0 || !out || !conv1x1_geometry(M, K, N, cus, g)) return 0;
+  if (block < 0 || count < 0 || block > g.grid || count > g.grid - block) return 0;
+  for (int64_t i = 0; i < count; ++i) {
+    const TileOf t = conv1x1_tile_of((unsigned)(block + i), M, g.tiles_n, g.pm, g.ct, (int)g.p_full);
+    out[3 * i] = t.m0; out[3 * i + 1] = t.rows; out[3 * i + 2] = t.n0;
+  }
+  return 1;
+}
 
 static int conv1x1_dispatch(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
                             const float *mean, const float *var, const float *weight, const float *bias, const float *ppack,

@@ -610,6 +610,53 @@ def test_frozen_bottleneck_fused_tail_equals_conv_plus_two_abn_passes(monkeypatc
     assert blk(x.clone(memory_format=torch.channels_last).requires_grad_(True)).requires_grad
 
 
+def test_teacher_reduce_gemm_routing_and_split_reduce_switch(monkeypatch):
+    """pspnet_combine.SPLIT_REDUCE: which of the frozen ResNet101 teacher's reduce / stride-1 down-sample 1x1 GEMMs run on the split
+    core of csrc/conv1x1.hip (functional.conv1x1_abn_eval without a prologue; here on the C double) and which on the library GEMM
+    (functional.conv1x1_bn_blas) -- the library keeps 512 -> 128 -- and that the switch changes the route, not the result.
+    Counts per forward, from ResNet._make_layer ([3, 4, 23, 3] blocks, 128 channels in) and Bottleneck.forward: layer1's down-sample
+    128 -> 256 (its conv1s have 64 outputs: MIOpen); layer2[0].conv1 256 -> 128, layer2[1..3].conv1 512 -> 128 (its down-sample has
+    stride 2: MIOpen); layer3's down-sample 512 -> 1024, layer3[0].conv1 512 -> 256, layer3[1..22].conv1 1024 -> 256; layer4's
+    down-sample 1024 -> 2048, layer4[0].conv1 1024 -> 512, layer4[1..2].conv1 2048 -> 512."""
+    from collections import Counter
+    from structure_knowledge_distillation_amd import functional as SF
+    kernel_shapes = {(128, 256): 1, (256, 128): 1, (512, 256): 1, (512, 1024): 1, (1024, 256): 22, (1024, 512): 1, (1024, 2048): 1,
+                     (2048, 512): 2}
+    library_shapes = {(512, 128): 3}
+    torch.manual_seed(6)
+    net = PC_MOD.Res_pspnet(PC_MOD.Bottleneck, [3, 4, 23, 3], 19).eval().to(memory_format=torch.channels_last)
+    seen = {"kernel": Counter(), "library": Counter()}
+    kernel, library = SF.conv1x1_abn_eval, SF.conv1x1_bn_blas
+
+    def spy_kernel(x, w, *a, **kw):
+        if kw.get("pro", a[8] if len(a) > 8 else None) is None:       # the block tails pass ``pro``: not the routed calls
+            seen["kernel"][(x.shape[1], w.shape[0])] += 1
+        return kernel(x, w, *a, **kw)
+
+    def spy_library(x, conv, *a, **kw):
+        seen["library"][(conv.in_channels, conv.out_channels)] += 1
+        return library(x, conv, *a, **kw)
+    monkeypatch.setattr(SF, "conv1x1_abn_eval", spy_kernel)
+    monkeypatch.setattr(SF, "conv1x1_bn_blas", spy_library)
+    x = torch.randn(1, 3, 49, 49).contiguous(memory_format=torch.channels_last)
+    outs = {}
+    for flag in (True, False):
+        monkeypatch.setattr(PC_MOD, "SPLIT_REDUCE", flag)
+        seen["kernel"].clear()
+        seen["library"].clear()
+        with torch.no_grad():
+            outs[flag] = net(x.clone(memory_format=torch.channels_last))
+        if flag:
+            assert dict(seen["kernel"]) == kernel_shapes and dict(seen["library"]) == library_shapes, seen
+        else:
+            assert not seen["kernel"] and dict(seen["library"]) == {**kernel_shapes, **library_shapes}, seen
+    for a, b in zip(outs[True], outs[False]):
+        a, b = a.double(), b.double()
+        assert a.shape == b.shape and bool(torch.isfinite(a).all())
+        err = float((a - b).abs().max()) / max(float(b.abs().max()), 1e-30)
+        assert err <= 2e-5, err
+
+
 def test_teacher_dsn_head_is_optional_and_everything_else_unchanged():
     """``model.teacher.skip_dsn = True`` (bench.py --dsn-ab's informative figure; never the default) skips the frozen teacher's
     deep-supervision head -- read by nothing but the teacher CE the reference computes and discards (kd_model.py:129):

@@ -1074,10 +1074,11 @@ def test_conv1x1_abn_gemm(hip, ref, M, K, N, act, with_res):
     r = torch.randn(M, N, generator=g) if with_res else None
     mean, var = torch.randn(N, generator=g) * 0.3, torch.rand(N, generator=g) + 0.5
     ga, be = torch.randn(N, generator=g), torch.randn(N, generator=g)
-    o_r, o_g = torch.empty(M, N), torch.full((M, N), 7.0, device=DEV)
+    o_r, o_g = torch.empty(M, N), torch.full((M + 160, N), 7.0, device=DEV)      # 160 rows (more than a tile) of sentinel slack
     assert ref.skd_conv1x1_abn_nhwc(M, K, N, P(x), P(w), P(r), P(o_r), P(mean), P(var), P(ga), P(be), 1e-5, act, 0.01, None)
     assert hip.skd_conv1x1_abn_nhwc(M, K, N, P(gpu(x)), P(gpu(w)), P(gpu(r)), P(o_g), P(gpu(mean)), P(gpu(var)), P(gpu(ga)), P(gpu(be)), 1e-5, act, 0.01, None)
-    close(o_g, o_r, 2e-5, "conv1x1+abn")
+    close(o_g[:M], o_r, 2e-5, "conv1x1+abn")
+    assert bool((o_g[M:] == 7.0).all()), "rows beyond M were written"
     assert hip.skd_conv1x1_abn_supported(M, K, N) == 1 and hip.skd_conv1x1_abn_supported(M, K + 8, N) == 0 and hip.skd_conv1x1_abn_supported(M, K, N + 64) == 0
     assert hip.skd_conv1x1_abn_nhwc(M, K + 8, N, P(gpu(x)), P(gpu(w)), None, P(o_g), P(gpu(mean)), P(gpu(var)), None, None, 1e-5, act, 0.01, None) == 0
 
@@ -1095,7 +1096,7 @@ def test_conv1x1_abn_gemm_with_bn_relu_prologue(hip, ref, M, K, N, with_res, aff
     ga, be = torch.randn(N, generator=g), torch.randn(N, generator=g)
     pm, pv = torch.randn(K, generator=g) * 0.5, torch.rand(K, generator=g) + 0.5
     pw, pb = (torch.randn(K, generator=g), torch.randn(K, generator=g) * 0.5) if affine else (None, None)
-    o_r, o_g = torch.empty(M, N), torch.full((M, N), 7.0, device=DEV)
+    o_r, o_g = torch.empty(M, N), torch.full((M + 160, N), 7.0, device=DEV)      # 160 rows (more than a tile) of sentinel slack
     pk_r, pk_g = torch.empty(4, K), torch.empty(4, K, device=DEV)
     assert ref.skd_abn_pack_eval_params(K, P(pm), P(pv), P(pw), P(pb), 1e-5, P(pk_r), None)
     assert hip.skd_abn_pack_eval_params(K, P(gpu(pm)), P(gpu(pv)), P(gpu(pw)), P(gpu(pb)), 1e-5, P(pk_g), None)
@@ -1104,7 +1105,8 @@ def test_conv1x1_abn_gemm_with_bn_relu_prologue(hip, ref, M, K, N, with_res, aff
     xg = gpu(x)
     assert hip.skd_conv1x1_abn_pro_nhwc(M, K, N, P(xg), P(gpu(w)), P(gpu(r)), P(o_g), P(gpu(mean)), P(gpu(var)), P(gpu(ga)), P(gpu(be)), 1e-5,
                                         P(pk_g), 3, 0.01, None)
-    close(o_g, o_r, 3e-5, "bn+relu -> conv1x1 -> abn")
+    close(o_g[:M], o_r, 3e-5, "bn+relu -> conv1x1 -> abn")
+    assert bool((o_g[M:] == 7.0).all()), "rows beyond M were written"
     assert torch.equal(xg.cpu(), x)
     assert hip.skd_conv1x1_abn_pro_nhwc(M, K, N, P(xg), P(gpu(w)), None, P(o_g), P(gpu(mean)), P(gpu(var)), None, None, 1e-5, None, 3, 0.01, None) == 0
 
@@ -1529,3 +1531,48 @@ def test_frozen_bottleneck_blas_tail(cfg, monkeypatch):
         y = torch.nn.functional.conv2d(x.double().cpu().contiguous(), blk.conv1.weight.double().cpu())
         want = torch.relu((y - bn.running_mean.double().cpu().view(1, -1, 1, 1)) * s.view(1, -1, 1, 1) + bn.bias.double().cpu().view(1, -1, 1, 1))
     close(got, want, 2e-5, "conv1x1_bn_blas vs float64")
+
+
+def test_frozen_layer4_block_split_reduce_on_and_off(monkeypatch):
+    """The first block of layer 4 -- where the three long-K routes of pspnet_combine.SPLIT_REDUCE meet: conv1 1024 -> 512, the
+    down-sample branch 1024 -> 2048 and, behind the 3x3, the tail 512 -> 2048 -- with the reduce / down-sample GEMMs on the split
+    core of csrc/conv1x1.hip (SPLIT_REDUCE) and on the library GEMM, both against the plain op sequence in float64 on the CPU."""
+    from structure_knowledge_distillation_amd.networks.pspnet_combine import Bottleneck, BatchNorm2d
+    F = torch.nn.functional
+    torch.manual_seed(5)
+    down = torch.nn.Sequential(torch.nn.Conv2d(1024, 2048, 1, 1, bias=False), BatchNorm2d(2048))
+    blk = Bottleneck(1024, 512, stride=1, dilation=4, downsample=down).eval()
+    for mod in blk.modules():
+        if getattr(mod, "running_mean", None) is not None:
+            mod.running_mean.normal_(0, 0.5)
+            mod.running_var.uniform_(0.5, 2.0)
+            mod.weight.data.normal_(0, 1.0)
+            mod.bias.data.normal_(0, 0.5)
+    x = torch.relu(torch.randn(1, 1024, 33, 33))
+
+    def bn64(y, bn):
+        v = lambda t: t.detach().double().view(1, -1, 1, 1)
+        return (y - v(bn.running_mean)) / torch.sqrt(v(bn.running_var) + bn.eps) * (v(bn.weight).abs() + bn.eps) + v(bn.bias)
+
+    with torch.no_grad():
+        xd = x.double()
+        o = torch.relu(bn64(F.conv2d(xd, blk.conv1.weight.double()), blk.bn1))
+        o = torch.relu(bn64(F.conv2d(o, blk.conv2.weight.double(), None, 1, 4, 4), blk.bn2))
+        o = bn64(F.conv2d(o, blk.conv3.weight.double()), blk.bn3)
+        want = torch.relu(o + bn64(F.conv2d(xd, down[0].weight.double()), down[1]))
+    blk = blk.to(DEV).to(memory_format=torch.channels_last)
+    dx = x.to(DEV).contiguous(memory_format=torch.channels_last)
+    from structure_knowledge_distillation_amd import functional as SF
+    calls = []
+    kernel, library = SF.conv1x1_abn_eval, SF.conv1x1_bn_blas
+    monkeypatch.setattr(SF, "conv1x1_abn_eval", lambda x, w, *a, **kw: (calls.append(("kernel", x.shape[1], w.shape[0])), kernel(x, w, *a, **kw))[1])
+    monkeypatch.setattr(SF, "conv1x1_bn_blas", lambda x, conv, *a, **kw: (calls.append(("library", x.shape[1], conv.out_channels)),
+                                                                        library(x, conv, *a, **kw))[1])
+    for flag in (True, False):
+        monkeypatch.setattr(PC_MOD, "SPLIT_REDUCE", flag)
+        del calls[:]
+        with torch.no_grad():
+            got = blk(dx.clone(memory_format=torch.channels_last))
+        route = "kernel" if flag else "library"
+        assert sorted(calls) == sorted([(route, 1024, 512), (route, 1024, 2048), ("kernel", 512, 2048)]), calls
+        close(got, want, 2e-5, "layer-4 block, SPLIT_REDUCE %s, vs float64" % flag)
