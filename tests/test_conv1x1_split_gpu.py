@@ -19,6 +19,7 @@ within 2e-6: largest 1.55e-6 at K = 4096); those figures are the "reduce-" / "do
 measured once on an MI355X by tools/conv1x1_parent_err.py and tabulated in profiles/r13_conv1x1_reduce_accuracy.md.
 
 Every launch writes into a buffer with sentinel slack behind row M, which must stay untouched.
+(The guard in FRONT of the output, and the guards around every input, are in the bounds table: tests/bounds_cases.py.)
 """
 import ctypes
 import zlib

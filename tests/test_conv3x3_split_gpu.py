@@ -8,6 +8,7 @@ tolerance for convolution outputs.  PARENT_ERR holds those figures, measured onc
 figures are tabulated in profiles/r12_conv3x3_split_accuracy.md.  The factor 4 is the one the 1x1 core was accepted under
 (tests/test_conv1x1_split_gpu.py).  The integer cases must be bit-exact.  Every launch writes into a buffer with sentinel
 slack behind row M, which must stay untouched.
+(The guard in FRONT of the output, and the guards around the input, the weights and the pack, are in the bounds table: tests/bounds_cases.py.)
 """
 import ctypes
 import zlib
