@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libskd_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd.h"))
 EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval.h"))
+MS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval_ms.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -148,6 +149,14 @@ EXT_SIGNATURES = {
     "skd_conv1x1_abn_tile_of": (_I, [_L, _I, _I, _I, _L, _L, _P]),
 }
 
+# Entry points declared in include/skd_eval_ms.h (csrc/evaluate_multiscale.hip): extension entries like the ones above, in a
+# table of their own (tests/test_multiscale_eval_cpu.py checks header <-> table <-> exported symbols, tests/test_multiscale_eval_gpu.py
+# holds their guard-band cases; DESIGN.md says why they are not simply rows of EXT_SIGNATURES).
+MS_SIGNATURES = {
+    "skd_zoom_linear": (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
+    "skd_seg_multiscale": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -177,7 +186,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for table in (SIGNATURES, EXT_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -15,16 +15,15 @@
 // stay in registers (2 CT VGPRs); a class count above 32 is refused by the entry point rather than spilled.
 // The tile table lives in device memory: every lane reads the same row, so the loads are scalar and cached, and the
 // number of tiles is not capped by the kernel-argument size.
-// Floating-point contraction is OFF in this file, as in evaluate.hip: individually rounded mul / add.
-#include "skd_common.hpp"
+// Floating-point contraction is OFF in this file, as in evaluate.hip: individually rounded mul / add.  The interpolation and the
+// epilogue are shared with evaluate_multiscale.hip and live in eval_dev.hpp (contraction is off there too).
+#include "eval_dev.hpp"
 #include "skd_eval.h"
 
 #pragma clang fp contract(off)
 
 namespace skd {
 namespace {
-
-constexpr int kMaxSlidingClasses = 32;
 
 template <int CT>
 __global__ __launch_bounds__(kThreads) void seg_sliding_kernel(
@@ -33,8 +32,7 @@ __global__ __launch_bounds__(kThreads) void seg_sliding_kernel(
     unsigned long long *__restrict__ confusion, int T, int C, int h, int w, int H, int W, int ignore_index, float sy,
     float sx) {
   extern __shared__ unsigned int hist[];  // C * C
-  for (int i = threadIdx.x; i < C * C; i += kThreads) hist[i] = 0u;
-  __syncthreads();
+  hist_clear(hist, C);
   const int64_t total = (int64_t)H * W;
   const int hw = h * w;
   const int64_t chw = (int64_t)C * hw;
@@ -48,56 +46,17 @@ __global__ __launch_bounds__(kThreads) void seg_sliding_kernel(
     for (int t = 0; t < T; ++t) {
       const int ty1 = tiles[4 * t + 0], tx1 = tiles[4 * t + 1], ty2 = tiles[4 * t + 2], tx2 = tiles[4 * t + 3];
       if (Y < ty1 || Y >= ty2 || X < tx1 || X >= tx2) continue;
-      // upsample_bilinear2d, align_corners=True, at (Y - y1, X - x1) of the tile: src = scale * dst; i0 = (int)src;
-      // i1 = i0 + (i0 < in - 1).  The clamps keep every read inside the tile's logit map whatever the table holds.
-      const float fy = sy * (float)(Y - ty1), fx = sx * (float)(X - tx1);
-      int y0 = (int)fy, x0 = (int)fx;
-      if (y0 > h - 1) y0 = h - 1;
-      if (x0 > w - 1) x0 = w - 1;
-      const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-      const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-      const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+      const Bilinear b = bilinear_at(sy, sx, Y - ty1, X - tx1, h, w);  // at (Y - y1, X - x1) of the tile
       const float *p = logits + (int64_t)t * chw;
-      const int o00 = y0 * w + x0, o01 = y0 * w + x1, o10 = y1 * w + x0, o11 = y1 * w + x1;
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        if (c < C) {
-          const float *q = p + c * hw;
-          const float v = ly0 * (lx0 * q[o00] + lx1 * q[o01]) + ly1 * (lx0 * q[o10] + lx1 * q[o11]);
-          acc[c] += (double)v;
-        }
-      }
-      ++cover;
-    }
-    const double n = (double)cover;  // 0 / 0 = NaN for a pixel outside every tile
-    double best = 0.0;
-    int arg = 0;
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      if (c < C) {
-        acc[c] = acc[c] / n;
-        if (c == 0 || acc[c] > best) {  // first maximum wins (numpy argmax); a NaN never replaces the running maximum
-          best = acc[c];
-          arg = c;
-        }
-      }
-    }
-    if (probs != nullptr) {
-      double *o = probs + pix * C;
 #pragma unroll
       for (int c = 0; c < CT; ++c)
-        if (c < C) o[c] = acc[c];
+        if (c < C) acc[c] += (double)bilinear_value(b, p + c * hw);
+      ++cover;
     }
-    if (pred != nullptr) pred[pix] = remap != nullptr ? remap[arg] : (unsigned char)arg;
-    if (target != nullptr) {
-      const int64_t g = target[pix];
-      if (g != (int64_t)ignore_index && g >= 0 && g < C) atomicAdd(&hist[(int)g * C + arg], 1u);
-    }
+    // 0 / 0 = NaN for a pixel outside every tile
+    finish_pixel<CT>(acc, (double)cover, C, pix, target, ignore_index, remap, pred, probs, hist);
   }
-  __syncthreads();
-  if (confusion != nullptr)
-    for (int i = threadIdx.x; i < C * C; i += kThreads)
-      if (hist[i] != 0u) atomicAdd(&confusion[i], (unsigned long long)hist[i]);
+  hist_flush(hist, C, confusion);
 }
 
 }  // namespace
@@ -110,33 +69,20 @@ extern "C" {
 int skd_seg_sliding(int T, int C, int h, int w, int tile_h, int tile_w, int H, int W, const float *logits,
                     const int *tiles, const int64_t *target, int ignore_index, const uint8_t *remap, uint8_t *pred,
                     double *probs, int64_t *confusion, skd_stream_t stream) {
-  if (T <= 0 || C <= 0 || C > kMaxSlidingClasses || h <= 0 || w <= 0 || tile_h <= 0 || tile_w <= 0 || H <= 0 || W <= 0) return 0;
+  if (T <= 0 || C <= 0 || C > kMaxAccumClasses || h <= 0 || w <= 0 || tile_h <= 0 || tile_w <= 0 || H <= 0 || W <= 0) return 0;
   if (!logits || !tiles) return 0;
   if (target != nullptr && confusion == nullptr) return 0;
   if ((int64_t)C * h * w > (int64_t)INT32_MAX) return 0;  // per-tile offsets are 32-bit
   const float sy = tile_h > 1 ? (float)(h - 1) / (float)(tile_h - 1) : 0.f;
   const float sx = tile_w > 1 ? (float)(w - 1) / (float)(tile_w - 1) : 0.f;
-  const int64_t total = (int64_t)H * W;
-  int64_t wgs = cdiv(total, (int64_t)kThreads * 4);  // ~4 pixels per lane: one histogram flush per 1024 pixels
-  if (wgs < 1) wgs = 1;
-  if (wgs > 8192) wgs = 8192;
-  const dim3 grid((unsigned)wgs), block(kThreads);
+  const dim3 grid(accum_grid((int64_t)H * W)), block(kThreads);
   const size_t lds = sizeof(unsigned int) * C * C;
   unsigned long long *cm = reinterpret_cast<unsigned long long *>(confusion);
   hipStream_t st = as_stream(stream);
-#define SKD_SLIDING_LAUNCH(CT) \
-  seg_sliding_kernel<CT><<<grid, block, lds, st>>>(logits, tiles, target, remap, pred, probs, cm, T, C, h, w, H, W, ignore_index, sy, sx)
-  if (C <= 8)
-    SKD_SLIDING_LAUNCH(8);
-  else if (C <= 16)
-    SKD_SLIDING_LAUNCH(16);
-  else if (C <= 19)
-    SKD_SLIDING_LAUNCH(19);
-  else if (C <= 21)
-    SKD_SLIDING_LAUNCH(21);
-  else
-    SKD_SLIDING_LAUNCH(32);
-#undef SKD_SLIDING_LAUNCH
+  with_class_bound(C, [&](auto ct) {
+    seg_sliding_kernel<decltype(ct)::value><<<grid, block, lds, st>>>(logits, tiles, target, remap, pred, probs, cm, T, C, h, w,
+                                                                      H, W, ignore_index, sy, sx);
+  });
   return ok();
 }
 

@@ -741,6 +741,100 @@ def seg_sliding(logits, tiles, tile_size, out_size, target=None, ignore_index=25
     return pred, probs, confusion
 
 
+def _require_ms_entry(name):
+    if not _lib.has_entry(name):
+        raise NotImplementedError("the active back-end does not provide %s (include/skd_eval_ms.h)" % name)
+
+
+def zoom_size(n, scale):
+    """Output length of ``scipy.ndimage.zoom`` for an axis of ``n`` at ``scale``: Python's ``round``, half to even
+    (30 x 0.75 = 22.5 gives 22, 50 x 0.75 = 37.5 gives 38)."""
+    return int(round(int(n) * float(scale)))
+
+
+def zoom_linear(image, scale, mirror=False, channels_last=False):
+    """``scipy.ndimage.zoom(image, (1, 1, scale, scale), order=1, prefilter=False)`` of networks/evaluate.py:127 as one kernel
+    (csrc/evaluate_multiscale.hip): float64 coordinates and weights, one cast to fp32, and scipy's zeroed last row / column
+    where the last coordinate rounds above ``n - 1``.  ``image``: (1, C, H, W) or (C, H, W) fp32.  Returns (F, C, Ho, Wo) with
+    F = 1 + mirror; element 1 is element 0 mirrored in X.  ``channels_last``: the result has channels-last memory."""
+    _lib.require_device(image)
+    _require_ms_entry("skd_zoom_linear")
+    img = _f32c(image.detach(), "zoom_linear")
+    if img.dim() == 4 and img.shape[0] == 1:
+        img = img[0]
+    if img.dim() != 3:
+        raise ValueError("zoom_linear: one image (1, C, H, W) or (C, H, W) expected (got %s)" % (tuple(image.shape),))
+    c, h, w = img.shape
+    ho, wo = zoom_size(h, scale), zoom_size(w, scale)
+    if min(c, h, w) <= 0 or ho < 2 or wo < 2:
+        raise ValueError("zoom_linear: a %d x %d image at scale %r gives %d x %d; both axes need at least 2" % (h, w, scale, ho, wo))
+    f = 2 if mirror else 1
+    out = torch.empty((f, c, ho, wo), dtype=torch.float32, device=img.device,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    _lib.check(_lib.get().skd_zoom_linear(c, h, w, ho, wo, img.data_ptr(), out.data_ptr(), int(bool(mirror)), int(bool(channels_last)),
+                                          _lib.stream_of(img)), "skd_zoom_linear")
+    return out
+
+
+def seg_multiscale(logits, out_size, target=None, ignore_index=255, confusion=None, remap=None, want_pred=True, want_probs=False):
+    """Multi-scale / flip evaluation tail (networks/evaluate.py:115-134, 187-198) as one fused kernel.  ``logits``: a list of
+    per-scale (F, C, h_s, w_s) fp32 tensors, the same F (1, or 2 = [forward, forward of the X-mirrored image]) and C throughout.
+    Per scale, in list order: align-corners upsample to ``out_size`` = (H, W) in fp32, with F = 2 the fp32 average
+    ``0.5 * (a + b mirrored back)``, float64 sum; mean over the scales, argmax (first maximum), optional 256-entry uint8
+    ``remap`` of the written prediction, (C, C) int64 ``confusion`` accumulated with the un-remapped prediction over the pixels
+    of ``target`` (H, W) int64 that are not ``ignore_index``.
+    Returns (pred (H, W) uint8 or None, probs (H, W, C) float64 or None, confusion [None without target and confusion])."""
+    logits = list(logits)
+    _lib.require_device(target, confusion, remap, *logits)
+    _require_ms_entry("skd_seg_multiscale")
+    if not logits:
+        raise ValueError("seg_multiscale: at least one scale expected")
+    maps = [_f32c(lg.detach(), "seg_multiscale") for lg in logits]
+    if any(m.dim() != 4 for m in maps):
+        raise ValueError("seg_multiscale: per-scale logits (F, C, h, w) expected (got %s)" % ([tuple(m.shape) for m in maps],))
+    f, c = maps[0].shape[0], maps[0].shape[1]
+    if f not in (1, 2):
+        raise ValueError("seg_multiscale: F is 1, or 2 with a mirrored forward (got %d)" % f)
+    if not 1 <= c <= SEG_SLIDING_MAX_CLASSES:
+        raise ValueError("seg_multiscale: 1 <= classes <= %d (got %d)" % (SEG_SLIDING_MAX_CLASSES, c))
+    H, W = (int(v) for v in out_size)
+    if min(H, W) <= 0:
+        raise ValueError("seg_multiscale: out_size must be positive")
+    rows, off = [], 0
+    for m in maps:
+        if m.shape[0] != f or m.shape[1] != c:
+            raise ValueError("seg_multiscale: every scale needs the same (F, C) = (%d, %d) (got %s)" % (f, c, tuple(m.shape)))
+        if min(m.shape[2], m.shape[3]) < 1 or m.numel() > 2 ** 31 - 1:
+            raise ValueError("seg_multiscale: a per-scale map holds between 1 and 2^31 - 1 floats (got %s)" % (tuple(m.shape),))
+        if m.device != maps[0].device:
+            raise ValueError("seg_multiscale: all scales on one device expected")
+        rows.append((off, m.shape[2], m.shape[3]))
+        off += m.numel()
+    dev = maps[0].device
+    packed = maps[0].reshape(-1) if len(maps) == 1 else torch.cat([m.reshape(-1) for m in maps])
+    table = torch.tensor(rows, dtype=torch.int64).reshape(len(rows), 3).to(dev)
+    if target is not None:
+        if target.dtype != torch.int64:
+            raise TypeError("seg_multiscale: int64 target expected (got %s)" % target.dtype)
+        if tuple(target.shape[-2:]) != (H, W) or target.numel() != H * W:
+            raise ValueError("seg_multiscale: target %s does not match out_size %s" % (tuple(target.shape), (H, W)))
+        tg = target if target.is_contiguous() else target.contiguous()
+        if confusion is None:
+            confusion = torch.zeros((c, c), dtype=torch.int64, device=dev)
+    else:
+        tg = None
+    if confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != (c, c) or not confusion.is_contiguous()):
+        raise TypeError("seg_multiscale: confusion must be a contiguous (%d, %d) int64 tensor" % (c, c))
+    if remap is not None and (remap.dtype != torch.uint8 or remap.numel() != 256 or not remap.is_contiguous()):
+        raise TypeError("seg_multiscale: remap must be 256 contiguous uint8 entries")
+    pred = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_pred else None
+    probs = torch.empty((H, W, c), dtype=torch.float64, device=dev) if want_probs else None
+    _lib.check(_lib.get().skd_seg_multiscale(len(rows), f, c, H, W, packed.data_ptr(), table.data_ptr(), _lib.ptr(tg), int(ignore_index),
+                                             _lib.ptr(remap), _lib.ptr(pred), _lib.ptr(probs), _lib.ptr(confusion),
+                                             _lib.stream_of(packed)), "skd_seg_multiscale")
+    return pred, probs, confusion
+
+
 def pool_out_size(n, k):
     """ceil_mode=True, stride = kernel, no padding."""
     return -(-n // k)

@@ -18,9 +18,19 @@ order, over the tiles that cover it, so the float64 sums carry the reference's b
 device and written as a palette PNG ``<outputs>/<name>.png``; nothing is scored and None is returned.  ``outputs=`` also
 dumps the (un-remapped) predictions of a validation run; without it a validation run writes no file.
 
-Not provided: multi-scale / flip averaging (evaluate.py:115-134 with more than ``[1.0], False``, which evaluate_main never
-passes) and the cv2-based dataset readers.  A back-end without ``skd_seg_sliding`` (the plain-C double of oracle/) cannot
-run the sliding mode: NotImplementedError names the entry point.
+Multi-scale / flip evaluation (evaluate.py:115-134, ``predict_multiscale`` with more than ``[1.0], False`` -- the mode of
+reported Cityscapes numbers and test-server submissions): ``evaluate_main(whole=True, scales=[...], flip=True)``.  Per scale
+one kernel resizes the image exactly as ``scipy.ndimage.zoom(order=1, prefilter=False)`` does (float64 coordinates, output
+size by Python ``round``, the zeroed last row / column of some sizes included) and writes the X-mirrored copy next to it; the
+two are forwarded as one batch of 2 and the logits stay on the device.  One gather kernel (csrc/evaluate_multiscale.hip)
+then does per pixel what the reference does per scale on the host with H x W x C arrays: upsample, fp32 flip average,
+float64 sum in scale order, mean, argmax, remap, confusion.  ``predict_multiscale`` / ``predict_whole`` return the
+reference's arrays for callers that want them.  ``scales`` None or ``[1.0]`` without ``flip`` is the whole-image path above,
+unchanged.
+
+Not provided: the cv2-based dataset readers; ``recurrence`` and flipping in sliding mode are accepted and ignored, as in the
+reference.  A back-end without ``skd_seg_sliding`` / ``skd_zoom_linear`` / ``skd_seg_multiscale`` (the plain-C double of
+oracle/) cannot run the sliding / multi-scale modes: NotImplementedError names the entry point.
 """
 import os
 from math import ceil
@@ -183,6 +193,76 @@ def predict_sliding(net, image, tile_size, classes, flip_evaluation=False, recur
     return probs.cpu().numpy()
 
 
+def _require_multiscale_backend(what):
+    for entry in ("skd_zoom_linear", "skd_seg_multiscale"):
+        if not _lib.has_entry(entry):
+            raise NotImplementedError("%s needs the entry point %s (include/skd_eval_ms.h, csrc/evaluate_multiscale.hip), "
+                                      "which the active back-end does not provide" % (what, entry))
+
+
+def _model_device(net):
+    try:
+        return next(net.parameters()).device
+    except StopIteration:
+        return torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+
+
+def _forward_logits(model, batch):
+    out = model(batch)
+    if isinstance(out, (list, tuple)):
+        out = out[0]
+    return out.float()
+
+
+def _scale_logits(model, image, scales, flip, cl_model):
+    """Per scale: resize ``image`` (1, C, H, W) on the device (with its X-mirrored copy when flipping) and forward the batch of
+    F = 1 + flip once.  Returns the list of (F, classes, h_s, w_s) logits, kept on the device."""
+    out = []
+    for scale in scales:
+        batch = SF.zoom_linear(image, float(scale), mirror=flip, channels_last=cl_model)
+        out.append(_forward_logits(model, batch))
+    return out
+
+
+def predict_whole(net, image, tile_size, recurrence=1):
+    """evaluate.py:106-113: the network's logits on ``image`` (1, 3, h, w), up-sampled (bilinear, align_corners) to
+    ``tile_size`` = (th, tw): a (th, tw, classes) float32 numpy array.  ``recurrence`` is accepted and ignored."""
+    _require_multiscale_backend("predict_whole")
+    device = _model_device(net)
+    th, tw = _parse_size(tile_size)
+    image = torch.as_tensor(np.asarray(image) if not torch.is_tensor(image) else image).float().to(device)
+    if image.dim() != 4 or image.shape[0] != 1:
+        raise ValueError("predict_whole takes one image (1, 3, h, w) (got %s)" % (tuple(image.shape),))
+    with torch.no_grad():
+        if _channels_last_model(net, device):
+            image = image.contiguous(memory_format=torch.channels_last)
+        logits = _forward_logits(net, image)
+        # one scale, no flip: sum = (double)v and v / 1.0 is exact, so the cast back to float32 loses nothing
+        _, probs, _ = SF.seg_multiscale([logits], (th, tw), want_pred=False, want_probs=True)
+    return probs.float().cpu().numpy()
+
+
+def predict_multiscale(net, image, tile_size, scales, classes, flip_evaluation, recurrence=1):
+    """evaluate.py:115-134: the (H, W, classes) float64 mean over ``scales`` of the up-sampled (and, with ``flip_evaluation``,
+    flip-averaged) logits as a numpy array.  ``image``: numpy or tensor (1, 3, H, W); ``tile_size`` must be its (H, W) -- the
+    reference's ``full_probs += scaled_probs`` only broadcasts then.  ``recurrence`` is accepted and ignored."""
+    _require_multiscale_backend("predict_multiscale")
+    device = _model_device(net)
+    image = _as_image(image, device)
+    H, W = int(image.shape[2]), int(image.shape[3])
+    if _parse_size(tile_size) != (H, W):
+        raise ValueError("predict_multiscale: tile_size %s must equal the image's size %s" % (tuple(_parse_size(tile_size)), (H, W)))
+    scales = [float(v) for v in scales]
+    if not scales:
+        raise ValueError("predict_multiscale: at least one scale expected")
+    with torch.no_grad():
+        logits = _scale_logits(net, image, scales, bool(flip_evaluation), _channels_last_model(net, device))
+        if logits[0].shape[1] != classes:
+            raise ValueError("predict_multiscale: the network returns %d classes, not %d" % (logits[0].shape[1], classes))
+        _, probs, _ = SF.seg_multiscale(logits, (H, W), want_pred=False, want_probs=True)
+    return probs.cpu().numpy()
+
+
 def _save_png(pred, directory, name, palette):
     """evaluate.py:189-191: mode-P PNG with the 256-colour palette."""
     try:
@@ -197,19 +277,30 @@ def _save_png(pred, directory, name, palette):
 
 
 def evaluate_main(model, loader, gpu_id, input_size, num_classes, whole=False, recurrence=1, type="val", rank=0, world=1,
-                  group=None, outputs=None, tile_batch=None):
+                  group=None, outputs=None, tile_batch=None, scales=None, flip=False):
     """``type='val'``: returns (mean_IU, IU_array) like evaluate.py:156-206.  ``loader`` yields (image (1,3,H,W) float,
     label (1,H,W), size, name) like CSDataSet (dataset/datasets.py:121-210); ``size[0][:2]`` is the valid (h, w) of the label.
     ``type='test'``: ``loader`` yields (image, size, name); the predictions are remapped trainId -> id and written as
     palette PNGs ``<outputs>/<name[0]>.png`` (``outputs`` defaults to the reference's ``'outputs'``); returns None.
     ``whole=False``: sliding-window inference with tiles of ``input_size`` ('h,w'), all tiles of an image in one forward
     unless ``tile_batch`` caps the batch.  ``outputs`` with ``type='val'`` also dumps the (un-remapped) predictions.
+    ``scales`` / ``flip`` (``whole=True`` only): multi-scale / flip evaluation, evaluate.py:115-134 -- the prediction is the
+    argmax of the mean over ``scales`` of the (flip-averaged) up-sampled logits; the output size is the label's (the image's
+    for ``type='test'``) and must equal the image's.  ``scales`` None or [1.0] without ``flip`` is plain whole-image scoring.
     ``rank`` / ``world`` (one process per GPU): every rank walks the same loader but evaluates only the batches with
     ``index % world == rank``; the integer confusion matrices are summed over ``group`` with one all-reduce, so every
     rank returns the identical result of the whole validation set (the reference's single process evaluated alone)."""
     if type not in ("val", "test"):
         raise ValueError("evaluate_main: type is 'val' or 'test' (got %r)" % (type,))
     tile_size = None
+    multiscale = None
+    if flip or (scales is not None and [float(v) for v in scales] != [1.0]):
+        if not whole:
+            raise ValueError("evaluate_main: scales / flip need whole=True (sliding-window evaluation ignores them in the reference)")
+        multiscale = ([float(v) for v in scales] if scales is not None else [1.0], bool(flip))
+        if not multiscale[0]:
+            raise ValueError("evaluate_main: scales is None or a non-empty list (got %r)" % (scales,))
+        _require_multiscale_backend("evaluate_main(scales=..., flip=...)")
     if not whole:
         _require_sliding_backend("evaluate_main(whole=False)")
         tile_size = _parse_size(input_size)
@@ -248,7 +339,7 @@ def evaluate_main(model, loader, gpu_id, input_size, num_classes, whole=False, r
                 continue
             seen += 1
             try:
-                _score_batch(model, batch, device, num_classes, cl_model, confusion, type, tile_size, tile_batch, dump)
+                _score_batch(model, batch, device, num_classes, cl_model, confusion, type, tile_size, tile_batch, dump, multiscale)
             except Exception as e:                    # reported AFTER the collective below, so that no rank is left hanging in it
                 if world <= 1:
                     raise
@@ -277,9 +368,12 @@ def evaluate_main(model, loader, gpu_id, input_size, num_classes, whole=False, r
     return iou_from_confusion(confusion.cpu().numpy())
 
 
-def _score_batch(model, batch, device, num_classes, cl_model, confusion, split="val", tile_size=None, tile_batch=None, dump=None):
+def _score_batch(model, batch, device, num_classes, cl_model, confusion, split="val", tile_size=None, tile_batch=None, dump=None,
+                 multiscale=None):
     """One batch.  Whole image (``tile_size`` None): forward, fused upsample + argmax + confusion accumulation
-    (csrc/evaluate.hip).  Sliding: batched tile forward, fused gather over the tiles (csrc/evaluate_sliding.hip).  With
+    (csrc/evaluate.hip).  Sliding: batched tile forward, fused gather over the tiles (csrc/evaluate_sliding.hip).
+    ``multiscale`` = (scales, flip): device resize and one forward per scale, fused gather over the scales
+    (csrc/evaluate_multiscale.hip).  With
     ``dump`` the uint8 prediction (remapped on the device for the test split) is copied to the host and written as a PNG."""
     if split == "val":
         image, label, size = batch[0], batch[1], batch[2]
@@ -300,7 +394,17 @@ def _score_batch(model, batch, device, num_classes, cl_model, confusion, split="
         full = label.new_full(label.shape, ignore_label)
         full[:, :hh, :ww] = label[:, :hh, :ww]
     remap = dump["remap"] if dump is not None else None
-    if tile_size is None:
+    if multiscale is not None:
+        image = _as_image(image, device)
+        H, W = int(image.shape[2]), int(image.shape[3])
+        if full is not None and tuple(full.shape[-2:]) != (H, W):
+            raise ValueError("label %s and image %s differ in size" % (tuple(full.shape), tuple(image.shape)))
+        logits = _scale_logits(model, image, multiscale[0], multiscale[1], cl_model)
+        if logits[0].shape[1] != num_classes:
+            raise ValueError("the network returns %d classes, evaluate_main was told %d" % (logits[0].shape[1], num_classes))
+        pred, _, _ = SF.seg_multiscale(logits, (H, W), full, ignore_label, confusion if full is not None else None, remap=remap,
+                                       want_pred=dump is not None)
+    elif tile_size is None:
         image = torch.as_tensor(np.asarray(image) if not torch.is_tensor(image) else image).float().to(device)
         if cl_model and image.dim() == 4:
             image = image.contiguous(memory_format=torch.channels_last)   # keep the network on its channels-last kernels
