@@ -33,8 +33,11 @@
 // and block is the 8 consecutive k of its row = one ds_read_b128 (lanes 0-31: k 0-7, lanes 32-63: k 8-15), laid out so that a
 // lane half reads 512 contiguous bytes (see kPlaneChunks).  Per K-tile and wave: 12 ds_read_b128 -> 24 MFMAs (768 matrix-pipe
 // cycles); per K-tile and thread 4 global float4 loads, the split (about 5.5 VALU instructions per element) and 12
-// ds_write_b64.  48 KB of LDS per workgroup (+ 16 bytes per input channel for the prologue's table), 136-140 VGPRs, no scratch
-// -> 3 workgroups (3 waves per SIMD) per CU up to K = 256 with the prologue, 2 at K = 512.
+// ds_write_b64.  The loads run TWO K-tiles ahead of the MFMAs and the split one (k_loop in conv_split_dev.hpp: loads of tile
+// kt + 2, then the split of tile kt + 1 behind a counted vmcnt, then the MFMAs of tile kt; round 15, DESIGN.md 9.9: 2-7 % per
+// launch over one tile of look-ahead, bit-identical).  48 KB of LDS per workgroup (+ 16 bytes per input channel for the
+// prologue's table), 154 VGPRs without and 168 with the prologue, no scratch
+// -> 3 workgroups (3 waves per SIMD, limit 168) per CU up to K = 256 with the prologue, 2 at K = 512.
 // The fp32-MFMA core this replaces lives on as variant 0 of tools/gemm_lab_kernels.hip for comparison.
 // Bound: per launch the larger of the HBM traffic (4*M*K + 4*N*K + 4*M*N (+ 4*M*N residual) bytes) and 6 bf16 products
 // (12*M*N*K flops at the bf16-MFMA peak); algorithmic flops stay 2*M*N*K, which is what bench.py's roofline leg reports against
@@ -50,9 +53,11 @@ namespace {
 // The core (split, LDS image, MFMA tile, block epilogue) is conv_split_dev.hpp, shared with conv3x3.hip.
 constexpr int kProMaxK = 512;                             // prologue form: the (4, K) parameter table rides in LDS (<= 8 KB)
 
+constexpr int kDepth1x1 = 2;                             // K-tiles of load look-ahead (k_loop, conv_split_dev.hpp)
+
 // Per K-tile a thread moves two (TM = 64: one) float4 of the A panel (rows t/4 + 64h, k quad t%4) and two of the B panel from
-// global memory to LDS.  The loads are issued at the top of a trip, the split and the LDS stores after the trip's MFMAs (a whole K-tile of
-// matrix-pipe time for them to land), the staging registers are not loop-carried (nothing for the compiler to copy).
+// global memory to LDS.  k_loop issues the loads of tile kt + 2 at the top of trip kt, then runs the prologue, the split and the
+// LDS stores of tile kt + 1 (loaded a whole trip earlier) in front of the trip's MFMAs; two named staging sets, none copied.
 template <int TM>          // TM = rows of the output tile: 128, or 64 for the tiles of a launch's last, partial round (see the kernel)
 struct Staging {
   float4 a[TM / kRPP], b[kRB];
@@ -79,7 +84,7 @@ __device__ __forceinline__ float pro_one(float x, float m, float is, float g, fl
 
 // `srow`: this thread's 8-byte slot inside a plane, in uint2 units (see conv1x1_tile); rows 64 apart are 128 slots apart.
 template <bool PRO, int TM>
-__device__ __forceinline__ void stage_store(const Staging<TM> s, uint4 *stage, int srow, const float *ptab, int K, int kq) {
+__device__ __forceinline__ void stage_store(const Staging<TM> &s, uint4 *stage, int srow, const float *ptab, int K, int kq) {
   constexpr int kRA = TM / kRPP;
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow, *sb = reinterpret_cast<uint2 *>(stage + kOperandChunks) + srow;
   if (PRO) {   // ptab (LDS copy of ppack): mean | invstd | gamma | beta, each K floats; kq = first of this thread's four k
@@ -104,6 +109,22 @@ __device__ __forceinline__ void stage_store(const Staging<TM> s, uint4 *stage, i
 #pragma unroll
   for (int h = 0; h < kRB; ++h) split_store(s.b[h], sb + 2 * kRPP * h);
 }
+
+// What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.
+template <bool PRO, int TM>
+struct Tile1 {
+  typedef Staging<TM> Stg;
+  const float *__restrict__ X, *__restrict__ Wt;
+  const float *ptab;
+  int K, gkq, srow;
+  int64_t wrow0, arow[TM / kRPP];
+  f32x16 (&acc)[TM / 64][2];
+  __device__ __forceinline__ void load(Stg &s, int kt) const { stage_load<PRO, TM>(s, X, Wt, kt * kBK, gkq, arow, wrow0, K); }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int kt) const {
+    stage_store<PRO, TM>(s, stage, srow, ptab, K, kt * kBK + gkq);
+  }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM>(stage, acc); }
+};
 
 // One output tile of TM x 128: K loop through the double-buffered LDS ring, then the epilogue.
 template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT>
@@ -135,19 +156,10 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
     for (int i = gt * 4; i < 4 * K; i += kThreads * 4) *reinterpret_cast<float4 *>(ptab + i) = *reinterpret_cast<const float4 *>(ppack + i);
     __syncthreads();
   }
-  Staging<TM> st;
-  stage_load<PRO, TM>(st, X, Wt, 0, gkq, arow, wrow0, K);
-  stage_store<PRO, TM>(st, lds, srow, ptab, K, gkq);
-  __syncthreads();
-  int stage = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool more = kt + 1 < nk;
-    if (more) stage_load<PRO, TM>(st, X, Wt, (kt + 1) * kBK, gkq, arow, wrow0, K);
-    tile_mma<TM>(lds + stage * kStageChunks, acc);
-    if (more) stage_store<PRO, TM>(st, lds + (stage ^ 1) * kStageChunks, srow, ptab, K, (kt + 1) * kBK + gkq);
-    __syncthreads();
-    stage ^= 1;
-  }
+  Tile1<PRO, TM> tile = {X, Wt, ptab, K, gkq, srow, wrow0, {}, acc};
+#pragma unroll
+  for (int h = 0; h < kRA; ++h) tile.arow[h] = arow[h];
+  k_loop<kDepth1x1>(tile, nk, lds);
   // ---- epilogue: the eval-mode InPlace-ABN formula on the accumulator (+ residual) + activation ----
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;

@@ -35,6 +35,7 @@ namespace {
 
 constexpr int kTileChunks = kOperandChunks;           // one (column tile, K-tile) of packed weights: 768 chunks = 12,288 bytes
 constexpr int kBChunksPerThread = kTileChunks / kThreads;   // 3: thread t copies chunk t of each plane
+constexpr int kDepth3x3 = 2;                          // K-tiles of load look-ahead (k_loop, conv_split_dev.hpp)
 
 template <int TM>
 struct Staging3 {
@@ -52,20 +53,25 @@ __device__ __forceinline__ int64_t tap_shift(int tap, int W, int dil, int Cin) {
   return ((int64_t)(ty - 1) * W + (tx - 1)) * dil * Cin;
 }
 
+// The packed weights: every lane loads its three chunks.
 template <int TM>
-__device__ __forceinline__ void stage_load3(Staging3<TM> &s, const float *__restrict__ X, const uint4 *__restrict__ bsrc,
-                                            const TapCursor &cur, const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP]) {
+__device__ __forceinline__ void stage_load3_b(Staging3<TM> &s, const uint4 *__restrict__ bsrc) {
+#pragma unroll
+  for (int p = 0; p < kBChunksPerThread; ++p) s.b[p] = bsrc[p * kPlaneChunks];
+}
+// The activations: a lane whose tap is outside the image issues no load and stages an exact zero.
+template <int TM>
+__device__ __forceinline__ void stage_load3_a(Staging3<TM> &s, const float *__restrict__ X, const TapCursor &cur,
+                                              const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP]) {
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) {
     s.a[h] = make_float4(0.f, 0.f, 0.f, 0.f);
     if ((mask[h] >> cur.tap) & 1u) s.a[h] = *reinterpret_cast<const float4 *>(X + abase[h] + cur.shift + cur.c0);
   }
-#pragma unroll
-  for (int p = 0; p < kBChunksPerThread; ++p) s.b[p] = bsrc[p * kPlaneChunks];
 }
 
 template <int TM>
-__device__ __forceinline__ void stage_store3(const Staging3<TM> s, uint4 *stage, int srow) {
+__device__ __forceinline__ void stage_store3(const Staging3<TM> &s, uint4 *stage, int srow) {
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) split_store(s.a[h], sa + 2 * kRPP * h);
@@ -73,6 +79,33 @@ __device__ __forceinline__ void stage_store3(const Staging3<TM> s, uint4 *stage,
 #pragma unroll
   for (int p = 0; p < kBChunksPerThread; ++p) sb[p * kPlaneChunks] = s.b[p];
 }
+
+// What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.  k_loop calls load for kt = 0, 1, 2, ... in order, so the
+// cursor is simply stepped behind every one: it runs as far ahead of the MFMAs as the loads do and crosses a tap boundary
+// wherever that falls.  (Behind the last tile it stands at tap 9, which nothing reads.)
+template <int TM>
+struct Tile3 {
+  typedef Staging3<TM> Stg;
+  const float *__restrict__ X;
+  const uint4 *__restrict__ bsrc;
+  int srow, W, dil, Cin;
+  TapCursor cur;
+  int64_t abase[TM / kRPP];
+  unsigned mask[TM / kRPP];
+  f32x16 (&low)[TM / 64][2], (&acc)[TM / 64][2];
+  __device__ __forceinline__ void load(Stg &s, int kt) {
+    stage_load3_a<TM>(s, X, cur, abase, mask);
+    stage_load3_b<TM>(s, bsrc + (int64_t)kt * kTileChunks);
+    cur.c0 += kBK;
+    if (cur.c0 == Cin) {
+      cur.c0 = 0;
+      ++cur.tap;
+      cur.shift = tap_shift(cur.tap, W, dil, Cin);
+    }
+  }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM>(s, stage, srow); }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM>(stage, low, acc); }
+};
 
 // One output tile of TM x 128 pixels x channels.
 template <int TM, int ACT>
@@ -113,28 +146,13 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
     abase[h] = mm * Cin + gkq;
   }
   const uint4 *bsrc = Bp + (int64_t)tn * nk * kTileChunks + gt;
-  TapCursor cur = {0, 0, tap_shift(0, W, dil, Cin)};
-  Staging3<TM> st;
-  stage_load3<TM>(st, X, bsrc, cur, abase, mask);
-  stage_store3<TM>(st, lds, srow);
-  __syncthreads();
-  int stage = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    const bool more = kt + 1 < nk;
-    if (more) {
-      cur.c0 += kBK;
-      if (cur.c0 == Cin) {
-        cur.c0 = 0;
-        ++cur.tap;
-        cur.shift = tap_shift(cur.tap, W, dil, Cin);
-      }
-      stage_load3<TM>(st, X, bsrc + (int64_t)(kt + 1) * kTileChunks, cur, abase, mask);
-    }
-    tile_mma<TM>(lds + stage * kStageChunks, low, acc);
-    if (more) stage_store3<TM>(st, lds + (stage ^ 1) * kStageChunks, srow);
-    __syncthreads();
-    stage ^= 1;
+  Tile3<TM> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
+#pragma unroll
+  for (int h = 0; h < kRA; ++h) {
+    tile.abase[h] = abase[h];
+    tile.mask[h] = mask[h];
   }
+  k_loop<kDepth3x3>(tile, nk, lds);
   // ---- epilogue: (+ conv bias) -> eval-mode InPlace-ABN formula (when there are statistics) -> activation ----
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
@@ -165,12 +183,11 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 }
 
 // TALL: row panels p < p_full are 128 pixels high, the panels behind them 64 (conv1x1.hip, round 6: the half-height mechanism);
-// the two accumulator sets of a 128 x 128 tile take 128 VGPRs and the kernel 206, so that form runs two workgroups per CU -- its
+// the two accumulator sets of a 128 x 128 tile take 128 VGPRs and the kernel 238 (two staging sets: k_loop), so that form runs two workgroups per CU -- its
 // 64-row panels too: they are the same kernel.  !TALL: every panel is 64 pixels high (p_full = 0), 64 accumulator registers,
-// 124-128 VGPRs; three workgroups per CU, which is what 48 KB of LDS per workgroup admits (the registers would admit four).
+// 148 VGPRs; three workgroups per CU, which is what 48 KB of LDS per workgroup and 168 registers admit.
 // The waves-per-SIMD range states those residencies (2, 3) so that the register budget follows from them and not from the
-// launch bound alone; with this compiler the !TALL form needs no more than 128 registers either way
-// (profiles/r12_kernel_resources.md).
+// launch bound alone (profiles/r15_kernel_resources.md).
 template <int ACT, bool TALL>
 __global__ __launch_bounds__(kThreads, TALL ? 2 : kMinWG) __attribute__((amdgpu_waves_per_eu(TALL ? 2 : kMinWG, TALL ? 2 : kMinWG)))
 void conv3x3_split_kernel(

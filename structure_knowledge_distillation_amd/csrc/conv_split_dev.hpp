@@ -105,6 +105,53 @@ __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[TM / 6
 template <int TM>
 __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 64][2]) { tile_mma<TM>(stage, acc, acc); }
 
+// The K loop of one output tile through the two LDS stages, shared by both kernels.  `Tile` supplies
+//   Stg                       the staging registers of one K-tile (every member written by load)
+//   load(Stg &, kt)           issue the global loads of tile kt (called for kt = 0, 1, 2, ... in order, each once)
+//   store(const Stg &, s, kt) prologue (if any) + split of tile kt's staging set, written to LDS stage s
+//   mma(s)                    tile_mma on LDS stage s
+// DEPTH = how many K-tiles the global loads run ahead of the MFMAs.
+//   2: trip kt issues the loads of tile kt + 2, then splits and stores tile kt + 1 -- loaded during trip kt - 1, so it has had a
+//      whole trip of every co-resident wave to land and the wait in front of the split is a counted vmcnt that leaves the loads
+//      just issued in flight -- into the stage that every wave left at the barrier ending trip kt - 1, then runs the MFMAs of tile kt.
+//   1: the loop before round 15: trip kt loads tile kt + 1, runs the MFMAs of tile kt, then splits and stores tile kt + 1.
+// Either way: one barrier per trip, tile order and MFMA order as written, no load for a tile index >= nk.  The loop is unrolled by
+// two trips so that the two staging sets and the two stages are named, not indexed: nothing is copied at the back edge.  Its
+// steady state (STEADY: the caller knows kt + 2 < nk) has no branch, so the compiler's count of the loads in flight is exact
+// there (a guard inside the loop made it wait for the loads it had just issued); the last one to three trips carry the guards.
+template <int DEPTH, bool STEADY, class Tile>
+__device__ __forceinline__ void k_trip(Tile &t, typename Tile::Stg &fill, typename Tile::Stg &next, const uint4 *cur, uint4 *nxt,
+                                       int kt, int nk) {
+  static_assert(DEPTH == 1 || DEPTH == 2, "load look-ahead of one or two K-tiles");
+  if (DEPTH == 2) {
+    if (STEADY || kt + 2 < nk) t.load(fill, kt + 2);       // `fill` held tile kt: stored one trip ago
+    if (STEADY || kt + 1 < nk) t.store(next, nxt, kt + 1);
+    t.mma(cur);
+  } else {
+    if (STEADY || kt + 1 < nk) t.load(next, kt + 1);
+    t.mma(cur);
+    if (STEADY || kt + 1 < nk) t.store(next, nxt, kt + 1);
+  }
+  __syncthreads();
+}
+template <int DEPTH, class Tile>
+__device__ __forceinline__ void k_loop(Tile &t, int nk, uint4 *lds) {
+  typename Tile::Stg s0, s1;                     // tiles of even / odd index
+  uint4 *const l0 = lds, *const l1 = lds + kStageChunks;
+  t.load(s0, 0);
+  if (DEPTH == 2 && nk > 1) t.load(s1, 1);
+  t.store(s0, l0, 0);
+  __syncthreads();
+  int kt = 0;
+  for (; kt + 3 < nk; kt += 2) {
+    k_trip<DEPTH, true>(t, s0, s1, l0, l1, kt, nk);
+    k_trip<DEPTH, true>(t, s1, s0, l1, l0, kt + 1, nk);
+  }
+  k_trip<DEPTH, false>(t, s0, s1, l0, l1, kt, nk);                        // one to three trips left, kt even
+  if (kt + 1 < nk) k_trip<DEPTH, false>(t, s1, s0, l1, l0, kt + 1, nk);
+  if (kt + 2 < nk) k_trip<DEPTH, false>(t, s0, s1, l0, l1, kt + 2, nk);
+}
+
 // Epilogue of one 32 x 32 accumulator block: rows row0 + frag_row(q), column col.  FULL: every row of the tile exists (all
 // but the last row tile) -- no per-element branches, and the sixteen residual loads are issued together before the first
 // use (round 2 interleaved load -> wait -> store per element behind a branch: 64 serialised HBM round trips per lane).
