@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libskd_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd.h"))
 EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval.h"))
 MS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval_ms.h"))
+OHEM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_ohem.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -157,6 +158,15 @@ MS_SIGNATURES = {
     "skd_seg_multiscale": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
+# Entry points declared in include/skd_ohem.h (csrc/ce_ohem.hip): the OHEM criterion, extension entries in a table of their own
+# for the reasons of MS_SIGNATURES (tests/test_ohem_cpu.py checks header <-> table <-> exported symbols, tests/test_ohem_gpu.py
+# holds their guard-band cases).
+OHEM_SIGNATURES = {
+    "skd_ce_ohem_workspace_floats": (_L, [_I, _I, _I, _I, _I, _I, _I]),
+    "skd_ohem_threshold": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
+    "skd_ce_ohem_dsn_forward": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -186,7 +196,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -5,6 +5,7 @@ hand-written gfx950 kernels behind the C ABI of include/skd.h (no eager fallback
 raise, see _lib.require_device):
 
     cross_entropy_dsn(m, d, y)   utils/criterion.py:179-188   csrc/ce_dsn.hip
+    ce_ohem_dsn(m, d, y, ...)    utils/criterion.py:11-90, 200-209   csrc/ce_ohem.hip  (include/skd_ohem.h)
     ppm_pool / ppm_concat        networks/pspnet_combine.py:102-111   csrc/ppm.hip
     seg_confusion(logits, y)     networks/evaluate.py:106-113,186-198 csrc/evaluate.hip  (no autograd)
     pixel_wise_loss(S, T)        utils/criterion.py:219-226   csrc/pixelwise.hip
@@ -103,6 +104,106 @@ def cross_entropy_dsn(logits_main, logits_dsn, target, ignore_index=255, aux_wei
     target's size, CE = mean over non-ignored pixels (utils/criterion.py:179-188) -- one fused kernel chain
     that never materialises a (B, C, H, W) tensor.  ``logits_dsn`` may be None (single CE)."""
     return _CrossEntropyDSN.apply(logits_main, logits_dsn, target, ignore_index, aux_weight)
+
+
+def _need_ohem_entry(name):
+    if not _lib.has_entry(name):
+        raise NotImplementedError("the active back-end does not provide %s (include/skd_ohem.h)" % name)
+
+
+def _ohem_inputs(logits_main, logits_dsn, target, factor, what):
+    _lib.require_device(logits_main, logits_dsn, target)
+    lm = _f32c(logits_main, what)
+    ld = _f32c(logits_dsn, what) if logits_dsn is not None else None
+    if target.dtype != torch.int64:
+        raise TypeError("%s: int64 target expected (got %s)" % (what, target.dtype))
+    tg = target if target.is_contiguous() else target.contiguous()
+    if lm.dim() != 4 or not 1 <= lm.shape[1] <= 64:
+        raise ValueError("%s: logits (B, C, h, w) with 1 <= C <= 64 expected (got %s)" % (what, tuple(lm.shape)))
+    if ld is not None and ld.shape != lm.shape:
+        raise ValueError("main and dsn logits differ in shape")
+    if tg.dim() != 3 or tg.shape[0] != lm.shape[0]:
+        raise ValueError("target must be (B, H, W)")
+    factor = int(factor)
+    if factor < 1:
+        raise ValueError("%s: factor >= 1 expected (got %d)" % (what, factor))
+    for n in tg.shape[1:]:
+        nd = zoom_size(n, 1.0 / factor)
+        if nd < 1 or (nd == 1 and n > 1):
+            raise ValueError("%s: an axis of %d down-samples to %d at factor %d: scipy's zoom step is undefined there"
+                             % (what, n, nd, factor))
+    return lm, ld, tg, factor
+
+
+def _ohem_threshold(lib, lm, tg, ignore_index, thresh, min_kept, factor, ws, pred_ds=None):
+    """Launches skd_ohem_threshold; returns the (threshold fp32 [], num_valid int32 []) DEVICE tensors."""
+    b, c, h, w = lm.shape
+    threshold = lm.new_empty(())
+    num_valid = torch.empty((), dtype=torch.int32, device=lm.device)
+    _lib.check(lib.skd_ohem_threshold(b, c, h, w, tg.shape[1], tg.shape[2], lm.data_ptr(), tg.data_ptr(), int(ignore_index),
+                                      float(thresh), int(min_kept), factor, threshold.data_ptr(), num_valid.data_ptr(),
+                                      _lib.ptr(pred_ds), ws.data_ptr(), _lib.stream_of(lm)), "skd_ohem_threshold")
+    return threshold, num_valid
+
+
+class _CrossEntropyOhemDSN(Function):
+    @staticmethod
+    def forward(ctx, logits_main, logits_dsn, target, ignore_index, thresh, min_kept, factor, aux_weight):
+        for name in ("skd_ce_ohem_workspace_floats", "skd_ohem_threshold", "skd_ce_ohem_dsn_forward"):
+            _need_ohem_entry(name)
+        lm, ld, tg, factor = _ohem_inputs(logits_main, logits_dsn, target, factor, "ce_ohem_dsn")
+        if int(min_kept) < 0:
+            raise ValueError("ce_ohem_dsn: min_kept >= 0 expected (got %d)" % int(min_kept))
+        b, c, h, w = lm.shape
+        H, W = tg.shape[1], tg.shape[2]
+        lib, st = _lib.get(), _lib.stream_of(lm)
+        need_m = ctx.needs_input_grad[0]
+        need_d = ld is not None and ctx.needs_input_grad[1]
+        loss, n_kept = lm.new_empty(()), lm.new_empty(())
+        gm = torch.empty_like(lm) if need_m else None
+        gd = torch.empty_like(ld) if need_d else None
+        ws = lm.new_empty((max(8, lib.skd_ce_ohem_workspace_floats(b, c, h, w, H, W, factor)),))
+        # two entry calls on one stream; the threshold stays in device memory between them
+        threshold, _ = _ohem_threshold(lib, lm, tg, ignore_index, thresh, min_kept, factor, ws)
+        _lib.check(lib.skd_ce_ohem_dsn_forward(b, c, h, w, H, W, lm.data_ptr(), _lib.ptr(ld), tg.data_ptr(), int(ignore_index),
+                                               float(aux_weight), threshold.data_ptr(), loss.data_ptr(), n_kept.data_ptr(),
+                                               None, _lib.ptr(gm), _lib.ptr(gd), ws.data_ptr(), st), "skd_ce_ohem_dsn_forward")
+        ctx.save_for_backward(gm, gd)
+        ctx.mark_non_differentiable(threshold, n_kept)
+        return loss, threshold, n_kept
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_threshold, _g_kept):
+        gm, gd = ctx.saved_tensors
+        return (gm * g if gm is not None else None), (gd * g if gd is not None else None), None, None, None, None, None, None
+
+
+def ce_ohem_dsn(logits_main, logits_dsn, target, ignore_index=255, thresh=0.7, min_kept=100000, factor=8, aux_weight=0.4):
+    """CriterionOhemDSN (utils/criterion.py:190-209): OHEM cross-entropy on the up-sampled main logits + ``aux_weight`` * plain
+    cross-entropy on the up-sampled dsn logits (``logits_dsn`` None: the single OhemCrossEntropy2d term).  A main-head pixel
+    counts iff it is valid and the softmax probability of its label is <= the threshold that OhemCrossEntropy2d.find_threshold
+    derives at 1 / ``factor`` resolution (the ``min_kept // factor**2``-th smallest such probability, at least ``thresh``; 1.0
+    when fewer valid pixels than that exist).  Everything runs on the device (csrc/ce_ohem.hip): nothing is copied to the
+    host and nothing of size (B, C, H, W) is written.  Returns (loss, threshold, n_kept): 0-dim tensors, the last two for
+    logging (no gradient)."""
+    return _CrossEntropyOhemDSN.apply(logits_main, logits_dsn, target, ignore_index, thresh, min_kept, factor, aux_weight)
+
+
+def ohem_threshold(logits_main, target, ignore_index=255, thresh=0.7, min_kept=100000, factor=8, want_keys=False):
+    """The OHEM threshold alone (OhemCrossEntropy2d.find_threshold on the up-sampled logits' softmax), without autograd:
+    (threshold fp32 [], num_valid int32 []) device tensors, and with ``want_keys`` the (B, Hd, Wd) down-sampled label
+    probabilities the selection ran on (-1 where the down-sampled label is ignored)."""
+    for name in ("skd_ce_ohem_workspace_floats", "skd_ohem_threshold"):
+        _need_ohem_entry(name)
+    lm, _, tg, factor = _ohem_inputs(logits_main.detach(), None, target, factor, "ohem_threshold")
+    b, c, h, w = lm.shape
+    H, W = tg.shape[1], tg.shape[2]
+    lib = _lib.get()
+    ws = lm.new_empty((max(8, lib.skd_ce_ohem_workspace_floats(b, c, h, w, H, W, factor)),))
+    keys = lm.new_empty((b, zoom_size(H, 1.0 / factor), zoom_size(W, 1.0 / factor))) if want_keys else None
+    threshold, num_valid = _ohem_threshold(lib, lm, tg, ignore_index, thresh, min_kept, factor, ws, keys)
+    return (threshold, num_valid, keys) if want_keys else (threshold, num_valid)
 
 
 def _is_cl(t):

@@ -28,7 +28,7 @@ import torch.optim as optim
 
 from .. import _lib
 from ..utils import parallel as parallel_old
-from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN,
+from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
 from ..utils.utils import print_model_parm_nums, to_tuple_str  # noqa: F401
 from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet
@@ -213,7 +213,13 @@ class NetModel():
 
         self.best_mean_IU = args.best_mean_IU
 
-        self.criterion = self.DataParallelCriterionProcess(CriterionDSN())
+        # args.ohem: online hard-example mining on the main head (utils/criterion.py:190-209 of the reference, which its
+        # kd_model.py imports and never constructs); off by default, and then this is the step as it always was
+        if getattr(args, "ohem", False):
+            self.criterion = self.DataParallelCriterionProcess(
+                CriterionOhemDSN(thresh=args.ohem_thresh, min_kept=args.ohem_keep))
+        else:
+            self.criterion = self.DataParallelCriterionProcess(CriterionDSN())
         self.criterion_pixel_wise = self.DataParallelCriterionProcess(CriterionPixelWise())
         self.criterion_pair_wise_for_interfeat = self.DataParallelCriterionProcess(
             CriterionPairWiseforWholeFeatAfterPool(scale=args.pool_scale, feat_ind=-5))
@@ -800,7 +806,8 @@ def default_args(**overrides):
         adv_conv_dim=64, preprocess_GAN_mode=1, parallel="True", gpu="0", gpu_num=1, best_mean_IU=0.0,
         T_ckpt_path=None, is_student_load_imgnet=False, student_pretrain_model_imgnet=None,
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
-        snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"))
+        snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
+        ohem=False, ohem_thresh=0.7, ohem_keep=100000)
     for k, v in overrides.items():
         setattr(a, k, v)
     return a

@@ -2,19 +2,84 @@
 arguments and list-indexing convention (``preds[0]`` logits, ``preds[1]`` DSN logits, ``preds[-5]``
 post-PSP feature), each returning a 0-dim tensor that participates in autograd.
 
+    OhemCrossEntropy2d                        :11-90     fused HIP kernels (csrc/ce_ohem.hip): threshold + mined CE on the device
     CriterionDSN                              :168-188   fused HIP kernels (csrc/ce_dsn.hip): upsample + CE, main + 0.4*aux
+    CriterionOhemDSN                          :190-209   fused HIP kernels (csrc/ce_ohem.hip): OHEM main head + 0.4*plain aux
     CriterionPixelWise                        :211-226   fused HIP kernel (csrc/pixelwise.hip)
     CriterionPairWiseforWholeFeatAfterPool    :228-245   fused HIP kernels (csrc/pairwise.hip)
     CriterionAdvForG / CriterionAdv           :122-166   wgan-gp / hinge on D's (B,1,1,1) output
     CriterionAdditionalGP                     :92-120    WGAN-GP gradient penalty (double backward in D)
-The OHEM variants (:11-90, :190-209) are never constructed on this path (kd_model.py:79) -- out of scope.
+The reference's kd_model.py imports CriterionOhemDSN and never constructs it (:18, :79); here NetModel builds it when
+``args.ohem`` is set.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import functional as SF
+from .. import _lib, functional as SF
 from .utils import sim_dis_compute
+
+
+class OhemCrossEntropy2d(nn.Module):
+    """Online hard-example mining cross-entropy on full-resolution logits (criterion.py:11-90): the mean of -log p over the
+    valid pixels whose label probability is <= the threshold of ``find_threshold``.  The reference finds that threshold on
+    the host (softmax copied out, scipy zoom, np.partition, a new target copied back); here it never leaves the device and
+    ``forward`` does not synchronise.  Nothing is printed (the reference's ``print('Labels: ...')`` is logging): the last
+    call's threshold and kept count stay on the module as 0-dim device tensors, ``last_threshold`` / ``last_kept``."""
+
+    def __init__(self, ignore_label=255, thresh=0.7, min_kept=100000, factor=8):
+        super().__init__()
+        self.ignore_label = ignore_label
+        self.thresh = float(thresh)
+        self.min_kept = int(min_kept)
+        self.factor = factor
+        self.last_threshold = None
+        self.last_kept = None
+
+    def find_threshold(self, predict, target):
+        """API parity with criterion.py:20-48.  ``predict`` (B, C, h, w), tensor or numpy array, holds either the softmax
+        PROBABILITIES, as the reference's callers pass them, or LOGITS (up-sampled to the target's size when smaller);
+        ``target`` (B, H, W).  Probabilities are recognised by what they are -- no negative element and every pixel's
+        channels summing to 1 within 1e-3 -- and handed to the kernels as their logarithms, whose softmax they are.
+        Returns a Python float, so this call (unlike ``forward``) waits for the device."""
+        lg, tg = torch.as_tensor(predict, dtype=torch.float32), torch.as_tensor(target).long()
+        if not lg.is_cuda and not _lib.test_backend_active():      # arrays, as the reference passes them: onto the device
+            lg = lg.to(tg.device if tg.is_cuda else "cuda")
+        tg = tg.to(lg.device)
+        if lg.dim() == 4 and bool((lg >= 0).all()) and bool(((lg.sum(1) - 1.0).abs() <= 1e-3).all()):
+            lg = lg.clamp_min(1e-30).log()                         # (a zero probability: exp(-69), not 0 * -inf in the interpolation)
+        threshold, _ = SF.ohem_threshold(lg, tg, self.ignore_label, self.thresh, self.min_kept, self.factor)
+        return float(threshold)
+
+    def forward(self, predict, target, weight=None):
+        """predict (n, c, h, w) logits, target (n, h, w); ``weight`` must be None (the reference ignores it)."""
+        assert not target.requires_grad
+        if weight is not None:
+            raise NotImplementedError("OhemCrossEntropy2d: class weights are not supported (the reference ignores them)")
+        loss, self.last_threshold, self.last_kept = SF.ce_ohem_dsn(predict, None, target, self.ignore_label, self.thresh,
+                                                                   self.min_kept, self.factor, 0.0)
+        return loss
+
+
+class CriterionOhemDSN(nn.Module):
+    """CriterionDSN with OHEM on the main head (criterion.py:190-209): OhemCrossEntropy2d(up(preds[0])) + 0.4 *
+    CE(up(preds[1])), both up-samplings, the threshold search and both losses fused on the device (csrc/ce_ohem.hip).
+    There is no ``criterion2`` attribute: the reference's second ``CrossEntropyLoss`` is part of the fused call, not a module
+    of its own.  ``use_weight`` is accepted and unused, as in the reference."""
+
+    def __init__(self, ignore_index=255, thresh=0.7, min_kept=100000, use_weight=True, reduce=True):
+        super().__init__()
+        if not reduce:
+            raise NotImplementedError("CriterionOhemDSN(reduce=False): the fused criterion has no per-pixel output (the "
+                                      "reference's criterion2 would return a loss map there)")
+        self.ignore_index = ignore_index
+        self.criterion1 = OhemCrossEntropy2d(ignore_index, thresh, min_kept)
+
+    def forward(self, preds, target):
+        c1 = self.criterion1
+        loss, c1.last_threshold, c1.last_kept = SF.ce_ohem_dsn(preds[0], preds[1], target, self.ignore_index, c1.thresh,
+                                                               c1.min_kept, c1.factor, 0.4)
+        return loss
 
 
 class CriterionDSN(nn.Module):
