@@ -15,6 +15,7 @@ HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd.h"))
 EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval.h"))
 MS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval_ms.h"))
 OHEM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_ohem.h"))
+INFER_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_infer.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -167,6 +168,14 @@ OHEM_SIGNATURES = {
     "skd_ce_ohem_dsn_forward": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# Entry points declared in include/skd_infer.h (csrc/conv3x3.hip): the student's fused inference path, extension entries in a
+# table of their own like the two above (tests/test_student_infer_cpu.py checks header <-> table <-> exported symbols,
+# tests/test_student_infer_gpu.py holds the guard-band case).  A back-end without them leaves the BasicBlocks on the op sequence
+# they ran before: nothing raises.
+INFER_SIGNATURES = {
+    "skd_conv3x3_split_res_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -196,7 +205,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -29,6 +29,7 @@
 // budget); the other runs 64 x 128 tiles throughout at three workgroups per CU and takes the problems that do not fill the
 // chip's two-per-CU slots once.  48 KB of LDS either way.
 #include "conv_split_dev.hpp"
+#include "skd_infer.h"
 
 namespace skd {
 namespace {
@@ -107,9 +108,11 @@ struct Tile3 {
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM>(stage, low, acc); }
 };
 
-// One output tile of TM x 128 pixels x channels.
-template <int TM, int ACT>
+// One output tile of TM x 128 pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
+// in front of the activation (store_block): the second convolution of a BasicBlock.
+template <int TM, int ACT, bool HAS_RES>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
+                                             const float *__restrict__ R,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
                                              const float *__restrict__ var, const float *__restrict__ weight,
                                              const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W,
@@ -175,9 +178,9 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
       }
       const int64_t row0 = m0 + wi + bi * 32;
       if (full)
-        store_block<ACT, false, true, false>(acc[bi][bj], nullptr, Y, row0, col, M, N, mu, is, ga, be, slope);
+        store_block<ACT, HAS_RES, true, false>(acc[bi][bj], R, Y, row0, col, M, N, mu, is, ga, be, slope);
       else
-        store_block<ACT, false, false, false>(acc[bi][bj], nullptr, Y, row0, col, M, N, mu, is, ga, be, slope);
+        store_block<ACT, HAS_RES, false, false>(acc[bi][bj], R, Y, row0, col, M, N, mu, is, ga, be, slope);
     }
   }
 }
@@ -188,13 +191,13 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 // 148 VGPRs; three workgroups per CU, which is what 48 KB of LDS per workgroup and 168 registers admit.
 // The waves-per-SIMD range states those residencies (2, 3) so that the register budget follows from them and not from the
 // launch bound alone (profiles/r15_kernel_resources.md).
-template <int ACT, bool TALL>
+template <int ACT, bool TALL, bool HAS_RES>
 __global__ __launch_bounds__(kThreads, TALL ? 2 : kMinWG) __attribute__((amdgpu_waves_per_eu(TALL ? 2 : kMinWG, TALL ? 2 : kMinWG)))
 void conv3x3_split_kernel(
     const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y, const float *__restrict__ cbias,
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
     const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil, int tiles_n,
-    int p_full) {
+    int p_full, const float *__restrict__ R) {
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -202,11 +205,11 @@ void conv3x3_split_kernel(
   if (TALL && tm < p_full) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, ACT>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, ACT>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -233,15 +236,15 @@ __global__ void conv3x3_pack_kernel(const float *__restrict__ Wt, int64_t sn, in
   for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * kPlaneChunks + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int ACT, bool TALL>
-static int launch3(const float *X, const uint4 *Bp, float *Y, const float *cbias, const float *mean, const float *var,
+template <int ACT, bool TALL, bool HAS_RES>
+static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                    int geometry, hipStream_t st) {
   static PerDeviceFlag ready;          // per instantiation AND per device
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<ACT, TALL>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<ACT, TALL, HAS_RES>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvLds) != hipSuccess) return 0;
     *rdy = true;
   }
@@ -257,8 +260,8 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *cbias
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<ACT, TALL><<<dim3((unsigned)grid), dim3(kThreads), kConvLds, st>>>(
-      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full);
+  conv3x3_split_kernel<ACT, TALL, HAS_RES><<<dim3((unsigned)grid), dim3(kThreads), kConvLds, st>>>(
+      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R);
   return ok();
 }
 
@@ -267,14 +270,14 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *cbias
 // profiles/r12_conv3x3_isolated.md (tools/conv3x3_bench.py) has every geometry per shape: on the four routed shapes 3 is 6-14 %
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
-template <int ACT>
-static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *cbias, const float *mean, const float *var,
+template <int ACT, bool HAS_RES>
+static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st) {
   if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
   if (geometry == 1 || geometry == 3)
-    return launch3<ACT, true>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
-  return launch3<ACT, false>(X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+    return launch3<ACT, true, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+  return launch3<ACT, false, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
 }
 
 }  // namespace
@@ -305,9 +308,11 @@ int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t st
   return ok();
 }
 
-int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
-                           const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
-                           float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+// The shared body of the two entries; residual == nullptr takes the instantiations without the residual read.
+static int conv3x3_split_run(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                             const float *residual, const float *conv_bias, const float *mean, const float *var,
+                             const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
+                             skd_stream_t stream) {
   if (!skd_conv3x3_split_supported(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
   if (!x || !wpack || !out || (mean == nullptr) != (var == nullptr) || geometry < 0 || geometry > 3) return 0;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack)) & 15) return 0;
@@ -315,12 +320,44 @@ int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation,
   const int64_t M = (int64_t)B * H * W;
   hipStream_t st = as_stream(stream);
   const uint4 *bp = static_cast<const uint4 *>(wpack);
+#define SKD_CONV3X3_ARGS x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st
+  if (residual != nullptr) {
+    switch (activation) {
+      case SKD_ACT_NONE: return launch3g<SKD_ACT_NONE, true>(SKD_CONV3X3_ARGS);
+      case SKD_ACT_RELU: return launch3g<SKD_ACT_RELU, true>(SKD_CONV3X3_ARGS);
+      case SKD_ACT_LEAKY_RELU: return launch3g<SKD_ACT_LEAKY_RELU, true>(SKD_CONV3X3_ARGS);
+      default: return 0;
+    }
+  }
   switch (activation) {
-    case SKD_ACT_NONE: return launch3g<SKD_ACT_NONE>(x, bp, out, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);
-    case SKD_ACT_RELU: return launch3g<SKD_ACT_RELU>(x, bp, out, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);
-    case SKD_ACT_LEAKY_RELU: return launch3g<SKD_ACT_LEAKY_RELU>(x, bp, out, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);
+    case SKD_ACT_NONE: return launch3g<SKD_ACT_NONE, false>(SKD_CONV3X3_ARGS);
+    case SKD_ACT_RELU: return launch3g<SKD_ACT_RELU, false>(SKD_CONV3X3_ARGS);
+    case SKD_ACT_LEAKY_RELU: return launch3g<SKD_ACT_LEAKY_RELU, false>(SKD_CONV3X3_ARGS);
     default: return 0;
   }
+#undef SKD_CONV3X3_ARGS
+}
+
+int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                           const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                           float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+  return conv3x3_split_run(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation,
+                           slope, geometry, stream);
+}
+
+// out = act(ABN_eval(conv3x3(x) + conv_bias) + residual) (include/skd_infer.h).  The kernel reads the residual through a
+// __restrict__ pointer at the offsets it writes, so a residual that overlaps the output is refused, not defined.
+int skd_conv3x3_split_res_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                               const float *residual, const float *conv_bias, const float *mean, const float *var,
+                               const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
+                               skd_stream_t stream) {
+  if (residual != nullptr && out != nullptr && B >= 1 && H >= 1 && W >= 1 && Cout >= 1) {
+    const uintptr_t bytes = (uintptr_t)B * H * W * Cout * sizeof(float);
+    const uintptr_t r = reinterpret_cast<uintptr_t>(residual), o = reinterpret_cast<uintptr_t>(out);
+    if (r < o + bytes && o < r + bytes) return 0;
+  }
+  return conv3x3_split_run(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation,
+                           slope, geometry, stream);
 }
 
 }  // extern "C"

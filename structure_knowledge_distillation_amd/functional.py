@@ -759,6 +759,62 @@ def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activ
     return out
 
 
+def conv3x3_infer_supported(x, conv, residual=False):
+    """True when a BasicBlock's inference form (networks.pspnet_combine.fuse_for_inference) may hand ``conv(x)`` to the split
+    core: the conditions of conv3x3_split_supported, asked of a back-end that has the entry the call needs --
+    ``skd_conv3x3_split_res_nhwc`` (include/skd_infer.h) with ``residual``, ``skd_conv3x3_split_nhwc`` without.  A back-end
+    without it (the tests' C double) answers False and the block runs the sequence it ran before.  Host tensors pass only
+    under a test double, as in conv1x1_abn_supported."""
+    entry = "skd_conv3x3_split_res_nhwc" if residual else "skd_conv3x3_split_nhwc"
+    if torch.is_grad_enabled() or not (_lib.has_entry(entry) and _lib.has_entry("skd_conv3x3_split_supported")):
+        return False
+    if not (isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
+        return False
+    s, p, d = _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation)
+    if s[0] != s[1] or p[0] != p[1] or d[0] != d[1]:
+        return False
+    wt = conv.weight
+    if not ((x.is_cuda or _lib.test_backend_active()) and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return False
+    if not (wt.dtype == torch.float32 and wt.device == x.device and tuple(wt.shape[2:]) == (3, 3)
+            and x.shape[1] == wt.shape[1] * conv.groups):
+        return False
+    return bool(_lib.get().skd_conv3x3_split_supported(int(wt.shape[1]), int(wt.shape[0]), s[0], p[0], d[0], conv.groups))
+
+
+def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, conv_bias=None, geometry=0):
+    """act(bn_running(conv3x3(x) + conv_bias) + residual) in one launch of csrc/conv3x3.hip (include/skd_infer.h; inference
+    only): conv3x3_split_eval with the residual added in the epilogue, behind the normalisation and in front of the activation
+    -- ``relu(bn2(conv2(.)) + residual)`` of a BasicBlock.  ``pack = conv3x3_pack_weights(...)`` (the same cache), ``bn`` an
+    eval-mode InPlace-ABN module or None, ``residual`` (B, cout, H, W) fp32, read in channels-last memory (copied when it is
+    not) and never written; ``residual=None`` is conv3x3_split_eval bit for bit.  The numerics of the convolution are those of
+    conv3x3_split_eval; the residual add is one more fp32 rounding."""
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError("conv3x3_split_res_eval is inference-only")
+    mean = var = gamma = beta = None
+    eps, slope = 0.0, 0.01
+    if bn is not None:
+        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
+    _lib.require_device(x, pack, residual, conv_bias, mean, var, gamma, beta)
+    if not _lib.has_entry("skd_conv3x3_split_res_nhwc"):
+        raise NotImplementedError("this back-end has no skd_conv3x3_split_res_nhwc (include/skd_infer.h)")
+    act = {"none": 0, "leaky_relu": 1, "relu": 3}[activation]
+    b, cin, h, w = x.shape
+    if pack.numel() != _lib.get().skd_conv3x3_split_pack_bytes(cin, cout):
+        raise ValueError("conv3x3_split_res_eval: the pack is not that of a (%d, %d, 3, 3) weight" % (cout, cin))
+    if residual is not None:
+        if tuple(residual.shape) != (b, cout, h, w) or residual.dtype != torch.float32:
+            raise ValueError("residual %s %s != output (%d, %d, %d, %d) fp32" % (tuple(residual.shape), residual.dtype, b, cout, h, w))
+        residual = _cl(residual)
+    out = _new_cl(x, b, cout, h, w)
+    _lib.check(_lib.get().skd_conv3x3_split_res_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(),
+                                                     out.data_ptr(), _lib.ptr(residual), _lib.ptr(conv_bias), _lib.ptr(mean),
+                                                     _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, act, slope,
+                                                     int(geometry), _lib.stream_of(x)), "skd_conv3x3_split_res_nhwc")
+    return out
+
+
 def seg_confusion(logits, target=None, ignore_index=255, confusion=None, want_pred=True):
     """Evaluation tail (networks/evaluate.py:106-113, 186-198): bilinear (align_corners) upsample of ``logits``
     (B, C, h, w) to the size of ``target`` (B, H, W) [or of ``want_pred`` = (H, W) when no target], argmax over the

@@ -28,6 +28,11 @@ float64 sum in scale order, mean, argmax, remap, confusion.  ``predict_multiscal
 reference's arrays for callers that want them.  ``scales`` None or ``[1.0]`` without ``flip`` is the whole-image path above,
 unchanged.
 
+The student's fused inference form (``networks.fuse_for_inference(model)``, or ``default_args(fused_eval=True)`` for NetModel's
+student): ``evaluate_main``, ``predict_whole``, ``predict_sliding`` and ``predict_multiscale`` take the model as it is given --
+flagged or not -- and need no argument for it; a flagged model's eval-mode forwards run its BasicBlocks on the split-core 3x3
+convolution (networks/pspnet_combine.py), everything behind the forward is the same code.
+
 Not provided: the cv2-based dataset readers; ``recurrence`` and flipping in sliding mode are accepted and ignored, as in the
 reference.  A back-end without ``skd_seg_sliding`` / ``skd_zoom_linear`` / ``skd_seg_multiscale`` (the plain-C double of
 oracle/) cannot run the sliding / multi-scale modes: NotImplementedError names the entry point.

@@ -31,7 +31,7 @@ from ..utils import parallel as parallel_old
 from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
 from ..utils.utils import print_model_parm_nums, to_tuple_str  # noqa: F401
-from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet
+from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference
 from .sagan_models import Discriminator
 
 
@@ -172,6 +172,10 @@ class NetModel():
         if self.student_nhwc:
             os.environ["PYTORCH_MIOPEN_SUGGEST_NHWC"] = "1"
             student.to(memory_format=torch.channels_last)
+        # args.fused_eval: the student's eval-mode / no-grad forwards (validation between epochs, evaluate_main) take the fused
+        # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
+        if getattr(args, "fused_eval", False):
+            fuse_for_inference(student)
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -807,7 +811,7 @@ def default_args(**overrides):
         T_ckpt_path=None, is_student_load_imgnet=False, student_pretrain_model_imgnet=None,
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
-        ohem=False, ohem_thresh=0.7, ohem_keep=100000)
+        ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False)
     for k, v in overrides.items():
         setattr(a, k, v)
     return a

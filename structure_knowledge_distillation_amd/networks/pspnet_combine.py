@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import functional as SF
+from .. import _lib, functional as SF
 from ..libs import InPlaceABN, InPlaceABNSync  # noqa: F401  (re-exported like pspnet_combine.py:11)
 
 affine_par = True
@@ -51,6 +51,18 @@ CONV3X3_SPLIT_MIN_CIN = 256   # the 64- / 128-channel 3x3s (stem, layer1, layer2
 SPLIT_REDUCE = True   # the reduce / stride-1 down-sample 1x1 GEMMs on csrc/conv1x1.hip's split core instead of the library GEMM wherever
                       # profiles/r11_stage2_isolated.md shows the kernel ahead (every shape but 512 -> 128); profiles/r12_step_ab.md:
                       # 55.40-55.67 ms per step off, 54.61-55.07 on, five interleaved runs each, the sets do not overlap
+
+
+# The student's inference form (fuse_for_inference, below): a flagged BasicBlock hands a 3x3 convolution to the split core when the
+# kernel takes it (stride 1, Cin a multiple of 16, Cout of 128) and it has at least ``min_cin`` input channels.
+# FUSED_EVAL_MIN_CIN is the default: 128, below the frozen teacher's CONV3X3_SPLIT_MIN_CIN, because at the student's evaluation
+# sizes (129 x 257 maps, batch 1, shapes the shipped MIOpen find-db was not tuned for) layer2's 128 -> 128 launch is 3.2 x ahead
+# of convolution + ABN pass, against a run-to-run spread of 1.1 - 2.6 % (profiles/r17_student_infer.md, which has every shape).  That
+# routes layer2's three stride-1 convolutions and all of layer3 / layer4; layer1 (Cout = 64) and layer2.0.conv1 (stride 2) are
+# not the kernel's.  A routed shape that measures behind is listed in INFER_ROUTING_EXCLUDED as (Cin, Cout, dilation) and keeps
+# conv -> forward_relu: none does.
+FUSED_EVAL_MIN_CIN = 128
+INFER_ROUTING_EXCLUDED = frozenset()
 
 
 def _fused_tail(x):
@@ -135,7 +147,48 @@ class BasicBlock(nn.Module):
         self.relu_inplace = nn.ReLU(inplace=True)
         self.downsample = downsample
 
+    def _infer_form(self, x):
+        """Whether this call takes the inference form: the block is flagged (fuse_for_inference), frozen for this call (eval mode,
+        no grad), the input is an fp32 channels-last map and both normalisations are plain eval-mode BatchNorms."""
+        return (getattr(self, "_skd_infer_min_cin", None) is not None and not self.training and not torch.is_grad_enabled()
+                and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+                and all(getattr(bn, "activation", None) == "none" and getattr(bn, "running_mean", None) is not None
+                        and getattr(bn, "running_var", None) is not None for bn in (self.bn1, self.bn2)))
+
+    def _routed(self, x, conv, residual):
+        """Whether the flagged block hands ``conv(x)`` to the split core.  Each convolution is asked on its own: one the kernel
+        does not take (stride 2, Cout = 64) or the policy leaves out keeps conv -> forward_relu while the other is fused."""
+        return (conv.bias is None and conv.in_channels >= self._skd_infer_min_cin
+                and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in INFER_ROUTING_EXCLUDED
+                and SF.conv3x3_infer_supported(x, conv, residual))
+
+    def _forward_infer(self, x):
+        """relu(bn1(conv1(x))) and relu(bn2(conv2(.)) + residual) as one launch of csrc/conv3x3.hip each (BN + ReLU, and BN +
+        residual + ReLU, in the epilogue) where _routed says so."""
+        r1 = self._routed(x, self.conv1, False)
+        if r1:
+            out = SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(self.conv1), self.conv1.out_channels, self.conv1.dilation[0],
+                                        None, self.bn1, "relu")
+        else:
+            out = self.bn1.forward_relu(self.conv1(x))
+        r2 = self._routed(out, self.conv2, True)
+        if self.downsample is None:
+            residual = x
+        elif not (r1 or r2):                 # nothing of this block is routed: the sequence it ran before, op for op
+            residual = self.downsample(x)
+        elif (_blas_tail(self, x) and len(self.downsample) == 2 and SF.blas_1x1_bn_supported(x, self.downsample[0])
+              and getattr(self.downsample[1], "activation", None) == "none"):
+            residual = _conv1x1_bn_eval(x, self.downsample[0], self.downsample[1], relu=False)
+        else:
+            residual = self.downsample(x)
+        if r2:
+            return SF.conv3x3_split_res_eval(out, SF.conv3x3_pack_weights(self.conv2), self.conv2.out_channels,
+                                             self.conv2.dilation[0], residual, self.bn2, "relu")
+        return self.bn2.forward_relu(self.conv2(out), residual)
+
     def forward(self, x):
+        if self._infer_form(x):
+            return self._forward_infer(x)
         if _fused(self, x):
             out = self.bn1.forward_relu(self.conv1(x))
             residual = self.downsample(x) if self.downsample is not None else x
@@ -374,3 +427,35 @@ class ResNet(nn.Module):
 def Res_pspnet(block=Bottleneck, layers=[3, 4, 23, 3], num_classes=21):
     """ResNet(Bottleneck, [3, 4, 23, 3], C) = teacher; ResNet(BasicBlock, [2, 2, 2, 2], C) = student."""
     return ResNet(block, layers, num_classes)
+
+
+def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
+    """Flag every BasicBlock of ``model`` (the student) for the fused inference form and return ``model``.
+
+    A flagged block in eval mode, with grad disabled, on an fp32 channels-last input runs ``conv1 -> bn1 -> relu`` and
+    ``conv2 -> bn2 -> + residual -> relu`` as one launch each of the split-core 3x3 convolution (csrc/conv3x3.hip) wherever the
+    kernel takes the convolution and it has at least ``min_cin`` input channels (FUSED_EVAL_MIN_CIN above); every other convolution,
+    and every training forward or forward with a graph, is what it was.  So the flag may be set on a live student: the
+    packed weights are keyed on ``(data_ptr, _version)`` and rebuild themselves after each optimizer update.  The weights that
+    are routed and already on the device are packed here, so a graph captured later allocates nothing for them.
+    ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
+    is set and changes nothing."""
+    for m in model.modules():
+        if not isinstance(m, BasicBlock):
+            continue
+        if not enable:
+            m._skd_infer_min_cin = None
+            for conv in (m.conv1, m.conv2):
+                if hasattr(conv, "_skd_conv3x3_pack"):
+                    del conv._skd_conv3x3_pack
+            continue
+        m._skd_infer_min_cin = int(min_cin)
+        with torch.no_grad():
+            for conv, res in ((m.conv1, False), (m.conv2, True)):
+                w = conv.weight
+                if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
+                    continue
+                probe = w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2)      # a channels-last map of the right width
+                if m._routed(probe, conv, res):
+                    SF.conv3x3_pack_weights(conv)
+    return model
