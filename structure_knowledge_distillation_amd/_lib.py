@@ -16,6 +16,7 @@ EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eva
 MS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval_ms.h"))
 OHEM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_ohem.h"))
 INFER_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_infer.h"))
+TRAIN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_train.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -176,6 +177,15 @@ INFER_SIGNATURES = {
     "skd_conv3x3_split_res_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
 }
 
+# Entry points declared in include/skd_train.h (csrc/conv3x3.hip): the training student's 3x3 convolutions on the split core,
+# extension entries in a table of their own like the three above (tests/test_conv3x3_train_cpu.py checks header <-> table <->
+# exported symbols, tests/test_conv3x3_train_gpu.py holds the guard-band case).  A back-end without them leaves the student's
+# convolutions on the library: nothing raises.
+TRAIN_SIGNATURES = {
+    "skd_conv3x3_split_train_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "skd_conv3x3_split_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -205,7 +215,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

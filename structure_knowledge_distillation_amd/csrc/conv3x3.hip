@@ -30,6 +30,7 @@
 // chip's two-per-CU slots once.  48 KB of LDS either way.
 #include "conv_split_dev.hpp"
 #include "skd_infer.h"
+#include "skd_train.h"
 
 namespace skd {
 namespace {
@@ -213,6 +214,15 @@ void conv3x3_split_kernel(
   }
 }
 
+// The three bf16 planes of one 16-byte chunk (8 consecutive k of one row) written to their places in the packed image.
+__device__ __forceinline__ void pack_chunk_store(const float (&v)[8], uint4 *__restrict__ pack, int64_t tile, int chunk) {
+  uint2 lo[3], hi[3];
+  split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
+  split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
+#pragma unroll
+  for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * kPlaneChunks + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
+}
+
 // One thread per 16-byte chunk of the image: the 8 consecutive k (one tap, 8 channels) of one output channel, three pieces.
 // The weight is read through its strides (elements), so contiguous and channels-last tensors give the same pack.
 __global__ void conv3x3_pack_kernel(const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int nk,
@@ -229,11 +239,44 @@ __global__ void conv3x3_pack_kernel(const float *__restrict__ Wt, int64_t sn, in
   float v[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = src[(c0 + i) * sc];
-  uint2 lo[3], hi[3];
-  split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
-  split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
+  pack_chunk_store(v, pack, tile, chunk);
+}
+
+// The training form's per-step split (include/skd_train.h): ONE launch writes the image of W (Cout, Cin, 3, 3) for the forward
+// convolution and the image of Wd[c][n][ty][tx] = W[n][c][2 - ty][2 - tx] (Cin, Cout, 3, 3) for the data gradient, both read
+// from W through its strides -- Wd is index arithmetic, never a tensor.  One workgroup of kPlaneChunks threads per (column tile,
+// K-tile) of one image, so the direction is uniform per workgroup: the first `fwd_tiles` workgroups are conv3x3_pack_kernel
+// chunk for chunk (the same eight loads, the same pack_chunk_store: the same bytes), the others write the backward image.
+// There the rows of a tile are 128 input channels c and the 8 consecutive k of a chunk are 8 output channels n at stride sn:
+// a wave's 64 lanes are 64 consecutive c, so each of its eight loads reads a run of 64 elements at stride sc -- 256 contiguous
+// bytes of a channels-last weight (sc = 1: the training student's, and the PSP bottleneck's channel slice).
+__global__ __launch_bounds__(kPlaneChunks) void conv3x3_pack_pair_kernel(
+    const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int Cout, int64_t fwd_tiles,
+    uint4 *__restrict__ pack_fwd, uint4 *__restrict__ pack_bwd) {
+  const int chunk = threadIdx.x;
+  const int kh = chunk >> 7, row = (chunk & 127) ^ (kh * 4);
+  float v[8];
+  if ((int64_t)blockIdx.x < fwd_tiles) {
+    const int64_t tile = blockIdx.x;                      // = tn * nk + kt, K = 9 * Cin
+    const int nk = 9 * (Cin / kBK);
+    const int kt = (int)(tile % nk), tn = (int)(tile / nk);
+    const int k0 = kt * kBK + kh * 8, tap = k0 / Cin, c0 = k0 - tap * Cin;
+    const int ty = tap / 3, tx = tap - 3 * ty;
+    const float *src = Wt + (int64_t)(tn * kTN + row) * sn + ty * sy + tx * sx;
 #pragma unroll
-  for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * kPlaneChunks + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
+    for (int i = 0; i < 8; ++i) v[i] = src[(c0 + i) * sc];
+    pack_chunk_store(v, pack_fwd, tile, chunk);
+  } else {
+    const int64_t tile = (int64_t)blockIdx.x - fwd_tiles;  // = tc * nk + kt, K = 9 * Cout
+    const int nk = 9 * (Cout / kBK);
+    const int kt = (int)(tile % nk), tc = (int)(tile / nk);
+    const int k0 = kt * kBK + kh * 8, tap = k0 / Cout, n0 = k0 - tap * Cout;
+    const int ty = 2 - tap / 3, tx = 2 - tap % 3;         // the flipped tap
+    const float *src = Wt + (int64_t)(tc * kTN + row) * sc + ty * sy + tx * sx;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = src[(n0 + i) * sn];
+    pack_chunk_store(v, pack_bwd, tile, chunk);
+  }
 }
 
 template <int ACT, bool TALL, bool HAS_RES>
@@ -305,6 +348,29 @@ int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t st
   const int64_t chunks = (int64_t)(Cout / kTN) * nk * kPlaneChunks;
   conv3x3_pack_kernel<<<dim3((unsigned)cdiv(chunks, 256)), dim3(256), 0, as_stream(stream)>>>(
       w, stride_n, stride_c, stride_y, stride_x, Cin, nk, chunks, static_cast<uint4 *>(pack));
+  return ok();
+}
+
+int skd_conv3x3_split_train_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return skd_conv3x3_split_supported(Cin, Cout, stride, padding, dilation, groups) && Cin % kTN == 0;
+}
+
+// Both images in one launch (include/skd_train.h); every refusal is decided here, in front of the launch.
+int skd_conv3x3_split_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
+                                skd_stream_t stream) {
+  if (!w || (!pack_fwd && !pack_bwd)) return 0;
+  if (stride_n < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0) return 0;
+  const int64_t need_f = pack_fwd ? skd_conv3x3_split_pack_bytes(Cin, Cout) : 0;
+  const int64_t need_b = pack_bwd ? skd_conv3x3_split_pack_bytes(Cout, Cin) : 0;
+  if (pack_fwd && (need_f == 0 || fwd_bytes < need_f || (reinterpret_cast<uintptr_t>(pack_fwd) & 15))) return 0;
+  if (pack_bwd && (need_b == 0 || bwd_bytes < need_b || (reinterpret_cast<uintptr_t>(pack_bwd) & 15))) return 0;
+  const int64_t fwd_tiles = pack_fwd ? (int64_t)(Cout / kTN) * (9 * (Cin / kBK)) : 0;
+  const int64_t bwd_tiles = pack_bwd ? (int64_t)(Cin / kTN) * (9 * (Cout / kBK)) : 0;
+  if (fwd_tiles + bwd_tiles > 2147483647) return 0;
+  conv3x3_pack_pair_kernel<<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(kPlaneChunks), 0, as_stream(stream)>>>(
+      w, stride_n, stride_c, stride_y, stride_x, Cin, Cout, fwd_tiles, static_cast<uint4 *>(pack_fwd),
+      static_cast<uint4 *>(pack_bwd));
   return ok();
 }
 

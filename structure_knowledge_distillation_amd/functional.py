@@ -421,29 +421,36 @@ def ppm_fold_supported(feats, sizes):
         and _is_cl(feats) and 3 * sum(sizes) <= 64 and len(sizes) <= 4
 
 
-def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False):
+def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False):
     """conv3x3(cat([upsample(p) for p in priors] + [feats], 1), weight, padding=1) (pspnet_combine.py:104-111) without
     the concatenated tensor and without convolving the priors' channels: the feature-map slice of the weight goes through
     the convolution, the priors through a (B s^2) x Cm x 9 Cout GEMM each and the fold kernel (csrc/ppm.hip).
     priors: (B, Cm, s, s) channels-last; feats: (B, Cf, H, W) channels-last; weight: (Cout, L*Cm + Cf, 3, 3).
     `cache` (a dict) keeps the rearranged weight slices of a frozen network between calls.  `split3x3`: run the feature-map
-    convolution on csrc/conv3x3.hip when conv3x3_split_supported-style conditions hold (no grad; weights packed once in `cache`)."""
+    convolution on csrc/conv3x3.hip when conv3x3_split_supported-style conditions hold (no grad; weights packed once in `cache`).
+    `split_train`: the same for a network in training, where conv3x3_train_supported says so (conv3x3_split_train on the strided
+    slice of the weight, so that autograd carries its gradient back into the full weight; packs once per weight version in `cache`)."""
     import torch.nn.functional as F
     cm = priors[0].shape[1]
     n_prior = len(priors) * cm
     cout = weight.shape[0]
     sizes = tuple(int(p.shape[2]) for p in priors)
+    train = bool(split_train and cache is not None and conv3x3_train_supported(feats, weight[:, n_prior:], 1, 1, 1, 1))
     key = (weight.data_ptr(), weight._version, tuple(weight.shape))
     mats = cache.get("mats") if cache is not None and cache.get("key") == key else None
     if mats is None:
-        wf = weight[:, n_prior:].contiguous(memory_format=torch.channels_last)
+        # (the routed training form reads the slice through its strides: no channels-last copy of it per step)
+        wf = None if train else weight[:, n_prior:].contiguous(memory_format=torch.channels_last)
         # (Cout, L, Cm, 3, 3) -> (Cm, L, 3, 3, Cout): column block k of the (Cm, L * 9 * Cout) matrix is level k's weights
         w_all = weight[:, :n_prior].reshape(cout, len(priors), cm, 3, 3).permute(2, 1, 3, 4, 0).reshape(cm, len(priors) * 9 * cout)
         mats = (wf, w_all)
-        if cache is not None and not (torch.is_grad_enabled() and weight.requires_grad):
+        if cache is not None and not train and not (torch.is_grad_enabled() and weight.requires_grad):
             cache["key"], cache["mats"] = key, mats
     wf, w_all = mats
-    if split3x3 and cache is not None and _conv3x3_split_ok(feats, weight[:, n_prior:], 1, 1, 1, 1):
+    if train:
+        owner = cache.setdefault("pack3x3_train", types.SimpleNamespace())
+        base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, owner)
+    elif split3x3 and cache is not None and _conv3x3_split_ok(feats, weight[:, n_prior:], 1, 1, 1, 1):
         owner = cache.setdefault("pack3x3", types.SimpleNamespace())
         base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], owner), cout)
     else:
@@ -813,6 +820,112 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
                                                      _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, act, slope,
                                                      int(geometry), _lib.stream_of(x)), "skd_conv3x3_split_res_nhwc")
     return out
+
+
+_TRAIN_ENTRIES = ("skd_conv3x3_split_train_supported", "skd_conv3x3_split_pack_pair", "skd_conv3x3_split_nhwc")
+
+
+def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
+    """True when conv3x3_split_train takes ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)`` of a network that is
+    being trained: grad enabled, a back-end that has the three entries (include/skd_train.h and skd_conv3x3_split_nhwc; the tests'
+    C double does not: callers then run the convolution they ran before), an fp32 channels-last 16-byte-aligned device input and
+    a (Cout, Cin, 3, 3) fp32 weight on its device whose forward AND data gradient fit the core: stride 1, padding == dilation,
+    ungrouped, Cin and Cout multiples of 128.  ``weight`` may be any strided view.  Host tensors pass only under a test double,
+    as in conv3x3_infer_supported."""
+    if not torch.is_grad_enabled() or not all(_lib.has_entry(n) for n in _TRAIN_ENTRIES):
+        return False
+    if not ((x.is_cuda or _lib.test_backend_active()) and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return False
+    if not (weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and weight.dtype == torch.float32
+            and weight.device == x.device and x.shape[1] == weight.shape[1] * groups):
+        return False
+    return bool(_lib.get().skd_conv3x3_split_train_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride), int(padding),
+                                                             int(dilation), int(groups)))
+
+
+def conv3x3_train_packs(weight, owner=None):
+    """``(pack_fwd, pack_bwd)`` of a trained (Cout, Cin, 3, 3) weight: the image csrc/conv3x3.hip streams for the forward
+    convolution and the image of the flipped, transposed weight for its data gradient, written by ONE launch of
+    skd_conv3x3_split_pack_pair under no_grad.  Cached on ``owner`` (any object that takes attributes; None: no cache) under
+    ``(data_ptr, _version, shape, stride)`` with the weight's storage held alive, as conv3x3_pack_weights does: one split per
+    weight version, so once per optimizer step -- provided the optimizer advances ``_version`` (torch's fused multi-tensor
+    optimizers do not: networks.kd_model.advance_versions_after_step is the step post-hook that does it for them)."""
+    w = weight
+    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()))
+    cached = getattr(owner, "_skd_conv3x3_train_pack", None)
+    if cached is not None and cached[0] == key:
+        return cached[1], cached[2]
+    _lib.require_device(w)
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    lib = _lib.get()
+    if (tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32
+            or not lib.skd_conv3x3_split_train_supported(cin, cout, 1, 1, 1, 1)):
+        raise ValueError("conv3x3_train_packs: unsupported weight %s" % (tuple(w.shape),))
+    nbytes = int(lib.skd_conv3x3_split_pack_bytes(cin, cout))
+    with torch.no_grad():
+        pack_fwd = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        pack_bwd = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+        sn, sc, sy, sx = (int(v) for v in w.stride())
+        _lib.check(lib.skd_conv3x3_split_pack_pair(cin, cout, w.data_ptr(), sn, sc, sy, sx, pack_fwd.data_ptr(), nbytes,
+                                                   pack_bwd.data_ptr(), nbytes, _lib.stream_of(pack_fwd)),
+                   "skd_conv3x3_split_pack_pair")
+    if owner is not None:
+        owner._skd_conv3x3_train_pack = (key, pack_fwd, pack_bwd, w.untyped_storage())
+    return pack_fwd, pack_bwd
+
+
+def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None):
+    """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc."""
+    b, cin, h, w = x.shape
+    # not a view (_new_cl's is one): the in-place ABN behind dsn[0] writes into a custom Function's output
+    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _lib.check(_lib.get().skd_conv3x3_split_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                                 _lib.ptr(conv_bias), None, None, None, None, 0.0, 0, 0.01, 0, _lib.stream_of(x)),
+               "skd_conv3x3_split_nhwc")
+    return out
+
+
+class _Conv3x3SplitTrain(Function):
+    """A same-size 3x3 convolution of a network in training, both directions on csrc/conv3x3.hip: the forward on ``pack_fwd``, the
+    data gradient -- the same kind of convolution of the output gradient with the flipped, transposed weight -- on the
+    ``pack_bwd`` THIS forward was given (kept in ctx: an optimizer step in between changes the cache, not this node).  The
+    weight gradient (and the bias gradient) are the library's, as before."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd):
+        _lib.require_device(x, weight, bias, pack_fwd, pack_bwd)
+        ctx.save_for_backward(x, weight)
+        ctx.pack_bwd, ctx.dilation, ctx.has_bias = pack_bwd, int(dilation), bias is not None
+        return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors         # a weight written since the forward raises autograd's version error here
+        d = ctx.dilation
+        g = _cl(g.to(torch.float32))
+        if g.data_ptr() % 16:
+            g = g.clone(memory_format=torch.channels_last)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _conv3x3_split_launch(g, ctx.pack_bwd, int(weight.shape[1]), d)
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if need_w or need_b:
+            _, dw, db = torch.ops.aten.convolution_backward(g, x, weight, [int(weight.shape[0])] if ctx.has_bias else None,
+                                                            [1, 1], [d, d], [d, d], False, [0, 0], 1, (False, need_w, need_b))
+            dw, db = dw if need_w else None, db if need_b else None
+        return dx, dw, db, None, None, None
+
+
+def conv3x3_split_train(x, weight, dilation, bias=None, owner=None):
+    """``F.conv2d(x, weight, bias, 1, dilation, dilation)`` for a call conv3x3_train_supported accepted, differentiable: forward
+    and data gradient are one launch each of the split-core implicit GEMM (csrc/conv3x3.hip: fp32 in and out, three bf16 pieces,
+    six products, fp32 accumulation; the numerics of conv3x3_split_eval in both directions), the weight and bias gradients come
+    from ``aten.convolution_backward``.  The weight is split once per version (conv3x3_train_packs, cached on ``owner``); the
+    bias is added in the forward's epilogue."""
+    pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
+    return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd)
 
 
 def seg_confusion(logits, target=None, ignore_index=255, confusion=None, want_pred=True):

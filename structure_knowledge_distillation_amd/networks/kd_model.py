@@ -31,7 +31,7 @@ from ..utils import parallel as parallel_old
 from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
 from ..utils.utils import print_model_parm_nums, to_tuple_str  # noqa: F401
-from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference
+from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_training_convs
 from .sagan_models import Discriminator
 
 
@@ -176,6 +176,15 @@ class NetModel():
         # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
         if getattr(args, "fused_eval", False):
             fuse_for_inference(student)
+        # args.split_train (None: SKD_SPLIT_TRAIN, default "0"): the student's stride-1 3x3 convolutions with >= 128 channels and
+        # their data gradients run on the split core in training (pspnet_combine.route_training_convs); the weight gradients,
+        # the eval forms and the frozen teacher are what they were.  Off by default (profiles/r18_step_ab.md has the A/B).
+        split_train = getattr(args, "split_train", None)
+        if split_train is None:
+            split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
+        self.split_train = bool(split_train)
+        if self.split_train:
+            route_training_convs(student)
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -212,6 +221,9 @@ class NetModel():
                                   momentum=args.momentum, weight_decay=args.weight_decay, **fused)
         self.D_solver = optim.SGD([{"params": self._d_params, "initial_lr": args.lr_d}], args.lr_d,
                                   momentum=args.momentum, weight_decay=args.weight_decay, **fused)
+        if self.split_train:
+            # the per-step weight split is keyed on the weights' autograd version, which torch's fused SGD does not advance
+            self.G_solver.register_step_post_hook(advance_versions_after_step)
         self._s_reducer = parallel_old.GradientAllReducer(self._s_params)
         self._d_reducer = parallel_old.GradientAllReducer(self._d_params)
 
@@ -799,6 +811,17 @@ class NetModel():
             torch.distributed.barrier()
 
 
+def advance_versions_after_step(optimizer, args=None, kwargs=None):
+    """Optimizer step post-hook (``optimizer.register_step_post_hook``): advance the autograd version counter of every parameter
+    the step wrote.  torch's fused multi-tensor optimizers update the parameters in place WITHOUT advancing ``_version`` (the
+    plain and foreach forms do), and the packed weights of functional.conv3x3_train_packs are keyed on it: without this hook
+    the second step's convolutions would run on the first step's weights.  No kernel is launched."""
+    for group in optimizer.param_groups:
+        for p in group["params"]:
+            if p.grad is not None:
+                torch.autograd.graph.increment_version(p)
+
+
 def default_args(**overrides):
     """The flag defaults of utils/train_options.py:18-63 that shape the step, as a namespace
     (``run_train_val.sh`` overrides: weight_decay 5e-4, lambda_pa 0.5)."""
@@ -811,7 +834,9 @@ def default_args(**overrides):
         T_ckpt_path=None, is_student_load_imgnet=False, student_pretrain_model_imgnet=None,
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
-        ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False)
+        ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None)
     for k, v in overrides.items():
         setattr(a, k, v)
+    if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
+        a.split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
     return a

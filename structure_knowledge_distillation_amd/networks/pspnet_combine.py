@@ -3,9 +3,11 @@
 Same public surface, module names and state-dict keys as the reference's
 networks/pspnet_combine.py:114-197 (150 tensors student / 565 teacher), so its checkpoints load
 and ``forward`` returns the same 7-element list ``[logits, dsn, feat_after_psp, x4, x3, x2, x1]``
-(pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm -- except the frozen teacher's 1x1 GEMMs (csrc/conv1x1.hip) and its wide
-stride-1 3x3 convolutions (csrc/conv3x3.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation
-is the hand-written InPlace-ABN of csrc/abn*.hip (``libs``), applied in place on the conv output.
+(pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm -- except the frozen teacher's 1x1 GEMMs (csrc/conv1x1.hip), its wide
+stride-1 3x3 convolutions (csrc/conv3x3.hip), the student's 3x3 convolutions in its inference form (fuse_for_inference) and, opt-in,
+the training student's stride-1 3x3 convolutions and their data gradients (route_training_convs; the weight gradients stay on
+MIOpen), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
+csrc/abn*.hip (``libs``), applied in place on the conv output.
 """
 import functools
 
@@ -63,6 +65,37 @@ SPLIT_REDUCE = True   # the reduce / stride-1 down-sample 1x1 GEMMs on csrc/conv
 # conv -> forward_relu: none does.
 FUSED_EVAL_MIN_CIN = 128
 INFER_ROUTING_EXCLUDED = frozenset()
+
+
+# The student's training form (route_training_convs, below; opt-in): a flagged module in training mode, with grad enabled, on an
+# fp32 channels-last device input hands a stride-1 3x3 convolution with at least ``min_cin`` input channels, and its data gradient,
+# to the split core (SF.conv3x3_split_train) where both directions fit it (Cin and Cout multiples of 128).  TRAIN_SPLIT_MIN_CIN = 128
+# routes 13 convolutions of the ResNet18 student: layer2.0.conv2, layer2.1, layer3, layer4, the deep-supervision head's dsn[0] and
+# the PSP bottleneck's feature-map half; the stem, layer1 (64 channels) and layer2.0.conv1 (stride 2) are not the kernel's.  A
+# routed shape that measures behind is listed in TRAIN_ROUTING_EXCLUDED as (Cin, Cout, dilation) and keeps the library
+# (profiles/r18_conv3x3_train_isolated.md has every shape).
+TRAIN_SPLIT_MIN_CIN = 128
+TRAIN_ROUTING_EXCLUDED = frozenset()
+
+
+def _train_routed(module, x, conv):
+    """Whether the flagged ``module`` (route_training_convs) in training mode hands ``conv(x)`` to SF.conv3x3_split_train."""
+    min_cin = getattr(module, "_skd_train_min_cin", None)
+    if min_cin is None or not module.training or conv.in_channels < min_cin:
+        return False
+    if not (isinstance(conv, nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
+        return False
+    s, p, d = conv.stride, conv.padding, conv.dilation
+    if s[0] != s[1] or p[0] != p[1] or d[0] != d[1] or (conv.in_channels, conv.out_channels, d[0]) in TRAIN_ROUTING_EXCLUDED:
+        return False
+    return SF.conv3x3_train_supported(x, conv.weight, s[0], p[0], d[0], conv.groups)
+
+
+def _train_conv(module, conv, x):
+    """``conv(x)``: on the split core in both directions where _train_routed says so, the module's own forward otherwise."""
+    if _train_routed(module, x, conv):
+        return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv)
+    return conv(x)
 
 
 def _fused_tail(x):
@@ -190,9 +223,9 @@ class BasicBlock(nn.Module):
         if self._infer_form(x):
             return self._forward_infer(x)
         if _fused(self, x):
-            out = self.bn1.forward_relu(self.conv1(x))
+            out = self.bn1.forward_relu(_train_conv(self, self.conv1, x))
             residual = self.downsample(x) if self.downsample is not None else x
-            return self.bn2.forward_relu(self.conv2(out), residual)
+            return self.bn2.forward_relu(_train_conv(self, self.conv2, out), residual)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         residual = self.downsample(x) if self.downsample is not None else x
@@ -306,8 +339,11 @@ class PSPModule(nn.Module):
                 # the priors never meet the convolution: conv3x3(cat) = conv3x3(feats) + fold(priors x W) by linearity
                 if not hasattr(self, "_fold_cache"):
                     self._fold_cache = {}
+                min_cin = getattr(self, "_skd_train_min_cin", None)
                 out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache,
-                                             split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN)
+                                             split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
+                                             split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
+                                                          and (feats.shape[1], conv.out_channels, 1) not in TRAIN_ROUTING_EXCLUDED))
                 return self.bottleneck[2](self.bottleneck[1](out))
             return self.bottleneck(SF.ppm_concat(priors, feats))
         h, w = feats.size(2), feats.size(3)
@@ -372,6 +408,8 @@ class ResNet(nn.Module):
             y = SF.conv3x3_split_eval(x3, SF.conv3x3_pack_weights(conv), conv.out_channels, conv.dilation[0], conv.bias, bn,
                                       bn.activation)
             return self.dsn[3](y)
+        if _train_routed(self, x3, conv):      # the training form: the same sequence with dsn[0] (bias in the epilogue) on the split core
+            return self.dsn[3](self.dsn[2](bn(_train_conv(self, conv, x3))))
         return self.dsn(x3)
 
     def forward(self, x):
@@ -458,4 +496,33 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
                 probe = w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2)      # a channels-last map of the right width
                 if m._routed(probe, conv, res):
                     SF.conv3x3_pack_weights(conv)
+    return model
+
+
+def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN):
+    """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
+
+    A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
+    ``conv2``, the deep-supervision head's ``dsn[0]`` (bias in the epilogue) and the feature-map half of the PSP bottleneck on the
+    split core of csrc/conv3x3.hip, forward and data gradient (SF.conv3x3_split_train), wherever both directions fit the kernel
+    and the convolution has at least ``min_cin`` input channels (TRAIN_SPLIT_MIN_CIN above); the weight gradients, every other
+    convolution, everything around these calls (forward_relu, the residual, dropout, the fold) and every eval-mode or no-grad
+    forward are what they were.  The weights are split once per weight version, i.e. once per optimizer step, in the forward.
+    The version is autograd's ``_version``: an optimizer that writes the weights without advancing it -- torch's FUSED
+    multi-tensor optimizers -- needs ``kd_model.advance_versions_after_step`` as a step post-hook (NetModel registers it), or the
+    next forward runs on the packs of the old weights.
+    ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
+    set and changes nothing."""
+    for m in model.modules():
+        if not isinstance(m, (BasicBlock, ResNet, PSPModule)):
+            continue
+        m._skd_train_min_cin = int(min_cin) if enable else None
+        if enable:
+            continue
+        convs = (m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0],) if isinstance(m, ResNet) else ()
+        for conv in convs:
+            if hasattr(conv, "_skd_conv3x3_train_pack"):
+                del conv._skd_conv3x3_train_pack
+        if isinstance(m, PSPModule):
+            getattr(m, "_fold_cache", {}).pop("pack3x3_train", None)
     return model
