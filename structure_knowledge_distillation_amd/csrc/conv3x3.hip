@@ -11,8 +11,8 @@
 // peak (profiles/r06w_conv_shapes.md); the pipe is the limit, and six bf16 MFMAs per 16 k take 2.67 x less matrix-pipe time than
 // eight fp32 ones (conv1x1.hip).
 //
-// Weights are split ONCE (the network is frozen): conv3x3_pack_kernel writes, per column tile of 128 output channels and
-// per K-tile of 16 k, the three bf16 planes in exactly the LDS image of the core (kPlaneChunks layout) -- 768 chunks of 16
+// Weights are split ONCE per weight version (once for a frozen network): conv3x3_pack_pair_kernel writes, per column tile of 128
+// output channels and per K-tile of 16 k, the three bf16 planes in exactly the LDS image of the core (kPlaneChunks layout) -- 768 chunks of 16
 // bytes.  The main loop's B stage is then three 16-byte global loads and three ds_write_b128 per thread: no VALU work.  The split
 // is a pure function of the fp32 value, so the result equals splitting in the loop bit for bit.  Activations are split on
 // their way into LDS as in the 1x1 kernel (each element nine times, once per tap).
@@ -223,31 +223,13 @@ __device__ __forceinline__ void pack_chunk_store(const float (&v)[8], uint4 *__r
   for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * kPlaneChunks + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-// One thread per 16-byte chunk of the image: the 8 consecutive k (one tap, 8 channels) of one output channel, three pieces.
-// The weight is read through its strides (elements), so contiguous and channels-last tensors give the same pack.
-__global__ void conv3x3_pack_kernel(const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int nk,
-                                    int64_t chunks, uint4 *__restrict__ pack) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= chunks) return;
-  const int chunk = (int)(idx % kPlaneChunks);
-  const int64_t tile = idx / kPlaneChunks;                // = tn * nk + kt
-  const int kt = (int)(tile % nk), tn = (int)(tile / nk);
-  const int kh = chunk >> 7, row = (chunk & 127) ^ (kh * 4);
-  const int k0 = kt * kBK + kh * 8, tap = k0 / Cin, c0 = k0 - tap * Cin;
-  const int ty = tap / 3, tx = tap - 3 * ty;
-  const float *src = Wt + (int64_t)(tn * kTN + row) * sn + ty * sy + tx * sx;
-  float v[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = src[(c0 + i) * sc];
-  pack_chunk_store(v, pack, tile, chunk);
-}
-
-// The training form's per-step split (include/skd_train.h): ONE launch writes the image of W (Cout, Cin, 3, 3) for the forward
-// convolution and the image of Wd[c][n][ty][tx] = W[n][c][2 - ty][2 - tx] (Cin, Cout, 3, 3) for the data gradient, both read
-// from W through its strides -- Wd is index arithmetic, never a tensor.  One workgroup of kPlaneChunks threads per (column tile,
-// K-tile) of one image, so the direction is uniform per workgroup: the first `fwd_tiles` workgroups are conv3x3_pack_kernel
-// chunk for chunk (the same eight loads, the same pack_chunk_store: the same bytes), the others write the backward image.
-// There the rows of a tile are 128 input channels c and the 8 consecutive k of a chunk are 8 output channels n at stride sn:
+// The weight split, of a frozen network (once) and of the training form (per step, include/skd_train.h): ONE launch writes the
+// image of W (Cout, Cin, 3, 3) for the forward convolution and / or the image of Wd[c][n][ty][tx] = W[n][c][2 - ty][2 - tx]
+// (Cin, Cout, 3, 3) for the data gradient, both read from W through its strides (elements) -- contiguous and channels-last
+// tensors give the same pack, and Wd is index arithmetic, never a tensor.  One workgroup of kPlaneChunks threads per (column tile,
+// K-tile) of one image, one thread per 16-byte chunk (the 8 consecutive k of one row, three pieces), so the direction is uniform
+// per workgroup: the first `fwd_tiles` workgroups write the forward image (8 k = one tap, 8 channels of one output channel), the
+// others the backward image.  There the rows of a tile are 128 input channels c and the 8 consecutive k of a chunk are 8 output channels n at stride sn:
 // a wave's 64 lanes are 64 consecutive c, so each of its eight loads reads a run of 64 elements at stride sc -- 256 contiguous
 // bytes of a channels-last weight (sc = 1: the training student's, and the PSP bottleneck's channel slice).
 __global__ __launch_bounds__(kPlaneChunks) void conv3x3_pack_pair_kernel(
@@ -339,39 +321,38 @@ int64_t skd_conv3x3_split_pack_bytes(int Cin, int Cout) {
   return (int64_t)(Cout / kTN) * (9 * (Cin / kBK)) * kTileChunks * (int64_t)sizeof(uint4);
 }
 
-int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
-                                   int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
-  const int64_t need = skd_conv3x3_split_pack_bytes(Cin, Cout);
-  if (need == 0 || !w || !pack || pack_bytes < need || (reinterpret_cast<uintptr_t>(pack) & 15)) return 0;
-  if (stride_n < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0) return 0;
-  const int nk = 9 * (Cin / kBK);
-  const int64_t chunks = (int64_t)(Cout / kTN) * nk * kPlaneChunks;
-  conv3x3_pack_kernel<<<dim3((unsigned)cdiv(chunks, 256)), dim3(256), 0, as_stream(stream)>>>(
-      w, stride_n, stride_c, stride_y, stride_x, Cin, nk, chunks, static_cast<uint4 *>(pack));
-  return ok();
-}
-
 int skd_conv3x3_split_train_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
   return skd_conv3x3_split_supported(Cin, Cout, stride, padding, dilation, groups) && Cin % kTN == 0;
 }
 
-// Both images in one launch (include/skd_train.h); every refusal is decided here, in front of the launch.
+// The (column tile, K-tile) count of the image of an (N, K / 9, 3, 3) weight in `pack`, 0 for no image (pack == nullptr), -1
+// for an image that is refused: a direction the core does not take, a buffer too small or not 16-byte aligned.
+static int64_t pack_image_tiles(int K9, int N, const void *pack, int64_t pack_bytes) {
+  if (!pack) return 0;
+  const int64_t need = skd_conv3x3_split_pack_bytes(K9, N);
+  if (need == 0 || pack_bytes < need || (reinterpret_cast<uintptr_t>(pack) & 15)) return -1;
+  return (int64_t)(N / kTN) * (9 * (K9 / kBK));
+}
+
+// Either image or both in one launch (include/skd_train.h); every refusal is decided here, in front of the launch.
 int skd_conv3x3_split_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
                                 int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
                                 skd_stream_t stream) {
   if (!w || (!pack_fwd && !pack_bwd)) return 0;
   if (stride_n < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0) return 0;
-  const int64_t need_f = pack_fwd ? skd_conv3x3_split_pack_bytes(Cin, Cout) : 0;
-  const int64_t need_b = pack_bwd ? skd_conv3x3_split_pack_bytes(Cout, Cin) : 0;
-  if (pack_fwd && (need_f == 0 || fwd_bytes < need_f || (reinterpret_cast<uintptr_t>(pack_fwd) & 15))) return 0;
-  if (pack_bwd && (need_b == 0 || bwd_bytes < need_b || (reinterpret_cast<uintptr_t>(pack_bwd) & 15))) return 0;
-  const int64_t fwd_tiles = pack_fwd ? (int64_t)(Cout / kTN) * (9 * (Cin / kBK)) : 0;
-  const int64_t bwd_tiles = pack_bwd ? (int64_t)(Cin / kTN) * (9 * (Cout / kBK)) : 0;
-  if (fwd_tiles + bwd_tiles > 2147483647) return 0;
+  const int64_t fwd_tiles = pack_image_tiles(Cin, Cout, pack_fwd, fwd_bytes);
+  const int64_t bwd_tiles = pack_image_tiles(Cout, Cin, pack_bwd, bwd_bytes);
+  if (fwd_tiles < 0 || bwd_tiles < 0 || fwd_tiles + bwd_tiles > 2147483647) return 0;
   conv3x3_pack_pair_kernel<<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(kPlaneChunks), 0, as_stream(stream)>>>(
       w, stride_n, stride_c, stride_y, stride_x, Cin, Cout, fwd_tiles, static_cast<uint4 *>(pack_fwd),
       static_cast<uint4 *>(pack_bwd));
   return ok();
+}
+
+// The forward image alone (include/skd_eval.h): the same launch without a backward image.
+int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                   int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
+  return skd_conv3x3_split_pack_pair(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
 }
 
 // The shared body of the two entries; residual == nullptr takes the instantiations without the residual read.
@@ -386,22 +367,17 @@ static int conv3x3_split_run(int B, int H, int W, int Cin, int Cout, int dilatio
   const int64_t M = (int64_t)B * H * W;
   hipStream_t st = as_stream(stream);
   const uint4 *bp = static_cast<const uint4 *>(wpack);
-#define SKD_CONV3X3_ARGS x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st
-  if (residual != nullptr) {
-    switch (activation) {
-      case SKD_ACT_NONE: return launch3g<SKD_ACT_NONE, true>(SKD_CONV3X3_ARGS);
-      case SKD_ACT_RELU: return launch3g<SKD_ACT_RELU, true>(SKD_CONV3X3_ARGS);
-      case SKD_ACT_LEAKY_RELU: return launch3g<SKD_ACT_LEAKY_RELU, true>(SKD_CONV3X3_ARGS);
-      default: return 0;
-    }
-  }
+#define SKD_CONV3X3_CASE(ACT)                                                                                                 \
+  case ACT:                                                                                                                   \
+    return (residual != nullptr ? launch3g<ACT, true> : launch3g<ACT, false>)(                                               \
+        x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
   switch (activation) {
-    case SKD_ACT_NONE: return launch3g<SKD_ACT_NONE, false>(SKD_CONV3X3_ARGS);
-    case SKD_ACT_RELU: return launch3g<SKD_ACT_RELU, false>(SKD_CONV3X3_ARGS);
-    case SKD_ACT_LEAKY_RELU: return launch3g<SKD_ACT_LEAKY_RELU, false>(SKD_CONV3X3_ARGS);
+    SKD_CONV3X3_CASE(SKD_ACT_NONE);
+    SKD_CONV3X3_CASE(SKD_ACT_RELU);
+    SKD_CONV3X3_CASE(SKD_ACT_LEAKY_RELU);
     default: return 0;
   }
-#undef SKD_CONV3X3_ARGS
+#undef SKD_CONV3X3_CASE
 }
 
 int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,

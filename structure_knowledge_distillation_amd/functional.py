@@ -19,7 +19,6 @@ derivatives of the discriminator's stock convolutions; the spectral-norm node is
 by the final ``d_loss.backward()``.
 """
 import ctypes
-import types
 
 import torch
 from torch.autograd import Function
@@ -219,6 +218,46 @@ def _cl(t):
 def _new_cl(ref, b, c, h, w):
     """Uninitialised (b, c, h, w) tensor with channels-last memory (b, h, w, c)."""
     return ref.new_empty((b, h, w, c), dtype=torch.float32).permute(0, 3, 1, 2)
+
+
+def _fp32_cl_map(x, host_ok=True):
+    """A device tensor (``host_ok``: or a host tensor under the tests' C-ABI double), fp32, 4-D, channels-last memory."""
+    return ((x.is_cuda or (host_ok and _lib.test_backend_active())) and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+# ---- the one version-keyed cache of everything derived from module tensors (folded BN operands, ABN constants, weight packs) ----
+# THE RULE: a cached value is that of its tensors for as long as their addresses and autograd version counters stand.  In-place
+# ops, ``load_state_dict`` and torch's plain / foreach optimizers advance ``_version``; torch's FUSED multi-tensor optimizers write
+# the parameters without advancing it, so whoever trains with one registers ``networks.kd_model.advance_versions_after_step`` as a
+# step post-hook on it (NetModel does, always) -- and a write through ``tensor.data`` is never seen: drop the cache by hand.
+
+def _version_key(tensors, *extras):
+    """``(data_ptr, _version, data_ptr, _version, ..., *extras)``: two entries per tensor, ``None, None`` for an absent one."""
+    return tuple(v for t in tensors for v in ((None, None) if t is None else (t.data_ptr(), t._version))) + extras
+
+
+def _cached(owner, attr, key, build, hold=None):
+    """The tuple ``build()`` returns, cached on ``owner`` (a dict, any object that takes attributes, or None: no cache) as
+    ``(key, *values)`` under ``attr`` and rebuilt when ``key`` differs.  ``hold``: a tensor whose storage is kept alive behind the
+    values -- while it lives no other tensor can take its address, so a weight moved to new storage (``.to()``) can never be
+    mistaken for the cached one."""
+    slot = owner if isinstance(owner, dict) or owner is None else vars(owner)
+    hit = slot.get(attr) if slot is not None else None
+    if hit is not None and hit[0] == key:
+        return hit[1:len(hit) - (hold is not None)]
+    values = tuple(build())
+    if slot is not None:
+        slot[attr] = (key,) + values + (() if hold is None else (hold.untyped_storage(),))
+    return values
+
+
+def drop_conv3x3_packs(owner):
+    """Forget the weight packs conv3x3_pack_weights / conv3x3_train_packs cached on ``owner`` (a module, or a PSPModule's
+    ``_fold_cache`` dict, whose packs sit under "pack3x3" / "pack3x3_train")."""
+    slot = owner if isinstance(owner, dict) else vars(owner)
+    for attr in ("_skd_conv3x3_pack", "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_train"):
+        slot.pop(attr, None)
 
 
 class _PPMPool(Function):
@@ -436,23 +475,19 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
     cout = weight.shape[0]
     sizes = tuple(int(p.shape[2]) for p in priors)
     train = bool(split_train and cache is not None and conv3x3_train_supported(feats, weight[:, n_prior:], 1, 1, 1, 1))
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape))
-    mats = cache.get("mats") if cache is not None and cache.get("key") == key else None
-    if mats is None:
+
+    def mats():
         # (the routed training form reads the slice through its strides: no channels-last copy of it per step)
         wf = None if train else weight[:, n_prior:].contiguous(memory_format=torch.channels_last)
         # (Cout, L, Cm, 3, 3) -> (Cm, L, 3, 3, Cout): column block k of the (Cm, L * 9 * Cout) matrix is level k's weights
-        w_all = weight[:, :n_prior].reshape(cout, len(priors), cm, 3, 3).permute(2, 1, 3, 4, 0).reshape(cm, len(priors) * 9 * cout)
-        mats = (wf, w_all)
-        if cache is not None and not train and not (torch.is_grad_enabled() and weight.requires_grad):
-            cache["key"], cache["mats"] = key, mats
-    wf, w_all = mats
+        return wf, weight[:, :n_prior].reshape(cout, len(priors), cm, 3, 3).permute(2, 1, 3, 4, 0).reshape(cm, len(priors) * 9 * cout)
+    # cached for a frozen call only: a weight that is being trained needs its matrices inside this call's graph
+    frozen = not train and not (torch.is_grad_enabled() and weight.requires_grad)
+    wf, w_all = _cached(cache if frozen else None, "mats", _version_key((weight,), tuple(weight.shape)), mats)
     if train:
-        owner = cache.setdefault("pack3x3_train", types.SimpleNamespace())
-        base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, owner)
-    elif split3x3 and cache is not None and _conv3x3_split_ok(feats, weight[:, n_prior:], 1, 1, 1, 1):
-        owner = cache.setdefault("pack3x3", types.SimpleNamespace())
-        base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], owner), cout)
+        base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}))
+    elif split3x3 and cache is not None and _conv3x3_ok(feats, weight[:, n_prior:], 1, 1, 1, 1, **_FROZEN):
+        base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3", {})), cout)
     else:
         base = F.conv2d(feats, wf, None, 1, 1)
     # ONE GEMM of all levels' priors against all levels' weight blocks (only the diagonal blocks are used: 4x the
@@ -501,11 +536,13 @@ def _pool_out(n, ceil_mode):
 stem_pool_out = _pool_out
 
 
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
 def is_stem_pool(pool):
     """nn.MaxPool2d(kernel_size=3, stride=2, padding=1[, ceil_mode]) without dilation / returned indices: what csrc/maxpool.hip and
     the fused stem kernels implement."""
-    def _pair(v):
-        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
     return (isinstance(pool, torch.nn.MaxPool2d) and _pair(pool.kernel_size) == (3, 3) and _pair(pool.stride) == (2, 2)
             and _pair(pool.padding) == (1, 1) and _pair(pool.dilation) == (1, 1) and not pool.return_indices)
 
@@ -591,20 +628,19 @@ def conv1x1_bn_blas(x, conv, bn, relu):
     eval-mode normalisation folds into it -- W' = W * s, b' = beta - mean * s, s = (|gamma| + eps) / sqrt(var + eps) -- and
     rocBLAS / hipBLASLt run that GEMM faster than MIOpen's implicit-GEMM convolution on the teacher's reduce layers
     (1024 -> 256 at 65 x 65, batch 8: 144 us with the epilogue vs 175 us convolution + 27 us ABN pass;
-    profiles/r02d_conv1x1_blas.jsonl), exact fp32 (no xf32 on gfx950).  The folded operands are cached on the BN module.
+    profiles/r02d_conv1x1_blas.jsonl), exact fp32 (no xf32 on gfx950).  The folded operands are cached on the BN module
+    (_cached, under THE RULE above it).
     In isolation the split-operand kernel behind conv1x1_abn_eval is now faster on most of these shapes (1024 -> 256 at
     65 x 65: 130 us against 146-155, profiles/r11_stage2_isolated.md); which of the two a frozen network's layer takes is
     networks.pspnet_combine.SPLIT_REDUCE, set by the step A/B of profiles/r12_step_ab.md (the kernel, except 512 -> 128)."""
-    key = tuple((t.data_ptr(), t._version) for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None)
-    fold = getattr(bn, "_blas_fold", None)
-    if fold is None or fold[0] != key:
+    def fold():
         gamma = (bn.weight.abs() + bn.eps) if bn.weight is not None else torch.ones_like(bn.running_var)
         scale = gamma / torch.sqrt(bn.running_var + bn.eps)
         w2 = (conv.weight.reshape(conv.out_channels, conv.in_channels) * scale.view(-1, 1)).contiguous()
         b2 = (bn.bias if bn.bias is not None else torch.zeros_like(scale)) - bn.running_mean * scale
-        fold = (key, w2, b2.contiguous())
-        bn._blas_fold = fold
-    _, w2, b2 = fold
+        return w2, b2.contiguous()
+    tensors = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    w2, b2 = _cached(bn, "_blas_fold", _version_key(tensors, float(bn.eps)), fold)
     b, _, h, w = x.shape
     x2 = x.permute(0, 2, 3, 1).reshape(b * h * w, conv.in_channels)
     out = torch._addmm_activation(b2, x2, w2.t()) if relu else torch.addmm(b2, x2, w2.t())
@@ -614,8 +650,7 @@ def conv1x1_bn_blas(x, conv, bn, relu):
 def conv1x1_abn_supported(x, conv):
     """True when the fused 1x1-convolution + eval-ABN GEMM of csrc/conv1x1.hip takes this call: fp32 channels-last
     input, a plain stride-1 1x1 convolution without bias, Cin a multiple of 16 and Cout of 128."""
-    if not ((x.is_cuda or _lib.test_backend_active()) and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):      # (CPU tensors only under the tests' C-ABI double)
+    if not _fp32_cl_map(x):
         return False
     if not (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
             and conv.bias is None and conv.weight.dtype == torch.float32):
@@ -626,22 +661,19 @@ def conv1x1_abn_supported(x, conv):
 
 def abn_pack_eval_params(bn):
     """(4, C) = [running_mean | 1 / sqrt(running_var + eps) | |weight| + eps | bias] of an eval-mode InPlace-ABN module (the
-    constants of bn.cu:146-159), cached on the module and rebuilt when any of its tensors is written (their autograd version
-    counters) or moved: the frozen teacher packs each BatchNorm once.  (A write through ``tensor.data`` does not bump the
-    version counter autograd keeps for ``tensor``: code that edits statistics that way must drop ``bn._skd_eval_pack`` itself;
-    ``load_state_dict``, optimizers and ordinary in-place ops are seen.)"""
-    key = tuple((t.data_ptr(), t._version) if t is not None else None
-                for t in (bn.running_mean, bn.running_var, bn.weight, bn.bias)) + (float(bn.eps),)
-    cached = getattr(bn, "_skd_eval_pack", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    c = bn.running_mean.numel()
-    pack = bn.running_mean.new_empty((4, c))
-    _lib.check(_lib.get().skd_abn_pack_eval_params(c, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), _lib.ptr(bn.weight),
-                                                   _lib.ptr(bn.bias), float(bn.eps), pack.data_ptr(), _lib.stream_of(pack)),
-               "skd_abn_pack_eval_params")
-    bn._skd_eval_pack = (key, pack)
-    return pack
+    constants of bn.cu:146-159), cached on the module as ``bn._skd_eval_pack`` and rebuilt when any of its tensors is written
+    (their autograd version counters) or moved: the frozen teacher packs each BatchNorm once.  What counts as written is THE RULE
+    above _version_key: ``load_state_dict``, ordinary in-place ops and torch's plain / foreach optimizers are seen; a fused
+    optimizer's step is seen only with ``kd_model.advance_versions_after_step`` registered on it (NetModel registers it; a caller
+    with a fused optimizer of their own must), a write through ``tensor.data`` never: drop ``bn._skd_eval_pack`` by hand."""
+    def build():
+        c = bn.running_mean.numel()
+        pack = bn.running_mean.new_empty((4, c))
+        _lib.check(_lib.get().skd_abn_pack_eval_params(c, bn.running_mean.data_ptr(), bn.running_var.data_ptr(), _lib.ptr(bn.weight),
+                                                       _lib.ptr(bn.bias), float(bn.eps), pack.data_ptr(), _lib.stream_of(pack)),
+                   "skd_abn_pack_eval_params")
+        return (pack,)
+    return _cached(bn, "_skd_eval_pack", _version_key((bn.running_mean, bn.running_var, bn.weight, bn.bias), float(bn.eps)), build)[0]
 
 
 def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
@@ -684,62 +716,138 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
     return out
 
 
-def _pair(v):
-    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+def conv2d_square_geometry(conv):
+    """``(stride, padding, dilation)`` of a plain nn.Conv2d (zero padding given as numbers, square), None for anything else."""
+    if not (isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
+        return None
+    s, p, d = _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation)
+    return None if s[0] != s[1] or p[0] != p[1] or d[0] != d[1] else (s[0], p[0], d[0])
 
 
-def _conv3x3_split_ok(x, weight, stride, padding, dilation, groups):
-    if torch.is_grad_enabled() or not _lib.has_entry("skd_conv3x3_split_nhwc"):
+def _conv3x3_ok(x, weight, stride, padding, dilation, groups, grad, entries, query, host_ok):
+    """The one predicate of the split-core 3x3 forms: grad is ``grad``, the back-end has every entry of ``entries``, ``x`` is an
+    fp32 channels-last 16-byte-aligned device map (``host_ok``: a host one passes under a test double), ``weight`` a
+    (Cout, Cin, 3, 3) fp32 tensor (any strided view) on its device with ``x.shape[1] == Cin * groups``, and the library's
+    ``query`` takes the geometry."""
+    if torch.is_grad_enabled() != grad or not all(_lib.has_entry(n) for n in entries):
         return False
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
-            and x.data_ptr() % 16 == 0):
+    if not (_fp32_cl_map(x, host_ok) and x.data_ptr() % 16 == 0):
         return False
     if not (weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and weight.dtype == torch.float32
             and weight.device == x.device and x.shape[1] == weight.shape[1] * groups):
         return False
-    return bool(_lib.get().skd_conv3x3_split_supported(int(weight.shape[1]), int(weight.shape[0]), stride, padding, dilation, groups))
+    return bool(getattr(_lib.get(), query)(int(weight.shape[1]), int(weight.shape[0]), int(stride), int(padding), int(dilation),
+                                           int(groups)))
+
+
+def _conv3x3_module_ok(x, conv, **form):
+    geometry = conv2d_square_geometry(conv)
+    return geometry is not None and _conv3x3_ok(x, conv.weight, *geometry, conv.groups, **form)
+
+
+# The frozen form refuses host tensors even under a test double: under the recording and computing doubles that is what keeps the
+# student's dsn[0] and PSP half on F.conv2d.
+_FROZEN = dict(grad=False, entries=("skd_conv3x3_split_nhwc",), query="skd_conv3x3_split_supported", host_ok=False)
+_TRAIN_ENTRIES = ("skd_conv3x3_split_train_supported", "skd_conv3x3_split_pack_pair", "skd_conv3x3_split_nhwc")
 
 
 def conv3x3_split_supported(x, conv):
     """True when the implicit-GEMM 3x3 convolution of csrc/conv3x3.hip takes ``conv(x)``: a back-end that has the entry (the
     tests' C double does not: callers then run ``F.conv2d`` as before), no grad, an fp32 channels-last input, a plain 3x3 /
     stride-1 / padding == dilation / ungrouped convolution with Cin a multiple of 16 and Cout of 128."""
-    if not (isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
-        return False
-    s, p, d = _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation)
-    if s[0] != s[1] or p[0] != p[1] or d[0] != d[1]:
-        return False
-    return _conv3x3_split_ok(x, conv.weight, s[0], p[0], d[0], conv.groups)
+    return _conv3x3_module_ok(x, conv, **_FROZEN)
+
+
+def conv3x3_infer_supported(x, conv, residual=False):
+    """True when a BasicBlock's inference form (networks.pspnet_combine.fuse_for_inference) may hand ``conv(x)`` to the split
+    core: the conditions of conv3x3_split_supported, asked of a back-end that has the entry the call needs --
+    ``skd_conv3x3_split_res_nhwc`` (include/skd_infer.h) with ``residual``, ``skd_conv3x3_split_nhwc`` without.  A back-end
+    without it (the tests' C double) answers False and the block runs the sequence it ran before.  Host tensors pass only
+    under a test double, as in conv1x1_abn_supported."""
+    entry = "skd_conv3x3_split_res_nhwc" if residual else "skd_conv3x3_split_nhwc"
+    return _conv3x3_module_ok(x, conv, grad=False, entries=(entry, "skd_conv3x3_split_supported"),
+                              query="skd_conv3x3_split_supported", host_ok=True)
+
+
+def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
+    """True when conv3x3_split_train takes ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)`` of a network that is
+    being trained: grad enabled, a back-end that has the three entries (include/skd_train.h and skd_conv3x3_split_nhwc; the tests'
+    C double does not: callers then run the convolution they ran before), an fp32 channels-last 16-byte-aligned device input and
+    a (Cout, Cin, 3, 3) fp32 weight on its device whose forward AND data gradient fit the core: stride 1, padding == dilation,
+    ungrouped, Cin and Cout multiples of 128.  ``weight`` may be any strided view.  Host tensors pass only under a test double,
+    as in conv3x3_infer_supported."""
+    return _conv3x3_ok(x, weight, stride, padding, dilation, groups, grad=True, entries=_TRAIN_ENTRIES,
+                       query="skd_conv3x3_split_train_supported", host_ok=True)
+
+
+def _conv3x3_packs(w, owner, attr, entry, both, what):
+    """The image(s) of the (Cout, Cin, 3, 3) weight ``w`` that csrc/conv3x3.hip streams into LDS, written by one launch of
+    ``entry`` and cached on ``owner`` as ``(key, *packs, storage)`` with ``key = (data_ptr, _version, shape, stride)``."""
+    def build():
+        _lib.require_device(w)
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        lib = _lib.get()
+        nbytes = int(lib.skd_conv3x3_split_pack_bytes(cin, cout))
+        if (nbytes <= 0 or tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32
+                or (both and not lib.skd_conv3x3_split_train_supported(cin, cout, 1, 1, 1, 1))):
+            raise ValueError("%s: unsupported weight %s" % (what, tuple(w.shape)))
+        with torch.no_grad():
+            packs = tuple(torch.empty((nbytes,), dtype=torch.uint8, device=w.device) for _ in range(1 + both))
+            sized = [v for pk in packs for v in (pk.data_ptr(), nbytes)]
+            _lib.check(getattr(lib, entry)(cin, cout, w.data_ptr(), *(int(v) for v in w.stride()), *sized, _lib.stream_of(packs[0])),
+                       entry)
+        return packs
+    return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build, hold=w)
 
 
 def conv3x3_pack_weights(conv, weight=None, owner=None):
     """The three bf16 planes of a frozen 3x3 convolution's weight in the layout csrc/conv3x3.hip streams into LDS (6 bytes per
-    weight), cached on ``owner`` (default: the conv module) under ``(data_ptr, _version)`` like abn_pack_eval_params and rebuilt
-    when the weight is written or moved.  ``weight`` (default ``conv.weight``) may be any strided (Cout, Cin, 3, 3) view -- the
-    PSP bottleneck packs the feature-map slice of its weight -- and either memory format gives the same pack.  The first call
+    weight), cached on ``owner`` (default: the conv module) like abn_pack_eval_params and rebuilt when the weight is written or
+    moved -- by THE RULE above _version_key: a fused optimizer's step counts as a write only with
+    ``kd_model.advance_versions_after_step`` registered on it (NetModel's has it; a caller who trains with a fused optimizer of
+    their own registers it themselves).  ``weight`` (default ``conv.weight``) may be any strided (Cout, Cin, 3, 3) view -- the PSP
+    bottleneck packs the feature-map slice of its weight -- and either memory format gives the same pack.  The first call
     allocates: a frozen network makes it in its eager warm-up steps, before any graph capture."""
     w = conv.weight if weight is None else weight
-    owner = conv if owner is None else owner
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_pack_weights is for frozen (no-grad) convolutions")
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()))
-    cached = getattr(owner, "_skd_conv3x3_pack", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    _lib.require_device(w)
-    cout, cin = int(w.shape[0]), int(w.shape[1])
+    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_pack", "skd_conv3x3_split_pack_weights", False,
+                          "conv3x3_pack_weights")[0]
+
+
+def conv3x3_train_packs(weight, owner=None):
+    """``(pack_fwd, pack_bwd)`` of a trained (Cout, Cin, 3, 3) weight: the image csrc/conv3x3.hip streams for the forward
+    convolution and the image of the flipped, transposed weight for its data gradient, written by ONE launch of
+    skd_conv3x3_split_pack_pair under no_grad.  Cached on ``owner`` (a dict or any object that takes attributes; None: no cache)
+    as conv3x3_pack_weights does: one split per weight version, so once per optimizer step -- provided the optimizer advances
+    ``_version`` (torch's fused multi-tensor optimizers do not: networks.kd_model.advance_versions_after_step is the step
+    post-hook that does it for them)."""
+    return _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack", "skd_conv3x3_split_pack_pair", True, "conv3x3_train_packs")
+
+
+_ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
+_RES_ENTRY = "skd_conv3x3_split_res_nhwc"
+
+
+def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0, residual=None):
+    """The one launcher of the split-core 3x3 forms: act(bn_running(conv3x3(x) + conv_bias) [+ residual]) by ``entry`` --
+    skd_conv3x3_split_nhwc, or skd_conv3x3_split_res_nhwc, which takes the ``residual`` pointer (None included)."""
     lib = _lib.get()
-    nbytes = int(lib.skd_conv3x3_split_pack_bytes(cin, cout))
-    if nbytes <= 0 or tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32:
-        raise ValueError("conv3x3_pack_weights: unsupported weight %s" % (tuple(w.shape),))
-    pack = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-    sn, sc, sy, sx = (int(v) for v in w.stride())
-    _lib.check(lib.skd_conv3x3_split_pack_weights(cin, cout, w.data_ptr(), sn, sc, sy, sx, pack.data_ptr(), nbytes,
-                                                  _lib.stream_of(pack)), "skd_conv3x3_split_pack_weights")
-    # the weight's storage is held with the pack: while it is alive no other tensor can take its address, so a weight moved
-    # to new storage (``.to()``) can never be mistaken for the packed one
-    owner._skd_conv3x3_pack = (key, pack, w.untyped_storage())
-    return pack
+    b, cin, h, w = x.shape
+    if pack.numel() != lib.skd_conv3x3_split_pack_bytes(cin, cout):
+        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
+    mean = var = gamma = beta = None
+    eps, slope = 0.0, 0.01
+    if bn is not None:
+        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
+    _lib.require_device(x, pack, residual, conv_bias, mean, var, gamma, beta)
+    # not a view (_new_cl's is one, with the same strides): the in-place ABN behind dsn[0] writes into a custom Function's output
+    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    res = (_lib.ptr(residual),) if entry == _RES_ENTRY else ()
+    _lib.check(getattr(lib, entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(), *res,
+                                   _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                   _ACT[activation], slope, int(geometry), _lib.stream_of(x)), entry)
+    return out
 
 
 def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0):
@@ -750,44 +858,7 @@ def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activ
     statistics and affine parameters go into the epilogue; ``activation``: 'none' / 'relu' / 'leaky_relu' (slope: ``bn.slope``)."""
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_split_eval is inference-only")
-    _lib.require_device(x, pack, conv_bias)
-    act = {"none": 0, "leaky_relu": 1, "relu": 3}[activation]
-    b, cin, h, w = x.shape
-    if pack.numel() != _lib.get().skd_conv3x3_split_pack_bytes(cin, cout):
-        raise ValueError("conv3x3_split_eval: the pack is not that of a (%d, %d, 3, 3) weight" % (cout, cin))
-    out = _new_cl(x, b, cout, h, w)
-    mean = var = gamma = beta = None
-    eps, slope = 0.0, 0.01
-    if bn is not None:
-        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
-    _lib.check(_lib.get().skd_conv3x3_split_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
-                                                 _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                                 eps, act, slope, int(geometry), _lib.stream_of(x)), "skd_conv3x3_split_nhwc")
-    return out
-
-
-def conv3x3_infer_supported(x, conv, residual=False):
-    """True when a BasicBlock's inference form (networks.pspnet_combine.fuse_for_inference) may hand ``conv(x)`` to the split
-    core: the conditions of conv3x3_split_supported, asked of a back-end that has the entry the call needs --
-    ``skd_conv3x3_split_res_nhwc`` (include/skd_infer.h) with ``residual``, ``skd_conv3x3_split_nhwc`` without.  A back-end
-    without it (the tests' C double) answers False and the block runs the sequence it ran before.  Host tensors pass only
-    under a test double, as in conv1x1_abn_supported."""
-    entry = "skd_conv3x3_split_res_nhwc" if residual else "skd_conv3x3_split_nhwc"
-    if torch.is_grad_enabled() or not (_lib.has_entry(entry) and _lib.has_entry("skd_conv3x3_split_supported")):
-        return False
-    if not (isinstance(conv, torch.nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
-        return False
-    s, p, d = _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation)
-    if s[0] != s[1] or p[0] != p[1] or d[0] != d[1]:
-        return False
-    wt = conv.weight
-    if not ((x.is_cuda or _lib.test_backend_active()) and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
-        return False
-    if not (wt.dtype == torch.float32 and wt.device == x.device and tuple(wt.shape[2:]) == (3, 3)
-            and x.shape[1] == wt.shape[1] * conv.groups):
-        return False
-    return bool(_lib.get().skd_conv3x3_split_supported(int(wt.shape[1]), int(wt.shape[0]), s[0], p[0], d[0], conv.groups))
+    return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias, bn, activation, geometry)
 
 
 def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, conv_bias=None, geometry=0):
@@ -799,91 +870,19 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
     conv3x3_split_eval; the residual add is one more fp32 rounding."""
     if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
         raise RuntimeError("conv3x3_split_res_eval is inference-only")
-    mean = var = gamma = beta = None
-    eps, slope = 0.0, 0.01
-    if bn is not None:
-        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
-    _lib.require_device(x, pack, residual, conv_bias, mean, var, gamma, beta)
-    if not _lib.has_entry("skd_conv3x3_split_res_nhwc"):
+    if not _lib.has_entry(_RES_ENTRY):
         raise NotImplementedError("this back-end has no skd_conv3x3_split_res_nhwc (include/skd_infer.h)")
-    act = {"none": 0, "leaky_relu": 1, "relu": 3}[activation]
-    b, cin, h, w = x.shape
-    if pack.numel() != _lib.get().skd_conv3x3_split_pack_bytes(cin, cout):
-        raise ValueError("conv3x3_split_res_eval: the pack is not that of a (%d, %d, 3, 3) weight" % (cout, cin))
     if residual is not None:
-        if tuple(residual.shape) != (b, cout, h, w) or residual.dtype != torch.float32:
-            raise ValueError("residual %s %s != output (%d, %d, %d, %d) fp32" % (tuple(residual.shape), residual.dtype, b, cout, h, w))
+        want = (x.shape[0], cout) + tuple(x.shape[2:])
+        if tuple(residual.shape) != want or residual.dtype != torch.float32:
+            raise ValueError("residual %s %s != output %s fp32" % (tuple(residual.shape), residual.dtype, want))
         residual = _cl(residual)
-    out = _new_cl(x, b, cout, h, w)
-    _lib.check(_lib.get().skd_conv3x3_split_res_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(),
-                                                     out.data_ptr(), _lib.ptr(residual), _lib.ptr(conv_bias), _lib.ptr(mean),
-                                                     _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, act, slope,
-                                                     int(geometry), _lib.stream_of(x)), "skd_conv3x3_split_res_nhwc")
-    return out
-
-
-_TRAIN_ENTRIES = ("skd_conv3x3_split_train_supported", "skd_conv3x3_split_pack_pair", "skd_conv3x3_split_nhwc")
-
-
-def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
-    """True when conv3x3_split_train takes ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)`` of a network that is
-    being trained: grad enabled, a back-end that has the three entries (include/skd_train.h and skd_conv3x3_split_nhwc; the tests'
-    C double does not: callers then run the convolution they ran before), an fp32 channels-last 16-byte-aligned device input and
-    a (Cout, Cin, 3, 3) fp32 weight on its device whose forward AND data gradient fit the core: stride 1, padding == dilation,
-    ungrouped, Cin and Cout multiples of 128.  ``weight`` may be any strided view.  Host tensors pass only under a test double,
-    as in conv3x3_infer_supported."""
-    if not torch.is_grad_enabled() or not all(_lib.has_entry(n) for n in _TRAIN_ENTRIES):
-        return False
-    if not ((x.is_cuda or _lib.test_backend_active()) and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
-        return False
-    if not (weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3) and weight.dtype == torch.float32
-            and weight.device == x.device and x.shape[1] == weight.shape[1] * groups):
-        return False
-    return bool(_lib.get().skd_conv3x3_split_train_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride), int(padding),
-                                                             int(dilation), int(groups)))
-
-
-def conv3x3_train_packs(weight, owner=None):
-    """``(pack_fwd, pack_bwd)`` of a trained (Cout, Cin, 3, 3) weight: the image csrc/conv3x3.hip streams for the forward
-    convolution and the image of the flipped, transposed weight for its data gradient, written by ONE launch of
-    skd_conv3x3_split_pack_pair under no_grad.  Cached on ``owner`` (any object that takes attributes; None: no cache) under
-    ``(data_ptr, _version, shape, stride)`` with the weight's storage held alive, as conv3x3_pack_weights does: one split per
-    weight version, so once per optimizer step -- provided the optimizer advances ``_version`` (torch's fused multi-tensor
-    optimizers do not: networks.kd_model.advance_versions_after_step is the step post-hook that does it for them)."""
-    w = weight
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()))
-    cached = getattr(owner, "_skd_conv3x3_train_pack", None)
-    if cached is not None and cached[0] == key:
-        return cached[1], cached[2]
-    _lib.require_device(w)
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    lib = _lib.get()
-    if (tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32
-            or not lib.skd_conv3x3_split_train_supported(cin, cout, 1, 1, 1, 1)):
-        raise ValueError("conv3x3_train_packs: unsupported weight %s" % (tuple(w.shape),))
-    nbytes = int(lib.skd_conv3x3_split_pack_bytes(cin, cout))
-    with torch.no_grad():
-        pack_fwd = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-        pack_bwd = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-        sn, sc, sy, sx = (int(v) for v in w.stride())
-        _lib.check(lib.skd_conv3x3_split_pack_pair(cin, cout, w.data_ptr(), sn, sc, sy, sx, pack_fwd.data_ptr(), nbytes,
-                                                   pack_bwd.data_ptr(), nbytes, _lib.stream_of(pack_fwd)),
-                   "skd_conv3x3_split_pack_pair")
-    if owner is not None:
-        owner._skd_conv3x3_train_pack = (key, pack_fwd, pack_bwd, w.untyped_storage())
-    return pack_fwd, pack_bwd
+    return _conv3x3_launch(_RES_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry, residual)
 
 
 def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None):
     """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc."""
-    b, cin, h, w = x.shape
-    # not a view (_new_cl's is one): the in-place ABN behind dsn[0] writes into a custom Function's output
-    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _lib.check(_lib.get().skd_conv3x3_split_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
-                                                 _lib.ptr(conv_bias), None, None, None, None, 0.0, 0, 0.01, 0, _lib.stream_of(x)),
-               "skd_conv3x3_split_nhwc")
-    return out
+    return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias)
 
 
 class _Conv3x3SplitTrain(Function):

@@ -221,9 +221,9 @@ class NetModel():
                                   momentum=args.momentum, weight_decay=args.weight_decay, **fused)
         self.D_solver = optim.SGD([{"params": self._d_params, "initial_lr": args.lr_d}], args.lr_d,
                                   momentum=args.momentum, weight_decay=args.weight_decay, **fused)
-        if self.split_train:
-            # the per-step weight split is keyed on the weights' autograd version, which torch's fused SGD does not advance
-            self.G_solver.register_step_post_hook(advance_versions_after_step)
+        # everything cached from the student's tensors (weight packs, folded PSP matrices, ABN constants: functional._cached) is
+        # keyed on their autograd version, which torch's fused SGD does not advance: a host call, nothing is launched
+        self.G_solver.register_step_post_hook(advance_versions_after_step)
         self._s_reducer = parallel_old.GradientAllReducer(self._s_params)
         self._d_reducer = parallel_old.GradientAllReducer(self._d_params)
 
@@ -814,12 +814,15 @@ class NetModel():
 def advance_versions_after_step(optimizer, args=None, kwargs=None):
     """Optimizer step post-hook (``optimizer.register_step_post_hook``): advance the autograd version counter of every parameter
     the step wrote.  torch's fused multi-tensor optimizers update the parameters in place WITHOUT advancing ``_version`` (the
-    plain and foreach forms do), and the packed weights of functional.conv3x3_train_packs are keyed on it: without this hook
-    the second step's convolutions would run on the first step's weights.  No kernel is launched."""
-    for group in optimizer.param_groups:
-        for p in group["params"]:
-            if p.grad is not None:
-                torch.autograd.graph.increment_version(p)
+    plain and foreach forms do), and every cache of functional.py that is derived from parameters is keyed on it
+    (functional._cached: the weight packs of conv3x3_pack_weights / conv3x3_train_packs, the PSP fold's matrices, the constants of
+    abn_pack_eval_params, the folded operands of conv1x1_bn_blas).  Without this hook the training form's second step would
+    run on the first step's weights, and every eval-mode forward of the student behind its first (the validation between
+    epochs) on the weights of that first one.  NetModel registers it on the student's optimizer, always; whoever trains these
+    modules with a fused optimizer of their own must register it themselves -- that much stays open.  No kernel is launched."""
+    written = [p for group in optimizer.param_groups for p in group["params"] if p.grad is not None]
+    if written:
+        torch.autograd.graph.increment_version(written)      # one host call for all of them
 
 
 def default_args(**overrides):

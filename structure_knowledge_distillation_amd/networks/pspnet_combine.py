@@ -83,12 +83,10 @@ def _train_routed(module, x, conv):
     min_cin = getattr(module, "_skd_train_min_cin", None)
     if min_cin is None or not module.training or conv.in_channels < min_cin:
         return False
-    if not (isinstance(conv, nn.Conv2d) and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)):
+    geometry = SF.conv2d_square_geometry(conv)
+    if geometry is None or (conv.in_channels, conv.out_channels, geometry[2]) in TRAIN_ROUTING_EXCLUDED:
         return False
-    s, p, d = conv.stride, conv.padding, conv.dilation
-    if s[0] != s[1] or p[0] != p[1] or d[0] != d[1] or (conv.in_channels, conv.out_channels, d[0]) in TRAIN_ROUTING_EXCLUDED:
-        return False
-    return SF.conv3x3_train_supported(x, conv.weight, s[0], p[0], d[0], conv.groups)
+    return SF.conv3x3_train_supported(x, conv.weight, *geometry, conv.groups)
 
 
 def _train_conv(module, conv, x):
@@ -119,6 +117,15 @@ def _conv1x1_bn_eval(x, conv, bn, relu):
 def _conv3x3_split(x, conv):
     return (CONV3X3_SPLIT and conv.in_channels >= CONV3X3_SPLIT_MIN_CIN and not conv.training
             and SF.conv3x3_split_supported(x, conv))
+
+
+def _split_conv(x, conv, bn=None, activation="none", residual=None):
+    """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, for a call one of the
+    SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names)."""
+    pack = SF.conv3x3_pack_weights(conv)
+    if residual is not None:
+        return SF.conv3x3_split_res_eval(x, pack, conv.out_channels, conv.dilation[0], residual, bn, activation, conv.bias)
+    return SF.conv3x3_split_eval(x, pack, conv.out_channels, conv.dilation[0], conv.bias, bn, activation)
 
 
 class _ClassifierConvFn(torch.autograd.Function):
@@ -199,11 +206,7 @@ class BasicBlock(nn.Module):
         """relu(bn1(conv1(x))) and relu(bn2(conv2(.)) + residual) as one launch of csrc/conv3x3.hip each (BN + ReLU, and BN +
         residual + ReLU, in the epilogue) where _routed says so."""
         r1 = self._routed(x, self.conv1, False)
-        if r1:
-            out = SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(self.conv1), self.conv1.out_channels, self.conv1.dilation[0],
-                                        None, self.bn1, "relu")
-        else:
-            out = self.bn1.forward_relu(self.conv1(x))
+        out = _split_conv(x, self.conv1, self.bn1, "relu") if r1 else self.bn1.forward_relu(self.conv1(x))
         r2 = self._routed(out, self.conv2, True)
         if self.downsample is None:
             residual = x
@@ -215,8 +218,7 @@ class BasicBlock(nn.Module):
         else:
             residual = self.downsample(x)
         if r2:
-            return SF.conv3x3_split_res_eval(out, SF.conv3x3_pack_weights(self.conv2), self.conv2.out_channels,
-                                             self.conv2.dilation[0], residual, self.bn2, "relu")
+            return _split_conv(out, self.conv2, self.bn2, "relu", residual)
         return self.bn2.forward_relu(self.conv2(out), residual)
 
     def forward(self, x):
@@ -257,10 +259,8 @@ class Bottleneck(nn.Module):
                 out = _conv1x1_bn_eval(x, self.conv1, self.bn1, relu=True)
             else:
                 out = self.bn1.forward_relu(self.conv1(x))
-            if _conv3x3_split(out, self.conv2):    # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
-                c2 = SF.conv3x3_split_eval(out, SF.conv3x3_pack_weights(self.conv2), self.conv2.out_channels, self.conv2.dilation[0])
-            else:
-                c2 = self.conv2(out)
+            # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
+            c2 = _split_conv(out, self.conv2) if _conv3x3_split(out, self.conv2) else self.conv2(out)
             tail = (not self.training and _fused_tail(x) and SF.conv1x1_abn_supported(c2, self.conv3) and self.conv3.in_channels <= 512
                     and getattr(self.bn2, "activation", None) == "none" and getattr(self.bn3, "activation", None) == "none")
             if not tail:
@@ -405,9 +405,7 @@ class ResNet(nn.Module):
         conv, bn = self.dsn[0], self.dsn[1]
         if (not self.training and not torch.is_grad_enabled() and getattr(bn, "activation", None) in ("none", "relu", "leaky_relu")
                 and hasattr(bn, "running_mean") and _conv3x3_split(x3, conv)):
-            y = SF.conv3x3_split_eval(x3, SF.conv3x3_pack_weights(conv), conv.out_channels, conv.dilation[0], conv.bias, bn,
-                                      bn.activation)
-            return self.dsn[3](y)
+            return self.dsn[3](_split_conv(x3, conv, bn, bn.activation))
         if _train_routed(self, x3, conv):      # the training form: the same sequence with dsn[0] (bias in the epilogue) on the split core
             return self.dsn[3](self.dsn[2](bn(_train_conv(self, conv, x3))))
         return self.dsn(x3)
@@ -474,7 +472,10 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
     ``conv2 -> bn2 -> + residual -> relu`` as one launch each of the split-core 3x3 convolution (csrc/conv3x3.hip) wherever the
     kernel takes the convolution and it has at least ``min_cin`` input channels (FUSED_EVAL_MIN_CIN above); every other convolution,
     and every training forward or forward with a graph, is what it was.  So the flag may be set on a live student: the
-    packed weights are keyed on ``(data_ptr, _version)`` and rebuild themselves after each optimizer update.  The weights that
+    packed weights are keyed on ``(data_ptr, _version)`` and rebuild themselves after each optimizer update that advances the
+    version -- torch's FUSED optimizers do not, so the optimizer needs ``kd_model.advance_versions_after_step`` as a step post-hook
+    (NetModel registers it on the student's optimizer; a caller with a fused optimizer of their own must do so themselves), or
+    every evaluation behind the first runs on stale packs.  The weights that
     are routed and already on the device are packed here, so a graph captured later allocates nothing for them.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
     is set and changes nothing."""
@@ -483,9 +484,8 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
             continue
         if not enable:
             m._skd_infer_min_cin = None
-            for conv in (m.conv1, m.conv2):
-                if hasattr(conv, "_skd_conv3x3_pack"):
-                    del conv._skd_conv3x3_pack
+            SF.drop_conv3x3_packs(m.conv1)
+            SF.drop_conv3x3_packs(m.conv2)
             continue
         m._skd_infer_min_cin = int(min_cin)
         with torch.no_grad():
@@ -519,10 +519,8 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN):
         m._skd_train_min_cin = int(min_cin) if enable else None
         if enable:
             continue
-        convs = (m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0],) if isinstance(m, ResNet) else ()
-        for conv in convs:
-            if hasattr(conv, "_skd_conv3x3_train_pack"):
-                del conv._skd_conv3x3_train_pack
-        if isinstance(m, PSPModule):
-            getattr(m, "_fold_cache", {}).pop("pack3x3_train", None)
+        owners = ((m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0],) if isinstance(m, ResNet)
+                  else (getattr(m, "_fold_cache", {}),))
+        for owner in owners:
+            SF.drop_conv3x3_packs(owner)
     return model

@@ -85,6 +85,60 @@ def test_pack_cache_follows_the_weight():
         _lib.install_test_backend(None)
 
 
+# The three forms of functional._conv3x3_ok: which grad state, which entries, whether host tensors pass under a double.
+#   frozen      grad off   skd_conv3x3_split_nhwc                                              host tensors refused
+#   inference   grad off   skd_conv3x3_split_[res_]nhwc + skd_conv3x3_split_supported          host tensors pass
+#   training    grad on    skd_conv3x3_split_train_supported, _pack_pair, skd_conv3x3_split_nhwc   host tensors pass
+@pytest.mark.parametrize("form", ["frozen", "inference", "inference-residual", "training"])
+def test_predicate_table(form):
+    """Every public predicate on a host map and a 128 -> 128 convolution the kernel takes, under the back-ends the other test
+    files define: the plain-C double (no 3x3 entry), Conv3x3Double (the frozen and inference entries) and TrainDouble (all)."""
+    from test_conv3x3_train_cpu import TrainDouble
+    from test_student_infer_cpu import Conv3x3Double
+    conv = torch.nn.Conv2d(128, 128, 3, 1, 2, 2, bias=False)
+    x = torch.zeros(1, 128, 4, 4).contiguous(memory_format=torch.channels_last)
+    ask = {"frozen": lambda t, c: SF.conv3x3_split_supported(t, c),
+           "inference": lambda t, c: SF.conv3x3_infer_supported(t, c),
+           "inference-residual": lambda t, c: SF.conv3x3_infer_supported(t, c, residual=True),
+           "training": lambda t, c: SF.conv3x3_train_supported(t, c.weight, c.stride[0], c.padding[0], c.dilation[0], c.groups)}[form]
+    need_grad, host_ok = form == "training", form != "frozen"
+    core = cref.load(_lib.SIGNATURES)
+    backends = {"plain-C": (core, False), "infer": (Conv3x3Double(core, False), form != "training"),
+                "train": (TrainDouble(core, False), True)}
+    try:
+        for name, (backend, has_entries) in backends.items():
+            _lib.install_test_backend(backend)
+            for grad in (False, True):
+                with torch.set_grad_enabled(grad):
+                    assert ask(x, conv) is (host_ok and has_entries and grad == need_grad), (form, name, grad)
+        # under the back-end that has every entry, in the grad state the form wants: what the tensor checks refuse
+        with torch.set_grad_enabled(need_grad):
+            assert ask(x, conv) is host_ok
+            assert not ask(x.contiguous(), conv) and not ask(x.double(), conv.double()) and not ask(x[0], conv)
+            assert not ask(torch.zeros(1, 64, 4, 4).contiguous(memory_format=torch.channels_last), conv)       # x.shape[1] != Cin
+            off = torch.zeros(4 * 4 * 128 + 1)[1:].view(1, 4, 4, 128).permute(0, 3, 1, 2)                       # not 16-byte aligned
+            assert off.is_contiguous(memory_format=torch.channels_last) and off.data_ptr() % 16 and not ask(off, conv)
+            assert not ask(x, torch.nn.Conv2d(128, 128, 3, 2, 1, bias=False))                                  # the library's query
+            assert not ask(x, torch.nn.Conv2d(128, 64, 3, 1, 1, bias=False))
+            if form != "training":      # the module forms: a plain square zero-padded Conv2d only
+                assert not ask(x, torch.nn.Conv2d(128, 128, 3, 1, (1, 2), (1, 2), bias=False))
+                assert not ask(x, torch.nn.Conv2d(128, 128, 3, 1, "same", bias=False))
+                assert not ask(x, torch.nn.Conv2d(128, 128, 3, 1, 1, padding_mode="reflect", bias=False))
+    finally:
+        _lib.install_test_backend(None)
+    for grad in (False, True):          # no double: a host tensor is nobody's
+        with torch.set_grad_enabled(grad):
+            assert not ask(x, conv)
+
+
+def test_conv2d_square_geometry():
+    assert SF.conv2d_square_geometry(torch.nn.Conv2d(8, 8, 3, 1, 2, 2)) == (1, 2, 2)
+    assert SF.conv2d_square_geometry(torch.nn.Conv2d(8, 8, 3, (2, 2), (1, 1))) == (2, 1, 1)
+    for bad in (torch.nn.Conv2d(8, 8, 3, (1, 2), 1), torch.nn.Conv2d(8, 8, 3, 1, (1, 0)), torch.nn.Conv2d(8, 8, 3, 1, 2, (2, 1)),
+                torch.nn.Conv2d(8, 8, 3, 1, "same"), torch.nn.Conv2d(8, 8, 3, 1, 1, padding_mode="circular"), torch.nn.ReLU()):
+        assert SF.conv2d_square_geometry(bad) is None
+
+
 def test_header_table_and_library_agree_on_the_new_names():
     protos = _lib.header_prototypes(_lib.EXT_HEADER_PATH)
     for name in NAMES:

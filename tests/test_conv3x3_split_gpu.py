@@ -219,6 +219,30 @@ def test_functional_path_matches_the_entry(hip):
     assert torch.equal(got.cpu(), want)
 
 
+def test_fused_sgd_step_rebuilds_the_eval_pack():
+    """torch's fused SGD writes the weight without advancing ``_version``, the key of the pack; with the step post-hook NetModel
+    registers, the pack fetched behind a step is that of the new weight."""
+    from structure_knowledge_distillation_amd import functional as SF
+    from structure_knowledge_distillation_amd.networks.kd_model import advance_versions_after_step
+    torch.manual_seed(21)
+    conv = torch.nn.Conv2d(16, 128, 3, 1, 1).to(DEV)
+    x = torch.randn(1, 16, 5, 7, device=DEV).contiguous(memory_format=torch.channels_last)
+    opt = torch.optim.SGD(conv.parameters(), 0.5, fused=True)
+    opt.register_step_post_hook(advance_versions_after_step)
+    with torch.no_grad():
+        before = SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv), 128, 1, conv.bias)
+    for p in conv.parameters():
+        p.grad = torch.ones_like(p)
+    version = conv.weight._version
+    opt.step()
+    assert conv.weight._version > version
+    with torch.no_grad():
+        got = SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv), 128, 1, conv.bias)
+        fresh = SF.conv3x3_pack_weights(None, conv.weight.detach().clone(), torch.nn.Module())
+        want = SF.conv3x3_split_eval(x, fresh, 128, 1, conv.bias)
+    assert torch.equal(got, want) and not torch.equal(got, before)
+
+
 def test_host_refusals(hip):
     """Refused on the host, before any launch."""
     sup = hip.skd_conv3x3_split_supported

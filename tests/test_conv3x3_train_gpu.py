@@ -123,28 +123,55 @@ def _weight_view(A, wt, layout):
     return A.inp("w", wide)[:, 64:]
 
 
+def pack_image(wt):
+    """The packed image of a (N, C, 3, 3) fp32 weight as torch computes it on the CPU, from the layout comments of
+    csrc/conv_split_dev.hpp and csrc/conv3x3.hip alone: per (column tile tn of 128 rows, K-tile kt of 16 k), tile index
+    tn * nk + kt with nk = 9 C / 16, three planes of 256 16-byte chunks; chunk kh * 128 + (row ^ 4 kh) holds the 8 bf16 of
+    k = 16 kt + 8 kh + i in ascending i, k = tap * C + c, tap = 3 ty + tx; plane j is piece p_j of v = p0 + p1 + p2,
+    p0 = bf16(v), p1 = bf16(v - p0), p2 = bf16(v - p0 - p1), each rounded to nearest even (torch's fp32 -> bf16 cast)."""
+    n, c = wt.shape[:2]
+    m = wt.permute(0, 2, 3, 1).reshape(n // 128, 128, 9 * c // 16, 2, 8).permute(0, 2, 3, 1, 4)     # (tn, kt, kh, row, i)
+    m = torch.stack([m[:, :, 0], m[:, :, 1][:, :, torch.arange(128) ^ 4]], 2).contiguous()          # chunk row' = row ^ 4 kh
+    planes = []
+    for _ in range(3):
+        piece = m.bfloat16()
+        planes.append(piece.view(torch.int16))
+        m = m - piece.float()
+    return torch.stack(planes, 2).contiguous().view(torch.uint8).reshape(-1)                        # (tn, kt, plane, chunk, i)
+
+
 @pytest.mark.parametrize("layout", ["contiguous", "channels_last", "slice"])
-@pytest.mark.parametrize("cout,cin", [(128, 128), (256, 128), (128, 256)])
+@pytest.mark.parametrize("cout,cin", [(128, 16), (256, 32), (128, 128), (256, 128), (128, 256)])
 def test_pack_pair_bits(hip, cout, cin, layout):
+    """Both pack entries against pack_image, the torch-on-CPU reference (neither entry is the other's truth: they share one
+    kernel).  The backward image is the same function of Wd[c][n][ty][tx] = W[n][c][2 - ty][2 - tx]; it needs Cout a multiple of
+    16 and Cin of 128, so the narrow cases take the forward forms only."""
     g = torch.Generator().manual_seed(cout + 3 * cin)
     wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
     wt[0, 0, 0, 1], wt[1, 2, 2, 0] = 1e-30, -3.0e4                 # a tiny and a large value: the residual pieces
-    wd = wt.flip(2, 3).transpose(0, 1).contiguous()
-    want_f, want_b = T3.pack(hip, wt.to(DEV)), T3.pack(hip, wd.to(DEV))
     nbytes = cout * cin * 54
-    assert want_f.numel() == want_b.numel() == nbytes == hip.skd_conv3x3_split_pack_bytes(cin, cout) == hip.skd_conv3x3_split_pack_bytes(cout, cin)
-    assert not torch.equal(want_f, want_b)
-    for fwd, bwd in ((True, True), (True, False), (False, True)):
+    want_f = pack_image(wt).to(DEV)
+    assert want_f.numel() == nbytes == hip.skd_conv3x3_split_pack_bytes(cin, cout)
+    forms = [("weights", True, False), ("pair", True, False)]
+    want_b = None
+    if cin % 128 == 0:
+        want_b = pack_image(wt.flip(2, 3).transpose(0, 1).contiguous()).to(DEV)
+        assert want_b.numel() == nbytes == hip.skd_conv3x3_split_pack_bytes(cout, cin) and not torch.equal(want_f, want_b)
+        forms += [("pair", True, True), ("pair", False, True)]
+    for entry, fwd, bwd in forms:
         A = BC.Arena(DEV)
         w = _weight_view(A, wt, layout)
         assert tuple(w.shape) == (cout, cin, 3, 3) and (layout == "contiguous") == w.is_contiguous()
         pf, pb = A.out("pack_fwd", nbytes, torch.uint8), A.out("pack_bwd", nbytes, torch.uint8)
         sn, sc, sy, sx = w.stride()
-        assert hip.skd_conv3x3_split_pack_pair(cin, cout, P(w), sn, sc, sy, sx, P(pf) if fwd else None, nbytes,
-                                               P(pb) if bwd else None, nbytes, None)
+        if entry == "weights":
+            assert hip.skd_conv3x3_split_pack_weights(cin, cout, P(w), sn, sc, sy, sx, P(pf), nbytes, None)
+        else:
+            assert hip.skd_conv3x3_split_pack_pair(cin, cout, P(w), sn, sc, sy, sx, P(pf) if fwd else None, nbytes,
+                                                   P(pb) if bwd else None, nbytes, None)
         A.check()
-        assert torch.equal(pf, want_f) if fwd else bool((pf == BC.FILL).all()), (layout, fwd, bwd)
-        assert torch.equal(pb, want_b) if bwd else bool((pb == BC.FILL).all()), (layout, fwd, bwd)
+        assert torch.equal(pf, want_f) if fwd else bool((pf == BC.FILL).all()), (layout, entry, fwd, bwd)
+        assert torch.equal(pb, want_b) if bwd else bool((pb == BC.FILL).all()), (layout, entry, fwd, bwd)
 
 
 def test_pack_pair_refusals_leave_the_buffers_alone(hip):
