@@ -17,6 +17,7 @@ MS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval
 OHEM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_ohem.h"))
 INFER_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_infer.h"))
 TRAIN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_train.h"))
+WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_wgrad.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -186,6 +187,16 @@ TRAIN_SIGNATURES = {
     "skd_conv3x3_split_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
 }
 
+# Entry points declared in include/skd_wgrad.h (csrc/conv3x3_wgrad.hip): the weight gradient of those convolutions on the split
+# core, extension entries in a table of their own like the four above (tests/test_conv3x3_wgrad_cpu.py checks header <-> table
+# <-> exported symbols, tests/test_conv3x3_wgrad_gpu.py holds the guard-band cases).  A back-end without them leaves the weight
+# gradients on the library: nothing raises.
+WGRAD_SIGNATURES = {
+    "skd_conv3x3_split_wgrad_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "skd_conv3x3_split_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "skd_conv3x3_split_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -215,7 +226,8 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES):
+    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
+                  WGRAD_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -1,0 +1,321 @@
+// conv3x3_wgrad.hip -- the WEIGHT GRADIENT of a 3x3, stride-1, "same" (padding = dilation) convolution on the split-operand
+// bf16-MFMA core of conv_split_dev.hpp (see conv1x1.hip for the core, conv3x3.hip for forward and data gradient): fp32 in, fp32 out.
+//
+//     dW[n][c][ty][tx] = sum_{m = (b, y, x)} g[m][n] * X[b, y + (ty - 1) d, x + (tx - 1) d, c]      (0 outside the image)
+//
+// with channels-last x (B, H, W, Cin) and g (B, H, W, Cout): nine GEMMs (Cout x P) (P x Cin), one per tap, reduced over the
+// P = B H W pixels.  On the core: operand A rows = 128 output channels of g, operand B rows = 128 input channels of the shifted
+// x, K = the pixel index in K-tiles of 16 pixels; tile_mma<128> with its two accumulator sets, k_loop<2> and store_block as they are.
+// One workgroup computes one (tap, n-tile, c-tile, K-slice) and writes a 128 x 128 fp32 block of the workspace
+// part[slice][n][tap][c]; conv3x3_wgrad_reduce_kernel sums the slices in the order 0 .. S - 1 (no atomics: the same bits every
+// time) and writes dW through the destination's strides.
+//
+// Staging -- the part that is this kernel's own.  Memory is [pixel][channel]; the LDS image wants eight consecutive k (= pixels)
+// of one row (= channel) in one chunk, so BOTH operands are transposed on the way in and BOTH are split in the loop (there is no
+// frozen pack to stream).  Waves 0, 1 stage g, waves 2, 3 stage x.  A thread owns (channel quad r, pixel quad q): four float4
+// loads at pixels 4 q .. 4 q + 3, channels 4 r .. 4 r + 3 (the forward's load count), a 4 x 4 transposition in registers, and one
+// split_store per channel row at plane_slot(row, 4 q) (twice the forward's split work).
+//
+// Bank conflicts of those stores (ds_write_b64: 16 consecutive lanes per LDS cycle, bank pair = 8-byte slot mod 16):
+//     slot(row, q) mod 16 = 2 ((row mod 8) ^ 4 (q >> 1)) + (q & 1).
+// With lanes running over r and every lane storing row 4 r + j in its j-th store, row mod 8 takes two values in a lane group
+// (4 (r & 1) + j) and q none: EIGHT-way.  So which lane owns which row is changed, not the image: within the 16 lanes of a group,
+// bits 0-2 of the lane are bits 0-2 of r and bit 3 is bit 0 of q, and the j-th store of a lane writes row 4 r + (j ^ s) with
+// s = (r >> 1) & 3 (the four channels of a load are permuted by XOR with s before the transposition: 8 v_cndmask per load).
+// Then (row mod 8, q & 1) takes all sixteen values in a group: conflict-free.  A load instruction of a wave still covers whole
+// pixels: two pixels x 32 channel quads = 2 x 512 contiguous bytes.
+//
+// Shifted operand: x row k = pixel m is read at m + shift(tap) when the shifted pixel stays inside ITS image and m < P, and is an
+// exact zero with no load issued otherwise (as stage_load3_a); g rows beyond P are zeros.  (y, x) of the first pixel of a
+// thread's quad come from one division pair per K-tile (multiply-high by a host-made reciprocal, one correction), the other three
+// pixels by stepping: a quad may straddle a row end or an image end, validity is per pixel.
+//
+// Grid: id -> (XCD = id & 7, j = id >> 3); the workgroups of one XCD take consecutive logical indices, and a logical index is
+// ((slice * tiles_n + tn) * tiles_c + tc) * 9 + tap: the nine taps of one (slice, n-tile, c-tile) are neighbours on ONE XCD and
+// read the same pixels of g and (shifted by at most d rows) of x from that L2.  -DSKD_WGRAD_GRID_ORDER=1 builds the other order
+// for measurements (logical index = blockIdx.x: neighbours land on eight different XCDs); tools/conv3x3_wgrad_bench.py --lib times
+// such a build beside the shipped one.
+#include "conv_split_dev.hpp"
+#include "skd_wgrad.h"
+
+#ifndef SKD_WGRAD_GRID_ORDER
+#define SKD_WGRAD_GRID_ORDER 0
+#endif
+
+namespace skd {
+namespace {
+
+constexpr int kWgDepth = 2;                            // K-tiles of load look-ahead (k_loop)
+constexpr int kMaxPixels = 1 << 30;                    // P below this: pixel arithmetic in 32 bits, dilation included
+constexpr int kMaxDilation = 1 << 24;
+
+struct StagingW {
+  float4 v[4];                                         // pixels 4 q .. 4 q + 3, channels 4 r .. 4 r + 3
+};
+
+// n / d and n % d for n < 2^31 with rcp = floor(2^32 / d) (2^32 - 1 for d = 1): the multiply-high is the quotient or one short.
+__device__ __forceinline__ void divmod(unsigned n, unsigned d, unsigned rcp, unsigned &q, unsigned &r) {
+  q = __umulhi(n, rcp);
+  r = n - q * d;
+  if (r >= d) {
+    ++q;
+    r -= d;
+  }
+}
+
+struct TileW {
+  typedef StagingW Stg;
+  const float *__restrict__ src;      // g or x, at the thread's first channel
+  int64_t shift;                      // the tap's pixel shift (0 for g)
+  int C;                              // floats per pixel of src
+  int P, H, W, hw;
+  unsigned rcp_hw, rcp_w;
+  int dy, dx;                         // the tap's (ty - 1) d, (tx - 1) d
+  int m_first;                        // first pixel of this thread's quad in K-tile 0 of the slice
+  bool is_x;                          // wave-uniform
+  int s;                              // channel permutation of this lane
+  int slot[4];                        // 8-byte LDS slot of the j-th stored row, the operand's offset included
+  f32x16 (&low)[2][2], (&acc)[2][2];
+
+  __device__ __forceinline__ void load(Stg &st, int kt) const {
+    const int m0 = m_first + kt * kBK;
+    unsigned y = 0, x = 0;
+    if (is_x) {
+      unsigned img, pix;
+      divmod((unsigned)m0, (unsigned)hw, rcp_hw, img, pix);
+      divmod(pix, (unsigned)W, rcp_w, y, x);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // unsigned compares: a negative shifted coordinate is a large one
+      const bool live = m0 + i < P && (unsigned)((int)y + dy) < (unsigned)H && (unsigned)((int)x + dx) < (unsigned)W;
+      st.v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (live) st.v[i] = *reinterpret_cast<const float4 *>(src + ((int64_t)(m0 + i) + shift) * C);
+      // the next pixel: one step, across a row end and an image end
+      ++x;
+      if (x == (unsigned)W) {
+        x = 0;
+        ++y;
+        if (y == (unsigned)H) y = 0;
+      }
+    }
+  }
+  __device__ __forceinline__ void store(const Stg &st, uint4 *stage, int) const {
+    float p[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float4 v = st.v[i];
+      // component j of the permuted load = channel j ^ s
+      const float a0 = (s & 1) ? v.y : v.x, a1 = (s & 1) ? v.x : v.y, a2 = (s & 1) ? v.w : v.z, a3 = (s & 1) ? v.z : v.w;
+      p[i][0] = (s & 2) ? a2 : a0;
+      p[i][1] = (s & 2) ? a3 : a1;
+      p[i][2] = (s & 2) ? a0 : a2;
+      p[i][3] = (s & 2) ? a1 : a3;
+    }
+    uint2 *base = reinterpret_cast<uint2 *>(stage);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) split_store(make_float4(p[0][j], p[1][j], p[2][j], p[3][j]), base + slot[j]);
+  }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<kTM>(stage, low, acc); }
+};
+
+// 128 accumulator registers, two staging sets: two workgroups per CU like the TALL forward (profiles/r20_kernel_resources.md).
+__global__ __launch_bounds__(kThreads, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ part, int P, int H, int W,
+                          int Cin, int Cout, int dil, int nk, int tiles_per_slice, int slices, unsigned rcp_hw, unsigned rcp_w,
+                          int total) {
+  extern __shared__ __attribute__((aligned(16))) uint4 lds[];
+  const int per_xcd = (int)(gridDim.x >> 3);
+  const int id = SKD_WGRAD_GRID_ORDER == 1 ? (int)blockIdx.x : (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+  if (id >= total) return;
+  const int tiles_c = Cin / kTN, tiles_n = Cout / kTM;
+  const int tap = id % 9;
+  int rest = id / 9;
+  const int tc = rest % tiles_c;
+  rest /= tiles_c;
+  const int tn = rest % tiles_n, slice = rest / tiles_n;
+  const int ty = tap / 3, tx = tap - 3 * ty;
+  const int kt0 = slice * tiles_per_slice;
+  const int nks = min(tiles_per_slice, nk - kt0);          // >= 1: the plan leaves no slice empty
+
+  f32x16 acc[2][2], low[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[i][j][q] = low[i][j][q] = 0.f;
+
+  // the thread's place in the staging of its operand: l = 0 .. 127 inside the operand's two waves
+  const int l = threadIdx.x & 127;
+  const bool is_x = threadIdx.x >= 128;
+  const int r = (l & 7) | (((l >> 4) & 3) << 3);           // channel quad 0 .. 31
+  const int q = ((l >> 3) & 1) | (((l >> 6) & 1) << 1);    // pixel quad 0 .. 3
+  const int s = (r >> 1) & 3;
+  const int C = is_x ? Cin : Cout;
+  const float *src = (is_x ? X + tc * kTN : G + tn * kTM) + 4 * r;
+  TileW tile = {src,
+                is_x ? ((int64_t)(ty - 1) * W + (tx - 1)) * dil : 0,
+                C, P, H, W, H * W, rcp_hw, rcp_w,
+                is_x ? (ty - 1) * dil : 0, is_x ? (tx - 1) * dil : 0,
+                kt0 * kBK + 4 * q, is_x, s, {}, low, acc};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) tile.slot[j] = (is_x ? 2 * kOperandChunks : 0) + plane_slot(4 * r + (j ^ s), 4 * q);
+  k_loop<kWgDepth>(tile, nks, lds);
+
+  // ---- epilogue: the slice's 128 x 128 block of part[slice][n][tap][c], every element written ----
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  const int wi = (wid >> 1) * (kTM / 2), wj = (wid & 1) * 64;
+  float *slab = part + (int64_t)slice * 9 * Cin * Cout;
+#pragma unroll
+  for (int bj = 0; bj < 2; ++bj) {
+    const int col = tap * Cin + tc * kTN + wj + bj * 32 + (lane & 31);
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[bi][bj][e] += low[bi][bj][e];
+      store_block<SKD_ACT_NONE, false, true, false>(acc[bi][bj], nullptr, slab, (int64_t)tn * kTM + wi + bi * 32, col, Cout, 9 * Cin,
+                                                    0.f, 1.f, 1.f, 0.f, 0.f);
+    }
+  }
+}
+
+// dw[n][c][ty][tx] = sum over the slices, in slice order, of part[slice][n][tap][c]; one thread per four consecutive c.
+// VEC: the destination takes the four as one 16-byte store (unit channel stride, everything else a multiple of four floats):
+// for a dense channels-last weight the whole kernel is a streaming sum.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void conv3x3_wgrad_reduce_kernel(const float *__restrict__ part, float *__restrict__ dw,
+                                                                        int Cin, int64_t quads, int64_t slab, int slices,
+                                                                        int64_t sn, int64_t sc, int64_t sy, int64_t sx) {
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= quads) return;
+  const int64_t e = 4 * t;
+  const float4 *p = reinterpret_cast<const float4 *>(part + e);
+  const int64_t step = slab / 4;
+  float4 sum = p[0];
+  int sl = 1;
+  for (; sl + 3 < slices; sl += 4) {               // four loads in flight, added in slice order
+    const float4 a = p[sl * step], b = p[(sl + 1) * step], c = p[(sl + 2) * step], d = p[(sl + 3) * step];
+    sum.x += a.x; sum.y += a.y; sum.z += a.z; sum.w += a.w;
+    sum.x += b.x; sum.y += b.y; sum.z += b.z; sum.w += b.w;
+    sum.x += c.x; sum.y += c.y; sum.z += c.z; sum.w += c.w;
+    sum.x += d.x; sum.y += d.y; sum.z += d.z; sum.w += d.w;
+  }
+  for (; sl < slices; ++sl) {
+    const float4 a = p[sl * step];
+    sum.x += a.x; sum.y += a.y; sum.z += a.z; sum.w += a.w;
+  }
+  const int64_t row = 9 * (int64_t)Cin;
+  const int64_t n = e / row;
+  const int rem = (int)(e - n * row);
+  const int tap = rem / Cin, c = rem - tap * Cin;
+  const int ty = tap / 3, tx = tap - 3 * ty;
+  float *dst = dw + n * sn + ty * sy + tx * sx + c * sc;
+  if (VEC) {
+    *reinterpret_cast<float4 *>(dst) = sum;
+  } else {
+    dst[0] = sum.x;
+    dst[sc] = sum.y;
+    dst[2 * sc] = sum.z;
+    dst[3 * sc] = sum.w;
+  }
+}
+
+unsigned reciprocal32(unsigned d) { return d == 1 ? 0xffffffffu : (unsigned)((1ull << 32) / d); }
+
+// Slices asked for -> the slices of an exact cover: T = ceil(nk / S) K-tiles each, and as many slices as that T needs.
+void cover(int64_t nk, int64_t slices, int64_t &used, int64_t &per_slice) {
+  if (slices > nk) slices = nk;
+  per_slice = cdiv(nk, slices);
+  used = cdiv(nk, per_slice);
+}
+
+}  // namespace
+}  // namespace skd
+
+using namespace skd;
+
+extern "C" {
+
+int skd_conv3x3_split_wgrad_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return Cin > 0 && Cout > 0 && Cin % kTN == 0 && Cout % kTM == 0 && stride == 1 && dilation >= 1 && padding == dilation && groups == 1;
+}
+
+// The shipped rule for slices == 0.  A launch of tiles * S workgroups takes ceil(tiles * S / slots) rounds of the device's
+// slots = 2 * cus two-per-CU places, each round as long as a slice: ceil(nk / S) K-tiles.  S is the count in 1 .. max(1, 2 slots /
+// tiles) (at most two rounds: the workspace and the reduce launch grow with S) with the smallest rounds * K-tiles-per-slice, the
+// smaller count on a tie.  Measured at batch 8, 65 x 65 on 256 CUs (profiles/r20_conv3x3_wgrad_isolated.md): 128 -> 128 (9 tiles)
+// 56 slices, 256 -> 256 (36) 14, 256 -> 512 (72) 7 -- one full round each, the counts on either side are slower -- and 512 -> 512
+// (144 tiles) 7 slices = 1008 workgroups in two rounds, 10 % ahead of the 3 slices of a single, 84 % full round and 26 % ahead of
+// 4 slices (one round and an eighth).
+int skd_conv3x3_split_wgrad_plan(int B, int H, int W, int Cin, int Cout, int slices, int cus, int64_t *plan) {
+  if (!plan || B < 1 || H < 1 || W < 1 || slices < 0 || cus < 0) return 0;
+  if (!skd_conv3x3_split_wgrad_supported(Cin, Cout, 1, 1, 1, 1)) return 0;
+  const int64_t P = (int64_t)B * H * W;
+  if (P >= kMaxPixels) return 0;
+  const int64_t nk = cdiv(P, kBK);
+  int64_t want = slices;
+  if (want == 0) {
+    const int64_t tiles = 9 * (int64_t)(Cin / kTN) * (Cout / kTM), slots = 2 * (int64_t)(cus > 0 ? cus : 256);
+    int64_t most = 2 * slots / tiles, best = 0;
+    if (most < 1) most = 1;
+    if (most > nk) most = nk;
+    for (int64_t s = 1; s <= most; ++s) {
+      const int64_t cost = cdiv(tiles * s, slots) * cdiv(nk, s);
+      if (want == 0 || cost < best) {
+        want = s;
+        best = cost;
+      }
+    }
+  }
+  int64_t used, per_slice;
+  cover(nk, want, used, per_slice);
+  plan[0] = used;
+  plan[1] = per_slice;
+  plan[2] = used * 9 * Cin * Cout * (int64_t)sizeof(float);
+  return 1;
+}
+
+int skd_conv3x3_split_wgrad_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const float *g, float *dw,
+                                 int64_t sn, int64_t sc, int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes,
+                                 int slices, skd_stream_t stream) {
+  if (!x || !g || !dw || !workspace || B < 1 || H < 1 || W < 1) return 0;
+  if (dilation < 1 || dilation > kMaxDilation || !skd_conv3x3_split_wgrad_supported(Cin, Cout, 1, dilation, dilation, 1)) return 0;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(workspace)) & 15) return 0;
+  if (sn < 0 || sc < 0 || sy < 0 || sx < 0) return 0;
+  const int64_t P = (int64_t)B * H * W;
+  if (P >= kMaxPixels) return 0;
+  const int64_t nk = cdiv(P, kBK);
+  if (slices < 1 || slices > nk) return 0;
+  int64_t used, per_slice;
+  cover(nk, slices, used, per_slice);
+  if (used != slices) return 0;                              // not a count the plan returns: geometry is decided there
+  const int64_t slab = 9 * (int64_t)Cin * Cout;
+  if (workspace_bytes < used * slab * (int64_t)sizeof(float)) return 0;
+  const int64_t total = 9 * (int64_t)(Cin / kTN) * (Cout / kTM) * used;
+  const int64_t grid = cdiv(total, 8) * 8;
+  const int64_t quads = slab / 4, rgrid = cdiv(quads, kThreads);
+  if (grid > 2147483647 || rgrid > 2147483647) return 0;
+  static PerDeviceFlag ready;
+  bool *rdy = ready.get();
+  if (rdy == nullptr) return 0;
+  if (!*rdy) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kConvLds) != hipSuccess) return 0;
+    *rdy = true;
+  }
+  hipStream_t st = as_stream(stream);
+  float *part = static_cast<float *>(workspace);
+  conv3x3_wgrad_kernel<<<dim3((unsigned)grid), dim3(kThreads), kConvLds, st>>>(
+      x, g, part, (int)P, H, W, Cin, Cout, dilation, (int)nk, (int)per_slice, (int)used, reciprocal32((unsigned)(H * W)),
+      reciprocal32((unsigned)W), (int)total);
+  if (!ok()) return 0;
+  const bool vec = sc == 1 && (sn | sy | sx) % 4 == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0;
+  if (vec)
+    conv3x3_wgrad_reduce_kernel<true><<<dim3((unsigned)rgrid), dim3(kThreads), 0, st>>>(part, dw, Cin, quads, slab, (int)used, sn, sc, sy, sx);
+  else
+    conv3x3_wgrad_reduce_kernel<false><<<dim3((unsigned)rgrid), dim3(kThreads), 0, st>>>(part, dw, Cin, quads, slab, (int)used, sn, sc, sy, sx);
+  return ok();
+}
+
+}  // extern "C"

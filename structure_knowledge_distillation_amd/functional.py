@@ -460,7 +460,7 @@ def ppm_fold_supported(feats, sizes):
         and _is_cl(feats) and 3 * sum(sizes) <= 64 and len(sizes) <= 4
 
 
-def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False):
+def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False):
     """conv3x3(cat([upsample(p) for p in priors] + [feats], 1), weight, padding=1) (pspnet_combine.py:104-111) without
     the concatenated tensor and without convolving the priors' channels: the feature-map slice of the weight goes through
     the convolution, the priors through a (B s^2) x Cm x 9 Cout GEMM each and the fold kernel (csrc/ppm.hip).
@@ -468,7 +468,8 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
     `cache` (a dict) keeps the rearranged weight slices of a frozen network between calls.  `split3x3`: run the feature-map
     convolution on csrc/conv3x3.hip when conv3x3_split_supported-style conditions hold (no grad; weights packed once in `cache`).
     `split_train`: the same for a network in training, where conv3x3_train_supported says so (conv3x3_split_train on the strided
-    slice of the weight, so that autograd carries its gradient back into the full weight; packs once per weight version in `cache`)."""
+    slice of the weight, so that autograd carries its gradient back into the full weight; packs once per weight version in `cache`).
+    `split_wgrad`: with `split_train`, the weight gradient of that slice on the split core too (conv3x3_split_train's ``wgrad``)."""
     import torch.nn.functional as F
     cm = priors[0].shape[1]
     n_prior = len(priors) * cm
@@ -485,7 +486,8 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
     frozen = not train and not (torch.is_grad_enabled() and weight.requires_grad)
     wf, w_all = _cached(cache if frozen else None, "mats", _version_key((weight,), tuple(weight.shape)), mats)
     if train:
-        base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}))
+        extra = dict(wgrad=True) if split_wgrad else {}
+        base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}), **extra)
     elif split3x3 and cache is not None and _conv3x3_ok(feats, weight[:, n_prior:], 1, 1, 1, 1, **_FROZEN):
         base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3", {})), cout)
     else:
@@ -885,17 +887,81 @@ def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None):
     return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias)
 
 
+_WGRAD_ENTRIES = ("skd_conv3x3_split_wgrad_supported", "skd_conv3x3_split_wgrad_plan", "skd_conv3x3_split_wgrad_nhwc")
+_device_cus = {}
+
+
+def conv3x3_wgrad_supported(x, weight, stride, padding, dilation, groups):
+    """True when conv3x3_split_wgrad takes the weight gradient of ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)``:
+    a back-end that has the three entries of include/skd_wgrad.h (the tests' C double does not: the gradient then comes from the
+    library, as before) and everything conv3x3_train_supported asks."""
+    return (all(_lib.has_entry(n) for n in _WGRAD_ENTRIES) and conv3x3_train_supported(x, weight, stride, padding, dilation, groups)
+            and bool(_lib.get().skd_conv3x3_split_wgrad_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride),
+                                                                  int(padding), int(dilation), int(groups))))
+
+
+def _cus_of(device):
+    """Compute units of ``device``, looked up once per device (0 -- the plan's default -- for a host tensor under a test double)."""
+    if device.type != "cuda":
+        return 0
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _device_cus:
+        _device_cus[key] = int(torch.cuda.get_device_properties(key).multi_processor_count)
+    return _device_cus[key]
+
+
+def _non_overlapping_and_dense(t):
+    """Whether the elements of ``t`` fill a block of memory exactly once, in whatever dimension order."""
+    want = 1
+    for size, stride in sorted(((int(n), int(s)) for n, s in zip(t.shape, t.stride()) if n != 1), key=lambda p: p[1]):
+        if stride != want:
+            return False
+        want *= size
+    return True
+
+
+def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
+    """The weight gradient of the same-size 3x3 convolution ``F.conv2d(x, w, None, 1, dilation, dilation)`` for the output gradient
+    ``g``, on the split core (csrc/conv3x3_wgrad.hip: both operands split in the loop, split-K over the pixels into a workspace,
+    a second launch that sums the slices in a fixed order -- the same bits on every call).  ``x`` (B, Cin, H, W) and ``g``
+    (B, Cout, H, W): fp32, channels-last, 16-byte aligned.  ``weight_like`` gives shape, device and layout of the result: its own
+    strides when it is non-overlapping and dense, channels-last otherwise (a channel slice of a wider weight).  ``slices``: 0 =
+    the plan's choice for the tensor's device."""
+    _lib.require_device(x, g)
+    lib = _lib.get()
+    b, cin, h, w = (int(v) for v in x.shape)
+    cout = int(g.shape[1])
+    if tuple(weight_like.shape) != (cout, cin, 3, 3) or tuple(g.shape) != (b, cout, h, w):
+        raise ValueError("conv3x3_split_wgrad: x %s, g %s, weight %s" % (tuple(x.shape), tuple(g.shape), tuple(weight_like.shape)))
+    if not (_fp32_cl_map(x, True) and _fp32_cl_map(g, True)):
+        raise ValueError("conv3x3_split_wgrad: fp32 channels-last maps expected")
+    plan = (ctypes.c_int64 * 3)()
+    _lib.check(lib.skd_conv3x3_split_wgrad_plan(b, h, w, cin, cout, int(slices), _cus_of(x.device),
+                                                ctypes.cast(plan, ctypes.c_void_p)), "skd_conv3x3_split_wgrad_plan")
+    ws = torch.empty((int(plan[2]),), dtype=torch.uint8, device=x.device)
+    if _non_overlapping_and_dense(weight_like):
+        dw = torch.empty_strided(tuple(weight_like.shape), tuple(weight_like.stride()), dtype=torch.float32, device=x.device)
+    else:
+        dw = torch.empty(tuple(weight_like.shape), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _lib.check(lib.skd_conv3x3_split_wgrad_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), g.data_ptr(), dw.data_ptr(),
+                                                *(int(v) for v in dw.stride()), ws.data_ptr(), int(plan[2]), int(plan[0]),
+                                                _lib.stream_of(x)), "skd_conv3x3_split_wgrad_nhwc")
+    return dw
+
+
 class _Conv3x3SplitTrain(Function):
     """A same-size 3x3 convolution of a network in training, both directions on csrc/conv3x3.hip: the forward on ``pack_fwd``, the
     data gradient -- the same kind of convolution of the output gradient with the flipped, transposed weight -- on the
     ``pack_bwd`` THIS forward was given (kept in ctx: an optimizer step in between changes the cache, not this node).  The
-    weight gradient (and the bias gradient) are the library's, as before."""
+    weight gradient (and the bias gradient) are the library's, as before -- with ``wgrad`` the weight gradient is
+    conv3x3_split_wgrad's where the back-end has its entries, and the library computes the bias gradient alone."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd):
+    def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, *wgrad):
         _lib.require_device(x, weight, bias, pack_fwd, pack_bwd)
         ctx.save_for_backward(x, weight)
         ctx.pack_bwd, ctx.dilation, ctx.has_bias = pack_bwd, int(dilation), bias is not None
+        ctx.wgrad, ctx.n_inputs = bool(wgrad and wgrad[0]), 6 + len(wgrad)
         return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
 
     @staticmethod
@@ -910,20 +976,26 @@ class _Conv3x3SplitTrain(Function):
         if ctx.needs_input_grad[0]:
             dx = _conv3x3_split_launch(g, ctx.pack_bwd, int(weight.shape[1]), d)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.wgrad and need_w and all(_lib.has_entry(n) for n in _WGRAD_ENTRIES):
+            dw = conv3x3_split_wgrad(x, g, weight, d)
+            need_w = False
         if need_w or need_b:
-            _, dw, db = torch.ops.aten.convolution_backward(g, x, weight, [int(weight.shape[0])] if ctx.has_bias else None,
+            _, lw, db = torch.ops.aten.convolution_backward(g, x, weight, [int(weight.shape[0])] if ctx.has_bias else None,
                                                             [1, 1], [d, d], [d, d], False, [0, 0], 1, (False, need_w, need_b))
-            dw, db = dw if need_w else None, db if need_b else None
-        return dx, dw, db, None, None, None
+            dw, db = lw if need_w else dw, db if need_b else None
+        return (dx, dw, db) + (None,) * (ctx.n_inputs - 3)
 
 
-def conv3x3_split_train(x, weight, dilation, bias=None, owner=None):
+def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False):
     """``F.conv2d(x, weight, bias, 1, dilation, dilation)`` for a call conv3x3_train_supported accepted, differentiable: forward
     and data gradient are one launch each of the split-core implicit GEMM (csrc/conv3x3.hip: fp32 in and out, three bf16 pieces,
     six products, fp32 accumulation; the numerics of conv3x3_split_eval in both directions), the weight and bias gradients come
     from ``aten.convolution_backward``.  The weight is split once per version (conv3x3_train_packs, cached on ``owner``); the
-    bias is added in the forward's epilogue."""
+    bias is added in the forward's epilogue.  ``wgrad=True`` (opt-in): the weight gradient runs on the split core too
+    (conv3x3_split_wgrad) where the back-end has the entries of include/skd_wgrad.h; the bias gradient stays with the library."""
     pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
+    if wgrad:
+        return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, True)
     return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd)
 
 

@@ -183,8 +183,18 @@ class NetModel():
         if split_train is None:
             split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
         self.split_train = bool(split_train)
+        # args.split_wgrad (None: SKD_SPLIT_WGRAD, default "0"): with split_train, the weight gradients of those convolutions run
+        # on the split core as well (csrc/conv3x3_wgrad.hip); without split_train it routes nothing.  Off by default
+        # (isolated: profiles/r20_conv3x3_wgrad_isolated.md; the step A/B of profiles/r20_step_ab.md has not been run yet).
+        split_wgrad = getattr(args, "split_wgrad", None)
+        if split_wgrad is None:
+            split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
+        self.split_wgrad = bool(split_wgrad) and self.split_train
         if self.split_train:
-            route_training_convs(student)
+            if self.split_wgrad:
+                route_training_convs(student, wgrad=True)
+            else:
+                route_training_convs(student)
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -837,9 +847,12 @@ def default_args(**overrides):
         T_ckpt_path=None, is_student_load_imgnet=False, student_pretrain_model_imgnet=None,
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
-        ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None)
+        ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
+        split_wgrad=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
         a.split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
+    if a.split_wgrad is None:          # effective only together with split_train
+        a.split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
     return a

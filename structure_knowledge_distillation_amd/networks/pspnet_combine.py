@@ -6,7 +6,7 @@ and ``forward`` returns the same 7-element list ``[logits, dsn, feat_after_psp, 
 (pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm -- except the frozen teacher's 1x1 GEMMs (csrc/conv1x1.hip), its wide
 stride-1 3x3 convolutions (csrc/conv3x3.hip), the student's 3x3 convolutions in its inference form (fuse_for_inference) and, opt-in,
 the training student's stride-1 3x3 convolutions and their data gradients (route_training_convs; the weight gradients stay on
-MIOpen), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
+MIOpen unless its ``wgrad`` is set: csrc/conv3x3_wgrad.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
 csrc/abn*.hip (``libs``), applied in place on the conv output.
 """
 import functools
@@ -76,6 +76,11 @@ INFER_ROUTING_EXCLUDED = frozenset()
 # (profiles/r18_conv3x3_train_isolated.md has every shape).
 TRAIN_SPLIT_MIN_CIN = 128
 TRAIN_ROUTING_EXCLUDED = frozenset()
+# The weight gradient of a routed convolution on the split core too (route_training_convs(wgrad=True); a second opt-in on top of
+# the first): SF.conv3x3_split_wgrad instead of the library's kernels.  A shape whose two launches do not measure ahead of the
+# library by more than the spread is listed here as (Cin, Cout, dilation) and keeps the library for its weight gradient
+# (profiles/r20_conv3x3_wgrad_isolated.md has every shape).
+WGRAD_ROUTING_EXCLUDED = frozenset()
 
 
 def _train_routed(module, x, conv):
@@ -89,9 +94,16 @@ def _train_routed(module, x, conv):
     return SF.conv3x3_train_supported(x, conv.weight, *geometry, conv.groups)
 
 
+def _wgrad_routed(module, cin, cout, dilation):
+    """Whether a convolution the flagged ``module`` routes takes its weight gradient on the split core as well."""
+    return bool(getattr(module, "_skd_train_wgrad", False)) and (cin, cout, dilation) not in WGRAD_ROUTING_EXCLUDED
+
+
 def _train_conv(module, conv, x):
     """``conv(x)``: on the split core in both directions where _train_routed says so, the module's own forward otherwise."""
     if _train_routed(module, x, conv):
+        if _wgrad_routed(module, conv.in_channels, conv.out_channels, conv.dilation[0]):
+            return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=True)
         return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv)
     return conv(x)
 
@@ -340,10 +352,12 @@ class PSPModule(nn.Module):
                 if not hasattr(self, "_fold_cache"):
                     self._fold_cache = {}
                 min_cin = getattr(self, "_skd_train_min_cin", None)
+                extra = dict(split_wgrad=True) if _wgrad_routed(self, feats.shape[1], conv.out_channels, 1) else {}
                 out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache,
                                              split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
                                              split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
-                                                          and (feats.shape[1], conv.out_channels, 1) not in TRAIN_ROUTING_EXCLUDED))
+                                                          and (feats.shape[1], conv.out_channels, 1) not in TRAIN_ROUTING_EXCLUDED),
+                                             **extra)
                 return self.bottleneck[2](self.bottleneck[1](out))
             return self.bottleneck(SF.ppm_concat(priors, feats))
         h, w = feats.size(2), feats.size(3)
@@ -499,7 +513,7 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
     return model
 
 
-def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN):
+def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False):
     """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
 
     A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
@@ -511,12 +525,16 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN):
     The version is autograd's ``_version``: an optimizer that writes the weights without advancing it -- torch's FUSED
     multi-tensor optimizers -- needs ``kd_model.advance_versions_after_step`` as a step post-hook (NetModel registers it), or the
     next forward runs on the packs of the old weights.
+    ``wgrad=True``: the weight gradients of the routed convolutions run on the split core as well (SF.conv3x3_split_wgrad,
+    csrc/conv3x3_wgrad.hip) except for the shapes of WGRAD_ROUTING_EXCLUDED; on a back-end without the entries of
+    include/skd_wgrad.h they stay with the library.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
     for m in model.modules():
         if not isinstance(m, (BasicBlock, ResNet, PSPModule)):
             continue
         m._skd_train_min_cin = int(min_cin) if enable else None
+        m._skd_train_wgrad = bool(wgrad and enable)
         if enable:
             continue
         owners = ((m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0],) if isinstance(m, ResNet)

@@ -1,0 +1,105 @@
+"""GPU tool: the weight gradients of the training student's routed 3x3 convolutions at batch 8, 65 x 65, isolated -- writes the
+table of profiles/r20_conv3x3_wgrad_isolated.md.  Per shape: MIOpen's weight gradient (``aten.convolution_backward`` with mask
+(False, True, False)) against the two launches of skd_conv3x3_split_wgrad_nhwc together, workspace and result allocated outside
+the timed region on both sides.  ``tools/_timing.warm_timed`` (>= 30 ms of the same launches as warm-up, then the median of 5
+groups of 10 back-to-back launches), ``--rounds`` interleaved rounds parent, split, parent, split, ...; spread = (max - min) /
+median of one side's rounds, the larger of the two sides.  ``--slices a,b,c``: further slice counts timed beside the plan's own
+(one extra column each, timed once) -- how the shipped rule of skd_conv3x3_split_wgrad_plan was chosen.  ``--lib PATH``: another
+build of the library (say, one compiled with -DSKD_WGRAD_GRID_ORDER=1) timed in the same rounds, one more column.
+    python tools/conv3x3_wgrad_bench.py [--rounds 3] [--slices 1,2,4,8] [--lib other/libskd_hip.so]
+"""
+import argparse
+import ctypes
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+os.environ.setdefault("PYTORCH_MIOPEN_SUGGEST_NHWC", "1")
+PROBLEMS = [  # (name, Cin, Cout, dilation, convolutions of this shape per student step)
+    ("layer2 128->128 d1", 128, 128, 1, 3),
+    ("layer3.0.conv1 128->256 d2", 128, 256, 2, 1),
+    ("layer3 256->256 d2", 256, 256, 2, 3),
+    ("layer4.0.conv1 256->512 d4", 256, 512, 4, 1),
+    ("layer4 512->512 d4", 512, 512, 4, 3),
+    ("dsn[0] 256->128 d1", 256, 128, 1, 1),
+    ("psp half 512->128 d1", 512, 128, 1, 1),
+]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--hw", type=int, default=65)
+    ap.add_argument("--slices", default="")
+    ap.add_argument("--lib", default=None)
+    a = ap.parse_args()
+    import torch
+    import structure_knowledge_distillation_amd as _skd
+    _skd.configure_miopen()
+    from structure_knowledge_distillation_amd import _lib
+    from _timing import warm_timed
+    lib = _lib.load()
+    other = _lib.load(a.lib) if a.lib else None
+    dev = torch.device("cuda", 0)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    B, hw = a.batch, a.hw
+    extra = [int(s) for s in a.slices.split(",") if s]
+    med = statistics.median
+    fmt = lambda runs: " / ".join("%.1f" % (1e3 * t) for t in runs)
+    print("%d compute units; batch %d, %d x %d" % (cus, B, hw, hw))
+    print()
+    print("| convolution | per step | slices (K-tiles each) | parent us (runs) | split us (runs) | parent / split | spread | verdict |"
+          + (" --lib us (runs) |" if other else "") + "".join(" %d slices us |" % s for s in extra))
+    print("|---|---|---|---|---|---|---|---|" + "---|" * (len(extra) + bool(other)))
+    total_p = total_s = 0.0
+    plan = (ctypes.c_int64 * 3)()
+    with torch.no_grad():
+        for name, cin, cout, d, count in PROBLEMS:
+            torch.manual_seed(cin + cout + d)
+            x = torch.relu(torch.randn(B, cin, hw, hw, device=dev)).contiguous(memory_format=torch.channels_last)
+            g = torch.randn(B, cout, hw, hw, device=dev).contiguous(memory_format=torch.channels_last)
+            w = torch.zeros(cout, cin, 3, 3, device=dev).contiguous(memory_format=torch.channels_last)
+            dw = torch.empty_like(w)
+            st = _lib.stream_of(x)
+
+            def split_side(slices, lib=lib):
+                assert lib.skd_conv3x3_split_wgrad_plan(B, hw, hw, cin, cout, slices, cus, ctypes.cast(plan, ctypes.c_void_p))
+                used, per_slice, nbytes = int(plan[0]), int(plan[1]), int(plan[2])
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+                def run():
+                    assert lib.skd_conv3x3_split_wgrad_nhwc(B, hw, hw, cin, cout, d, x.data_ptr(), g.data_ptr(), dw.data_ptr(),
+                                                            *dw.stride(), ws.data_ptr(), nbytes, used, st)
+                return run, used, per_slice
+            run_s, used, per_slice = split_side(0)
+            run_p = lambda: torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [d, d], [d, d], False, [0, 0], 1,
+                                                                (False, True, False))
+            run_o = split_side(0, other)[0] if other else None
+            runs = {"p": [], "s": [], "o": []}
+            for _ in range(a.rounds):
+                runs["p"].append(warm_timed(run_p))
+                runs["s"].append(warm_timed(run_s))
+                if other:
+                    runs["o"].append(warm_timed(run_o))
+            parent, split = med(runs["p"]), med(runs["s"])
+            spread = max((max(v) - min(v)) / med(v) for v in (runs["p"], runs["s"]))
+            gain = (parent - split) / parent
+            verdict = "ahead" if gain > spread else ("behind" if -gain > spread else "within the spread")
+            total_p += count * parent
+            total_s += count * split
+            cols = " %s |" % fmt(runs["o"]) if other else ""
+            for s in extra:
+                run_e, used_e, _ = split_side(s)
+                cols += " %.1f (%d) |" % (1e3 * warm_timed(run_e), used_e)
+            print("| %s | %d | %d (%d) | %s | %s | %.2f | %.1f %% | %s |%s" % (
+                name, count, used, per_slice, fmt(runs["p"]), fmt(runs["s"]), parent / split, 100 * spread, verdict, cols), flush=True)
+    print()
+    print("Per student step (the counts above): parent %.2f ms, split %.2f ms, difference %.2f ms." % (total_p, total_s, total_p - total_s))
+
+
+if __name__ == "__main__":
+    main()
