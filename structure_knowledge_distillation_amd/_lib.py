@@ -18,6 +18,7 @@ OHEM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_oh
 INFER_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_infer.h"))
 TRAIN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_train.h"))
 WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_wgrad.h"))
+NARROW_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -197,6 +198,17 @@ WGRAD_SIGNATURES = {
     "skd_conv3x3_split_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
 }
 
+# Entry points declared in include/skd_narrow.h (csrc/conv3x3_narrow.hip): the 64-column form of the split-core 3x3 convolution,
+# extension entries in a table of their own like the five above (tests/test_conv3x3_narrow_cpu.py checks header <-> table <->
+# exported symbols, tests/test_conv3x3_narrow_gpu.py holds the guard-band cases).  A back-end without them leaves the 64-channel
+# convolutions where they were: nothing raises.
+NARROW_SIGNATURES = {
+    "skd_conv3x3_narrow_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "skd_conv3x3_narrow_pack_bytes": (_L, [_I, _I]),
+    "skd_conv3x3_narrow_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
+    "skd_conv3x3_narrow_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -227,7 +239,7 @@ def load(path=None):
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
-                  WGRAD_SIGNATURES):
+                  WGRAD_SIGNATURES, NARROW_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

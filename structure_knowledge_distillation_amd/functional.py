@@ -253,10 +253,11 @@ def _cached(owner, attr, key, build, hold=None):
 
 
 def drop_conv3x3_packs(owner):
-    """Forget the weight packs conv3x3_pack_weights / conv3x3_train_packs cached on ``owner`` (a module, or a PSPModule's
-    ``_fold_cache`` dict, whose packs sit under "pack3x3" / "pack3x3_train")."""
+    """Forget the weight packs conv3x3_pack_weights / conv3x3_train_packs / conv3x3_narrow_pack_weights / conv3x3_split_train's
+    narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under "pack3x3" /
+    "pack3x3_train")."""
     slot = owner if isinstance(owner, dict) else vars(owner)
-    for attr in ("_skd_conv3x3_pack", "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_train"):
+    for attr in ("_skd_conv3x3_pack", "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_train") + _NARROW_PACK_ATTRS:
         slot.pop(attr, None)
 
 
@@ -782,9 +783,26 @@ def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
                        query="skd_conv3x3_split_train_supported", host_ok=True)
 
 
-def _conv3x3_packs(w, owner, attr, entry, both, what):
+def _conv3x3_packs(w, owner, attr, entry, both, what, images=None, bytes_entry="skd_conv3x3_split_pack_bytes"):
     """The image(s) of the (Cout, Cin, 3, 3) weight ``w`` that csrc/conv3x3.hip streams into LDS, written by one launch of
-    ``entry`` and cached on ``owner`` as ``(key, *packs, storage)`` with ``key = (data_ptr, _version, shape, stride)``."""
+    ``entry`` and cached on ``owner`` as ``(key, *packs, storage)`` with ``key = (data_ptr, _version, shape, stride)``.
+    ``images = (forward?, backward?)``: ``entry`` is one of the two pack_pair entries (skd_train.h, skd_narrow.h) and writes the
+    chosen image(s) alone -- ``(pack_fwd, pack_bwd)`` with None for the one not asked for, sized by ``bytes_entry``."""
+    def build_images():
+        _lib.require_device(w)
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        lib = _lib.get()
+        if tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32 or not any(images):
+            raise ValueError("%s: unsupported weight %s" % (what, tuple(w.shape)))
+        sizes = [int(getattr(lib, bytes_entry)(*dims)) if want else None for want, dims in zip(images, ((cin, cout), (cout, cin)))]
+        if any(n is not None and n <= 0 for n in sizes):
+            raise ValueError("%s: unsupported weight %s" % (what, tuple(w.shape)))
+        with torch.no_grad():
+            packs = tuple(None if n is None else torch.empty((n,), dtype=torch.uint8, device=w.device) for n in sizes)
+            sized = [v for pk, n in zip(packs, sizes) for v in ((None, 0) if pk is None else (pk.data_ptr(), n))]
+            _lib.check(getattr(lib, entry)(cin, cout, w.data_ptr(), *(int(v) for v in w.stride()), *sized, _lib.stream_of(w)), entry)
+        return packs
+
     def build():
         _lib.require_device(w)
         cout, cin = int(w.shape[0]), int(w.shape[1])
@@ -799,7 +817,8 @@ def _conv3x3_packs(w, owner, attr, entry, both, what):
             _lib.check(getattr(lib, entry)(cin, cout, w.data_ptr(), *(int(v) for v in w.stride()), *sized, _lib.stream_of(packs[0])),
                        entry)
         return packs
-    return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build, hold=w)
+    return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build if images is None else build_images,
+                   hold=w)
 
 
 def conv3x3_pack_weights(conv, weight=None, owner=None):
@@ -829,14 +848,20 @@ def conv3x3_train_packs(weight, owner=None):
 
 _ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
 _RES_ENTRY = "skd_conv3x3_split_res_nhwc"
+# include/skd_narrow.h (csrc/conv3x3_narrow.hip): the 64-column form.  Its one convolution entry takes the residual pointer.
+_NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
+_NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
+_NARROW_PACK_ATTRS = ("_skd_conv3x3_narrow_pack", "_skd_conv3x3_train_pack_wide", "_skd_conv3x3_train_pack_narrow")
 
 
 def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0, residual=None):
     """The one launcher of the split-core 3x3 forms: act(bn_running(conv3x3(x) + conv_bias) [+ residual]) by ``entry`` --
-    skd_conv3x3_split_nhwc, or skd_conv3x3_split_res_nhwc, which takes the ``residual`` pointer (None included)."""
+    skd_conv3x3_split_nhwc, or skd_conv3x3_split_res_nhwc / skd_conv3x3_narrow_nhwc, which take the ``residual`` pointer (None
+    included)."""
     lib = _lib.get()
     b, cin, h, w = x.shape
-    if pack.numel() != lib.skd_conv3x3_split_pack_bytes(cin, cout):
+    pack_bytes = lib.skd_conv3x3_narrow_pack_bytes if entry == _NARROW_ENTRY else lib.skd_conv3x3_split_pack_bytes
+    if pack.numel() != pack_bytes(cin, cout):
         raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
     mean = var = gamma = beta = None
     eps, slope = 0.0, 0.01
@@ -845,7 +870,7 @@ def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, act
     _lib.require_device(x, pack, residual, conv_bias, mean, var, gamma, beta)
     # not a view (_new_cl's is one, with the same strides): the in-place ABN behind dsn[0] writes into a custom Function's output
     out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    res = (_lib.ptr(residual),) if entry == _RES_ENTRY else ()
+    res = (_lib.ptr(residual),) if entry in (_RES_ENTRY, _NARROW_ENTRY) else ()
     _lib.check(getattr(lib, entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(), *res,
                                    _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
                                    _ACT[activation], slope, int(geometry), _lib.stream_of(x)), entry)
@@ -885,6 +910,75 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
 def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None):
     """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc."""
     return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias)
+
+
+def _conv3x3_narrow_launch(x, pack, cout, dilation, conv_bias=None):
+    """The same on the 64-column form, for a pack of skd_conv3x3_narrow_pack_pair: one launch of skd_conv3x3_narrow_nhwc."""
+    return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias)
+
+
+def conv3x3_narrow_supported(x, conv, residual=False):
+    """True when the 64-column form of the split-core 3x3 convolution (csrc/conv3x3_narrow.hip, include/skd_narrow.h) takes
+    ``conv(x)`` of a frozen forward: no grad, a back-end that has the four entries (the tests' C double does not: callers then run
+    what they ran before), an fp32 channels-last 16-byte-aligned input, a plain 3x3 / stride-1 / padding == dilation / ungrouped
+    convolution with Cin a multiple of 16 and Cout of 64.  ``residual``: the one entry takes it, so the answer is the same.
+    Host tensors pass only under a test double, as in conv3x3_infer_supported."""
+    return _conv3x3_module_ok(x, conv, grad=False, entries=_NARROW_ENTRIES, query="skd_conv3x3_narrow_supported", host_ok=True)
+
+
+def conv3x3_narrow_pack_weights(conv, weight=None, owner=None):
+    """conv3x3_pack_weights for the 64-column form: the three bf16 planes of a frozen 3x3 convolution's weight per column tile of
+    64 output channels (6 bytes per weight), written by skd_conv3x3_narrow_pack_pair and cached on ``owner`` (default: the conv
+    module) under the same rule, in a slot of its own."""
+    w = conv.weight if weight is None else weight
+    if torch.is_grad_enabled() and w.requires_grad:
+        raise RuntimeError("conv3x3_narrow_pack_weights is for frozen (no-grad) convolutions")
+    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_narrow_pack", _NARROW_PACK_PAIR, False,
+                          "conv3x3_narrow_pack_weights", images=(True, False), bytes_entry="skd_conv3x3_narrow_pack_bytes")[0]
+
+
+def conv3x3_narrow_eval(x, pack, cout, dilation, residual=None, conv_bias=None, bn=None, activation="none", geometry=0):
+    """act(bn_running(conv3x3(x) + conv_bias) [+ residual]) in one launch of csrc/conv3x3_narrow.hip (inference only) with
+    ``pack = conv3x3_narrow_pack_weights(...)``: conv3x3_split_eval / conv3x3_split_res_eval for a Cout that is a multiple of 64.
+    The arithmetic of every output element is the wide kernel's, in its order: where both take a convolution they give the same
+    bits.  ``residual`` (B, cout, H, W) fp32 is read in channels-last memory (copied when it is not) and never written."""
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError("conv3x3_narrow_eval is inference-only")
+    if not _lib.has_entry(_NARROW_ENTRY):
+        raise NotImplementedError("this back-end has no skd_conv3x3_narrow_nhwc (include/skd_narrow.h)")
+    if residual is not None:
+        want = (x.shape[0], cout) + tuple(x.shape[2:])
+        if tuple(residual.shape) != want or residual.dtype != torch.float32:
+            raise ValueError("residual %s %s != output %s fp32" % (tuple(residual.shape), residual.dtype, want))
+        residual = _cl(residual)
+    return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry, residual)
+
+
+def conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups):
+    """True when conv3x3_split_train(..., narrow=True) takes the convolution of a network that is being trained: everything
+    conv3x3_train_supported asks, except that each direction need only fit the wide form OR the narrow one -- Cin and Cout
+    multiples of 64 -- and the back-end has the entries of include/skd_narrow.h as well."""
+    return (_conv3x3_ok(x, weight, stride, padding, dilation, groups, grad=True, entries=_TRAIN_ENTRIES + _NARROW_ENTRIES,
+                        query="skd_conv3x3_narrow_supported", host_ok=True)
+            and bool(_lib.get().skd_conv3x3_narrow_supported(int(weight.shape[0]), int(weight.shape[1]), int(stride), int(padding),
+                                                             int(dilation), int(groups))))
+
+
+def _conv3x3_narrow_train_packs(weight, owner):
+    """``(pack_fwd, pack_bwd, fwd_narrow, bwd_narrow)`` of a trained weight whose directions are chosen by their N -- Cout for the
+    forward, Cin for the data gradient: the wide image for a multiple of 128, the narrow one otherwise.  One launch per entry
+    that has an image to write, each cached in a slot of its own; both wide is conv3x3_train_packs."""
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    narrow = (cout % 128 != 0, cin % 128 != 0)
+    if not any(narrow):
+        return conv3x3_train_packs(weight, owner) + narrow
+    wide = (None, None)
+    if not all(narrow):
+        wide = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_wide", "skd_conv3x3_split_pack_pair", False,
+                              "conv3x3_split_train", images=(not narrow[0], not narrow[1]))
+    thin = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_narrow", _NARROW_PACK_PAIR, False, "conv3x3_split_train",
+                          images=narrow, bytes_entry="skd_conv3x3_narrow_pack_bytes")
+    return tuple(t if n else v for t, v, n in zip(thin, wide, narrow)) + narrow
 
 
 _WGRAD_ENTRIES = ("skd_conv3x3_split_wgrad_supported", "skd_conv3x3_split_wgrad_plan", "skd_conv3x3_split_wgrad_nhwc")
@@ -962,6 +1056,10 @@ class _Conv3x3SplitTrain(Function):
         ctx.save_for_backward(x, weight)
         ctx.pack_bwd, ctx.dilation, ctx.has_bias = pack_bwd, int(dilation), bias is not None
         ctx.wgrad, ctx.n_inputs = bool(wgrad and wgrad[0]), 6 + len(wgrad)
+        # (forward?, backward?) on the narrow entry: the third optional argument (conv3x3_split_train's ``narrow``)
+        fwd_narrow, ctx.bwd_narrow = wgrad[1] if len(wgrad) > 1 else (False, False)
+        if fwd_narrow:
+            return _conv3x3_narrow_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
         return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
 
     @staticmethod
@@ -974,7 +1072,7 @@ class _Conv3x3SplitTrain(Function):
             g = g.clone(memory_format=torch.channels_last)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = _conv3x3_split_launch(g, ctx.pack_bwd, int(weight.shape[1]), d)
+            dx = (_conv3x3_narrow_launch if ctx.bwd_narrow else _conv3x3_split_launch)(g, ctx.pack_bwd, int(weight.shape[1]), d)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.wgrad and need_w and all(_lib.has_entry(n) for n in _WGRAD_ENTRIES):
             dw = conv3x3_split_wgrad(x, g, weight, d)
@@ -986,13 +1084,20 @@ class _Conv3x3SplitTrain(Function):
         return (dx, dw, db) + (None,) * (ctx.n_inputs - 3)
 
 
-def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False):
+def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False):
     """``F.conv2d(x, weight, bias, 1, dilation, dilation)`` for a call conv3x3_train_supported accepted, differentiable: forward
     and data gradient are one launch each of the split-core implicit GEMM (csrc/conv3x3.hip: fp32 in and out, three bf16 pieces,
     six products, fp32 accumulation; the numerics of conv3x3_split_eval in both directions), the weight and bias gradients come
     from ``aten.convolution_backward``.  The weight is split once per version (conv3x3_train_packs, cached on ``owner``); the
     bias is added in the forward's epilogue.  ``wgrad=True`` (opt-in): the weight gradient runs on the split core too
-    (conv3x3_split_wgrad) where the back-end has the entries of include/skd_wgrad.h; the bias gradient stays with the library."""
+    (conv3x3_split_wgrad) where the back-end has the entries of include/skd_wgrad.h; the bias gradient stays with the library.
+    ``narrow=True`` (opt-in; conv3x3_narrow_train_supported says when): each direction is chosen by its N -- Cout for the forward,
+    Cin for the data gradient: the wide kernel for a multiple of 128, csrc/conv3x3_narrow.hip otherwise -- which takes one pack
+    launch per entry and weight version; the weight gradient of a shape with a 64-channel side stays with the library."""
+    if narrow:
+        pack_fwd, pack_bwd, fwd_narrow, bwd_narrow = _conv3x3_narrow_train_packs(weight, owner)
+        if fwd_narrow or bwd_narrow:
+            return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, False, (fwd_narrow, bwd_narrow))
     pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
     if wgrad:
         return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, True)

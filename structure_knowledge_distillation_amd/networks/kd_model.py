@@ -174,8 +174,18 @@ class NetModel():
             student.to(memory_format=torch.channels_last)
         # args.fused_eval: the student's eval-mode / no-grad forwards (validation between epochs, evaluate_main) take the fused
         # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
+        # args.split_narrow (None: SKD_SPLIT_NARROW, default "0"): the 64-channel 3x3 convolutions of the stem and layer1 on the
+        # split core too (csrc/conv3x3_narrow.hip) -- in the fused inference form together with fused_eval, in training together
+        # with split_train; alone it routes nothing.  Off by default (profiles/r21_conv3x3_narrow_isolated.md, profiles/r21_step_ab.md).
+        split_narrow = getattr(args, "split_narrow", None)
+        if split_narrow is None:
+            split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"
+        self.split_narrow = bool(split_narrow)
         if getattr(args, "fused_eval", False):
-            fuse_for_inference(student)
+            if self.split_narrow:
+                fuse_for_inference(student, narrow=True)
+            else:
+                fuse_for_inference(student)
         # args.split_train (None: SKD_SPLIT_TRAIN, default "0"): the student's stride-1 3x3 convolutions with >= 128 channels and
         # their data gradients run on the split core in training (pspnet_combine.route_training_convs); the weight gradients,
         # the eval forms and the frozen teacher are what they were.  Off by default (profiles/r18_step_ab.md has the A/B).
@@ -191,10 +201,11 @@ class NetModel():
             split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
         self.split_wgrad = bool(split_wgrad) and self.split_train
         if self.split_train:
+            extra = dict(narrow=True) if self.split_narrow else {}
             if self.split_wgrad:
-                route_training_convs(student, wgrad=True)
+                route_training_convs(student, wgrad=True, **extra)
             else:
-                route_training_convs(student)
+                route_training_convs(student, **extra)
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -848,11 +859,13 @@ def default_args(**overrides):
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
-        split_wgrad=None)
+        split_wgrad=None, split_narrow=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
         a.split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
     if a.split_wgrad is None:          # effective only together with split_train
         a.split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
+    if a.split_narrow is None:         # effective only together with fused_eval (inference) or split_train (training)
+        a.split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"
     return a

@@ -6,7 +6,8 @@ and ``forward`` returns the same 7-element list ``[logits, dsn, feat_after_psp, 
 (pspnet_combine.py:189).  Convolutions run on MIOpen through PyTorch-ROCm -- except the frozen teacher's 1x1 GEMMs (csrc/conv1x1.hip), its wide
 stride-1 3x3 convolutions (csrc/conv3x3.hip), the student's 3x3 convolutions in its inference form (fuse_for_inference) and, opt-in,
 the training student's stride-1 3x3 convolutions and their data gradients (route_training_convs; the weight gradients stay on
-MIOpen unless its ``wgrad`` is set: csrc/conv3x3_wgrad.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
+MIOpen unless its ``wgrad`` is set: csrc/conv3x3_wgrad.hip; the 64-channel convolutions of the stem and layer1 only with ``narrow``:
+csrc/conv3x3_narrow.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
 csrc/abn*.hip (``libs``), applied in place on the conv output.
 """
 import functools
@@ -60,8 +61,8 @@ SPLIT_REDUCE = True   # the reduce / stride-1 down-sample 1x1 GEMMs on csrc/conv
 # FUSED_EVAL_MIN_CIN is the default: 128, below the frozen teacher's CONV3X3_SPLIT_MIN_CIN, because at the student's evaluation
 # sizes (129 x 257 maps, batch 1, shapes the shipped MIOpen find-db was not tuned for) layer2's 128 -> 128 launch is 3.2 x ahead
 # of convolution + ABN pass, against a run-to-run spread of 1.1 - 2.6 % (profiles/r17_student_infer.md, which has every shape).  That
-# routes layer2's three stride-1 convolutions and all of layer3 / layer4; layer1 (Cout = 64) and layer2.0.conv1 (stride 2) are
-# not the kernel's.  A routed shape that measures behind is listed in INFER_ROUTING_EXCLUDED as (Cin, Cout, dilation) and keeps
+# routes layer2's three stride-1 convolutions and all of layer3 / layer4; layer2.0.conv1 (stride 2) is not the kernel's, and
+# layer1 (Cout = 64) is the 64-column form's, routed only with ``narrow`` (NARROW_ROUTING_EXCLUDED below).  A routed shape that measures behind is listed in INFER_ROUTING_EXCLUDED as (Cin, Cout, dilation) and keeps
 # conv -> forward_relu: none does.
 FUSED_EVAL_MIN_CIN = 128
 INFER_ROUTING_EXCLUDED = frozenset()
@@ -71,7 +72,8 @@ INFER_ROUTING_EXCLUDED = frozenset()
 # fp32 channels-last device input hands a stride-1 3x3 convolution with at least ``min_cin`` input channels, and its data gradient,
 # to the split core (SF.conv3x3_split_train) where both directions fit it (Cin and Cout multiples of 128).  TRAIN_SPLIT_MIN_CIN = 128
 # routes 13 convolutions of the ResNet18 student: layer2.0.conv2, layer2.1, layer3, layer4, the deep-supervision head's dsn[0] and
-# the PSP bottleneck's feature-map half; the stem, layer1 (64 channels) and layer2.0.conv1 (stride 2) are not the kernel's.  A
+# the PSP bottleneck's feature-map half; layer2.0.conv1 and the stem's conv1 (stride 2) are not the kernel's, and the stem's
+# conv2 / conv3 and layer1 (64 channels) are routed only with ``narrow`` (below).  A
 # routed shape that measures behind is listed in TRAIN_ROUTING_EXCLUDED as (Cin, Cout, dilation) and keeps the library
 # (profiles/r18_conv3x3_train_isolated.md has every shape).
 TRAIN_SPLIT_MIN_CIN = 128
@@ -81,6 +83,43 @@ TRAIN_ROUTING_EXCLUDED = frozenset()
 # library by more than the spread is listed here as (Cin, Cout, dilation) and keeps the library for its weight gradient
 # (profiles/r20_conv3x3_wgrad_isolated.md has every shape).
 WGRAD_ROUTING_EXCLUDED = frozenset()
+# The 64-channel convolutions (fuse_for_inference(narrow=True), route_training_convs(narrow=True); a further opt-in on top of either):
+# the stem's conv2 (64 -> 64) and layer1's four convolutions (128 -> 64, then three 64 -> 64) on the 64-column form of the kernel
+# (csrc/conv3x3_narrow.hip), the stem's conv3 (64 -> 128) on the wide kernel in the forward and on the narrow one for its data
+# gradient (layer1.0.conv1 the other way round).  These six are chosen by their channel counts -- multiples of 64 on both sides,
+# one of them not a multiple of 128 -- not by ``min_cin``.  A shape
+# that does not measure ahead of the library by more than the spread is listed here as (Cin, Cout, dilation, form), form =
+# "infer" or "train", and keeps the library (profiles/r21_conv3x3_narrow_isolated.md has every shape).
+NARROW_ROUTING_EXCLUDED = frozenset()
+
+
+def _narrow_shape(conv):
+    """A convolution the ``narrow`` opt-in is about: 64 channels on one side at least, multiples of 64 on both."""
+    cin, cout = conv.in_channels, conv.out_channels
+    return cin % 64 == 0 and cout % 64 == 0 and (cin % 128 != 0 or cout % 128 != 0)
+
+
+def _narrow_infer_routed(module, x, conv, residual=False):
+    """Whether the ``narrow``-flagged ``module`` (fuse_for_inference) hands ``conv(x)`` of a frozen forward to the split core:
+    "narrow" for the 64-column entry (Cout = 64), "wide" for the existing one (the stem's conv3, 64 -> 128), False otherwise."""
+    if not getattr(module, "_skd_infer_narrow", False) or conv.bias is not None or not _narrow_shape(conv):
+        return False
+    if (conv.in_channels, conv.out_channels, conv.dilation[0], "infer") in NARROW_ROUTING_EXCLUDED:
+        return False
+    if conv.out_channels % 128 == 0:
+        return "wide" if SF.conv3x3_infer_supported(x, conv, residual) else False
+    return "narrow" if SF.conv3x3_narrow_supported(x, conv, residual) else False
+
+
+def _narrow_train_routed(module, x, conv):
+    """Whether the ``narrow``-flagged ``module`` (route_training_convs) in training mode hands ``conv(x)`` to
+    SF.conv3x3_split_train(..., narrow=True)."""
+    if not getattr(module, "_skd_train_narrow", False) or not module.training or not _narrow_shape(conv):
+        return False
+    geometry = SF.conv2d_square_geometry(conv)
+    if geometry is None or (conv.in_channels, conv.out_channels, geometry[2], "train") in NARROW_ROUTING_EXCLUDED:
+        return False
+    return SF.conv3x3_narrow_train_supported(x, conv.weight, *geometry, conv.groups)
 
 
 def _train_routed(module, x, conv):
@@ -105,6 +144,8 @@ def _train_conv(module, conv, x):
         if _wgrad_routed(module, conv.in_channels, conv.out_channels, conv.dilation[0]):
             return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=True)
         return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv)
+    if _narrow_train_routed(module, x, conv):
+        return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, narrow=True)
     return conv(x)
 
 
@@ -131,9 +172,13 @@ def _conv3x3_split(x, conv):
             and SF.conv3x3_split_supported(x, conv))
 
 
-def _split_conv(x, conv, bn=None, activation="none", residual=None):
+def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False):
     """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, for a call one of the
-    SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names)."""
+    SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names).  ``narrow``: the
+    64-column form (csrc/conv3x3_narrow.hip) on its own pack, for a call SF.conv3x3_narrow_supported accepted."""
+    if narrow:
+        return SF.conv3x3_narrow_eval(x, SF.conv3x3_narrow_pack_weights(conv), conv.out_channels, conv.dilation[0], residual, conv.bias,
+                                      bn, activation)
     pack = SF.conv3x3_pack_weights(conv)
     if residual is not None:
         return SF.conv3x3_split_res_eval(x, pack, conv.out_channels, conv.dilation[0], residual, bn, activation, conv.bias)
@@ -209,16 +254,19 @@ class BasicBlock(nn.Module):
 
     def _routed(self, x, conv, residual):
         """Whether the flagged block hands ``conv(x)`` to the split core.  Each convolution is asked on its own: one the kernel
-        does not take (stride 2, Cout = 64) or the policy leaves out keeps conv -> forward_relu while the other is fused."""
-        return (conv.bias is None and conv.in_channels >= self._skd_infer_min_cin
+        does not take (stride 2; Cout = 64 without ``narrow``) or the policy leaves out keeps conv -> forward_relu while the other
+        is fused.  "narrow": the 64-column form takes it (_narrow_infer_routed)."""
+        if (conv.bias is None and conv.in_channels >= self._skd_infer_min_cin
                 and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in INFER_ROUTING_EXCLUDED
-                and SF.conv3x3_infer_supported(x, conv, residual))
+                and SF.conv3x3_infer_supported(x, conv, residual)):
+            return True
+        return _narrow_infer_routed(self, x, conv, residual) == "narrow" and "narrow"
 
     def _forward_infer(self, x):
         """relu(bn1(conv1(x))) and relu(bn2(conv2(.)) + residual) as one launch of csrc/conv3x3.hip each (BN + ReLU, and BN +
         residual + ReLU, in the epilogue) where _routed says so."""
         r1 = self._routed(x, self.conv1, False)
-        out = _split_conv(x, self.conv1, self.bn1, "relu") if r1 else self.bn1.forward_relu(self.conv1(x))
+        out = _split_conv(x, self.conv1, self.bn1, "relu", narrow=r1 == "narrow") if r1 else self.bn1.forward_relu(self.conv1(x))
         r2 = self._routed(out, self.conv2, True)
         if self.downsample is None:
             residual = x
@@ -230,7 +278,7 @@ class BasicBlock(nn.Module):
         else:
             residual = self.downsample(x)
         if r2:
-            return _split_conv(out, self.conv2, self.bn2, "relu", residual)
+            return _split_conv(out, self.conv2, self.bn2, "relu", residual, narrow=r2 == "narrow")
         return self.bn2.forward_relu(self.conv2(out), residual)
 
     def forward(self, x):
@@ -424,6 +472,14 @@ class ResNet(nn.Module):
             return self.dsn[3](self.dsn[2](bn(_train_conv(self, conv, x3))))
         return self.dsn(x3)
 
+    def _stem_narrow(self, x):
+        """Whether the frozen forward asks _narrow_infer_routed about the stem's conv2 / conv3: this network is flagged
+        (fuse_for_inference(narrow=True): an unflagged teacher never is), no grad, ``x`` an fp32 channels-last map and bn2 a plain
+        eval-mode BatchNorm."""
+        return (getattr(self, "_skd_infer_narrow", False) and not torch.is_grad_enabled() and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last) and getattr(self.bn2, "activation", None) == "none"
+                and getattr(self.bn2, "running_mean", None) is not None and getattr(self.bn2, "running_var", None) is not None)
+
     def forward(self, x):
         if _fused(self, x) and not self.training and getattr(self.bn3, "activation", None) == "none":
             # Frozen network: eval-mode BN + ReLU is a non-decreasing map per channel (its scale (|gamma| + eps) / sqrt(var + eps) is
@@ -431,17 +487,25 @@ class ResNet(nn.Module):
             # the max-pool bit for bit: relu(bn(max(window))) == max(relu(bn(.)) over the window).  The pass over the 268 MB
             # conv3 output becomes a pass over the 68 MB pooled map (pspnet_combine.py:131-135; VERDICT r04 missing 5).
             x = self.bn1.forward_relu(self.conv1(x))
-            x = self.bn2.forward_relu(self.conv2(x))
-            x = self.bn3.forward_relu(SF.max_pool_stem(self.conv3(x), self.maxpool))
+            if self._stem_narrow(x):
+                # fuse_for_inference(narrow=True): conv2 + bn2 + ReLU as one launch of the 64-column form, conv3 raw on the wide kernel
+                r2 = _narrow_infer_routed(self, x, self.conv2)
+                x = _split_conv(x, self.conv2, self.bn2, "relu", narrow=True) if r2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
+                c3 = _split_conv(x, self.conv3) if _narrow_infer_routed(self, x, self.conv3) == "wide" else self.conv3(x)
+            else:
+                x = self.bn2.forward_relu(self.conv2(x))
+                c3 = self.conv3(x)
+            x = self.bn3.forward_relu(SF.max_pool_stem(c3, self.maxpool))
         else:
             if _fused(self, x):
                 x = self.bn1.forward_relu(self.conv1(x))
-                x = self.bn2.forward_relu(self.conv2(x))
+                x = self.bn2.forward_relu(_train_conv(self, self.conv2, x))
                 # training: bn3 -> relu3 -> maxpool in two fused passes per direction (csrc/abn_stem.hip, round 6): the
                 # 268 MB normalised conv3 output is never written, its gradient never un-pooled into memory; STEM_FUSED = False or an
                 # input the fused kernels do not take: forward_relu, then csrc/maxpool.hip (channels-last) / the stock pool
-                x = (self.bn3.forward_relu_maxpool(self.conv3(x), self.maxpool) if STEM_FUSED
-                     else SF.max_pool_stem(self.bn3.forward_relu(self.conv3(x)), self.maxpool))
+                c3 = _train_conv(self, self.conv3, x)       # the library's, unless route_training_convs(narrow=True) flagged the stem
+                x = (self.bn3.forward_relu_maxpool(c3, self.maxpool) if STEM_FUSED
+                     else SF.max_pool_stem(self.bn3.forward_relu(c3), self.maxpool))
             else:
                 x = self.relu1(self.bn1(self.conv1(x)))
                 x = self.relu2(self.bn2(self.conv2(x)))
@@ -479,7 +543,7 @@ def Res_pspnet(block=Bottleneck, layers=[3, 4, 23, 3], num_classes=21):
     return ResNet(block, layers, num_classes)
 
 
-def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
+def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False):
     """Flag every BasicBlock of ``model`` (the student) for the fused inference form and return ``model``.
 
     A flagged block in eval mode, with grad disabled, on an fp32 channels-last input runs ``conv1 -> bn1 -> relu`` and
@@ -491,29 +555,41 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN):
     (NetModel registers it on the student's optimizer; a caller with a fused optimizer of their own must do so themselves), or
     every evaluation behind the first runs on stale packs.  The weights that
     are routed and already on the device are packed here, so a graph captured later allocates nothing for them.
+    ``narrow=True`` (a further opt-in): the 64-channel convolutions as well, in the same kind of forward -- layer1's four on the
+    64-column form of the kernel (csrc/conv3x3_narrow.hip; BN + ReLU, and BN + residual + ReLU, in the epilogue), the stem's
+    conv2 on it with bn2 + ReLU in the epilogue, the stem's conv3 (64 -> 128) raw on the existing kernel in front of
+    max_pool_stem and bn3 -- except the shapes of NARROW_ROUTING_EXCLUDED.  The stem is flagged on the ResNet itself.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
     is set and changes nothing."""
     for m in model.modules():
-        if not isinstance(m, BasicBlock):
+        if not isinstance(m, (BasicBlock, ResNet)):
             continue
+        stem = isinstance(m, ResNet)
+        convs = ((m.conv2, False), (m.conv3, False)) if stem else ((m.conv1, False), (m.conv2, True))
+        m._skd_infer_narrow = bool(narrow and enable)
         if not enable:
-            m._skd_infer_min_cin = None
-            SF.drop_conv3x3_packs(m.conv1)
-            SF.drop_conv3x3_packs(m.conv2)
+            if not stem:
+                m._skd_infer_min_cin = None
+            for conv, _ in convs:
+                SF.drop_conv3x3_packs(conv)
             continue
-        m._skd_infer_min_cin = int(min_cin)
+        if not stem:
+            m._skd_infer_min_cin = int(min_cin)
         with torch.no_grad():
-            for conv, res in ((m.conv1, False), (m.conv2, True)):
+            for conv, res in convs:
                 w = conv.weight
                 if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
                     continue
                 probe = w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2)      # a channels-last map of the right width
-                if m._routed(probe, conv, res):
+                how = _narrow_infer_routed(m, probe, conv, res) if stem else m._routed(probe, conv, res)
+                if how == "narrow":
+                    SF.conv3x3_narrow_pack_weights(conv)
+                elif how:
                     SF.conv3x3_pack_weights(conv)
     return model
 
 
-def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False):
+def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False, narrow=False):
     """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
 
     A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
@@ -528,6 +604,9 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     ``wgrad=True``: the weight gradients of the routed convolutions run on the split core as well (SF.conv3x3_split_wgrad,
     csrc/conv3x3_wgrad.hip) except for the shapes of WGRAD_ROUTING_EXCLUDED; on a back-end without the entries of
     include/skd_wgrad.h they stay with the library.
+    ``narrow=True``: the stem's conv2 / conv3 and layer1's four convolutions too (SF.conv3x3_split_train(..., narrow=True): each
+    direction on the wide kernel where its N is a multiple of 128, on csrc/conv3x3_narrow.hip otherwise; their weight gradients
+    stay with the library) except for the shapes of NARROW_ROUTING_EXCLUDED.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
     for m in model.modules():
@@ -535,9 +614,10 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
             continue
         m._skd_train_min_cin = int(min_cin) if enable else None
         m._skd_train_wgrad = bool(wgrad and enable)
+        m._skd_train_narrow = bool(narrow and enable)
         if enable:
             continue
-        owners = ((m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0],) if isinstance(m, ResNet)
+        owners = ((m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0], m.conv2, m.conv3) if isinstance(m, ResNet)
                   else (getattr(m, "_fold_cache", {}),))
         for owner in owners:
             SF.drop_conv3x3_packs(owner)

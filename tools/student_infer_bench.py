@@ -10,9 +10,10 @@ csrc/conv3x3.hip with that epilogue (``conv3x3_split_eval`` / ``conv3x3_split_re
 
 Whole forward -- the seeded student, batch 1 at 1024 x 2048, and the five-scale flip set of tools/multiscale_eval_bench.py (five
 batches of 2), each without ``fuse_for_inference`` and with it at every ``--min-cin`` (default: the frozen teacher's 256 and the
-shipped FUSED_EVAL_MIN_CIN).
+shipped FUSED_EVAL_MIN_CIN), and with ``narrow=True`` on top of the shipped policy (the row "fused, narrow": the stem and layer1 on
+the split core too, csrc/conv3x3_narrow.hip).
 
-    python tools/student_infer_bench.py [--rounds 3] [--min-cin 256 128] [--out FILE]
+    python tools/student_infer_bench.py [--rounds 3] [--min-cin 256 128] [--skip-launches] [--out FILE]
 
 Prints one JSON line and writes the tables to ``--out`` (default profiles/r17_student_infer.md).
 """
@@ -94,6 +95,7 @@ def main():
     ap.add_argument("--min-cin", type=int, nargs="+", default=None, help="fuse_for_inference policies of the whole-forward rows")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r17_student_infer.md"))
     ap.add_argument("--skip-multiscale", action="store_true")
+    ap.add_argument("--skip-launches", action="store_true", help="the whole-forward tables only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("student_infer_bench needs an MI355X: there is no CPU timing")
@@ -103,7 +105,7 @@ def main():
     dev = torch.device("cuda", 0)
     out = {"rounds": args.rounds, "min_cins": min_cins, "launches": {}, "forwards": {}}
     with torch.no_grad():
-        for label, cin, cout, dil, h, w, both in LAUNCHES:
+        for label, cin, cout, dil, h, w, both in ([] if args.skip_launches else LAUNCHES):
             for residual in ((False, True) if both else (False,)):
                 key = label + (" + residual" if residual else "")
                 out["launches"][key] = launch_case(cin, cout, dil, h, w, residual, dev, args.rounds)
@@ -121,12 +123,14 @@ def main():
             run = lambda: [net(b) for b in batches]
             fuse_for_inference(net, enable=False)
             plain = [o[0].clone() for o in run()]
-            sides = [("plain", None)] + [("fused, min_cin %d" % m, m) for m in min_cins]
+            sides = [("plain", None)] + [("fused, min_cin %d" % m, m) for m in min_cins] + [("fused, narrow", "narrow")]
             runs, diff = {k: [] for k, _ in sides}, {}
             for _ in range(args.rounds):
                 for k, m in sides:
                     fuse_for_inference(net, enable=False)
-                    if m is not None:
+                    if m == "narrow":
+                        fuse_for_inference(net, narrow=True)
+                    elif m is not None:
                         fuse_for_inference(net, min_cin=m)
                     runs[k].append(warm_timed(run, reps=2, warm_ms=200.0, groups=3))
                     diff[k] = max(float((p - o[0]).abs().max() / p.abs().max()) for p, o in zip(plain, run()))
@@ -145,16 +149,19 @@ def main():
         "groups of 2).  Every row is %d interleaved rounds parent, fused, parent, fused, ...; the runs column lists each round, **spread**" % args.rounds,
         "is (max - min) / median of one side's repeated identical runs, the larger of the two sides.",
         "",
-        "## Per launch, batch 1",
-        "",
-        "Parent: the MIOpen fp32 convolution (channels-last) + the in-place eval-mode InPlace-ABN pass with ReLU, which also adds the",
-        "residual where there is one (`bn.forward_relu(conv(x)[, residual])`, what an unflagged BasicBlock runs).  Fused: one launch of",
-        "`csrc/conv3x3.hip` with BN + ReLU (`skd_conv3x3_split_nhwc`) or BN + residual + ReLU (`skd_conv3x3_split_res_nhwc`) in the epilogue.",
-        "",
-        "| convolution | map | parent ms (runs) | fused ms (runs) | parent median | fused median | parent / fused | spread | verdict |",
-        "|---|---|---|---|---|---|---|---|---|",
     ]
-    for label, cin, cout, dil, h, w, both in LAUNCHES:
+    if not args.skip_launches:
+        lines += [
+            "## Per launch, batch 1",
+            "",
+            "Parent: the MIOpen fp32 convolution (channels-last) + the in-place eval-mode InPlace-ABN pass with ReLU, which also adds the",
+            "residual where there is one (`bn.forward_relu(conv(x)[, residual])`, what an unflagged BasicBlock runs).  Fused: one launch of",
+            "`csrc/conv3x3.hip` with BN + ReLU (`skd_conv3x3_split_nhwc`) or BN + residual + ReLU (`skd_conv3x3_split_res_nhwc`) in the epilogue.",
+            "",
+            "| convolution | map | parent ms (runs) | fused ms (runs) | parent median | fused median | parent / fused | spread | verdict |",
+            "|---|---|---|---|---|---|---|---|---|",
+        ]
+    for label, cin, cout, dil, h, w, both in ([] if args.skip_launches else LAUNCHES):
         for residual in ((False, True) if both else (False,)):
             key = label + (" + residual" if residual else "")
             r = out["launches"][key]
@@ -162,7 +169,8 @@ def main():
                 key, h, w, fmt_runs(r["parent"]), fmt_runs(r["fused"]), r["parent"]["median_ms"], r["fused"]["median_ms"],
                 r["parent_over_fused"], 100 * max(r["parent"]["spread"], r["fused"]["spread"]), r["verdict"]))
     lines += ["", "## Whole forward (Res_pspnet BasicBlock [2, 2, 2, 2], seeded, eval, channels-last)", "",
-              "Interleaved per round: plain, then `fuse_for_inference(net, min_cin=m)` for every m listed.", "",
+              "Interleaved per round: plain, then `fuse_for_inference(net, min_cin=m)` for every m listed, then",
+              "`fuse_for_inference(net, narrow=True)` (\"fused, narrow\": the shipped min_cin plus the stem and layer1).", "",
               "| input | forward | ms (runs) | median ms | plain / this | spread | logits: max difference from plain / max |", "|---|---|---|---|---|---|---|"]
     for name, res in out["forwards"].items():
         for k, r in res.items():
@@ -171,7 +179,8 @@ def main():
     lines += ["", "The parent's convolutions are MIOpen's with the find-db shipped in `miopen_db/`, which was tuned for the 512 x 512 training",
               "shapes only: at these map sizes MIOpen runs whatever its heuristics pick.  That is the path an unflagged student takes today, so it",
               "is the baseline here; it is not MIOpen at its best."]
-    lines += ["", "Not measured: other batch sizes or image sizes, a counter profile of the new instantiations, the 64-column shapes of layer1", ""]
+    lines += ["", "Not measured: other batch sizes or image sizes, a counter profile of the new instantiations.  The 64-column shapes of the stem",
+              "and layer1, isolated: profiles/r21_conv3x3_narrow_isolated.md (tools/conv3x3_narrow_bench.py).", ""]
     with open(args.out, "w") as fh:
         fh.write("\n".join(lines))
 
