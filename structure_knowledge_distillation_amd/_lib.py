@@ -198,7 +198,7 @@ WGRAD_SIGNATURES = {
     "skd_conv3x3_split_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
 }
 
-# Entry points declared in include/skd_narrow.h (csrc/conv3x3_narrow.hip): the 64-column form of the split-core 3x3 convolution,
+# Entry points declared in include/skd_narrow.h (csrc/conv3x3.hip): the 64-column form of the split-core 3x3 convolution,
 # extension entries in a table of their own like the five above (tests/test_conv3x3_narrow_cpu.py checks header <-> table <->
 # exported symbols, tests/test_conv3x3_narrow_gpu.py holds the guard-band cases).  A back-end without them leaves the 64-channel
 # convolutions where they were: nothing raises.

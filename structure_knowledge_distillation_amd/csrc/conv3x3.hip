@@ -1,5 +1,5 @@
-// conv3x3.hip -- 3x3, stride-1, "same" (padding = dilation) convolution of a frozen network as an IMPLICIT GEMM on the
-// split-operand bf16-MFMA core of conv_split_dev.hpp (see conv1x1.hip for the core): fp32 in, fp32 out.
+// conv3x3.hip -- 3x3, stride-1, "same" (padding = dilation) convolution as an IMPLICIT GEMM on the split-operand bf16-MFMA core
+// of conv_split_dev.hpp (see conv1x1.hip for the core): fp32 in, fp32 out.
 //
 //     Y[m][n] = epi( sum_{tap, c} X[pixel(m) + shift(tap)][c] * W[n][c][tap] ),   M = B*H*W output pixels (channels-last),
 //     N = Cout, K = 9 * Cin with k = tap * Cin + c, tap = 3 ty + tx, shift = ((ty - 1) * W + (tx - 1)) * dilation pixels.
@@ -11,38 +11,57 @@
 // peak (profiles/r06w_conv_shapes.md); the pipe is the limit, and six bf16 MFMAs per 16 k take 2.67 x less matrix-pipe time than
 // eight fp32 ones (conv1x1.hip).
 //
-// Weights are split ONCE per weight version (once for a frozen network): conv3x3_pack_pair_kernel writes, per column tile of 128
-// output channels and per K-tile of 16 k, the three bf16 planes in exactly the LDS image of the core (kPlaneChunks layout) -- 768 chunks of 16
-// bytes.  The main loop's B stage is then three 16-byte global loads and three ds_write_b128 per thread: no VALU work.  The split
-// is a pure function of the fp32 value, so the result equals splitting in the loop bit for bit.  Activations are split on
-// their way into LDS as in the 1x1 kernel (each element nine times, once per tap).
+// ONE kernel family with the column-tile width TN as a template parameter: TN = 128 output channels per tile (include/skd_eval.h,
+// skd_infer.h, skd_train.h: the frozen teacher, the student's wide layers) and TN = 64 (include/skd_narrow.h: the student's stem
+// conv2, layer1 and the data gradient of conv3, whose N is a multiple of 64 only).  TN sets the wave map and the B image
+// (tile_mma) and nothing else: taps, masks, K loop, product order and epilogue are the same code, so every output element sees
+// the same operations in the same order and at a Cout both forms take they give the same bits (tests/test_conv3x3_narrow_gpu.py).
 //
-// Epilogue (store_block): out = act( ((acc + conv_bias - mean) * invstd) * (|weight| + eps) + bias ), every term optional:
-// the identity (raw convolution output: the PSP bottleneck's `feats` half, the bottleneck blocks' conv2), conv bias + eval-mode
-// InPlace-ABN + leaky ReLU (the deep-supervision head), eval-mode BN + ReLU.
+// Weights are split ONCE per weight version (once for a frozen network): conv3x3_pack_pair_kernel writes, per column tile of TN
+// output channels and per K-tile of 16 k, the three bf16 planes in exactly the LDS image of the core -- chunk(h, row) = h * TN +
+// (row ^ 4 h), 6 TN chunks of 16 bytes (768 or 384).  The main loop's B stage is then three (TN = 64: one, and a second for the
+// first two waves) 16-byte global loads and ds_write_b128 per thread: no VALU work.  The split is a pure function of the fp32
+// value, so the result equals splitting in the loop bit for bit.  Activations are split on their way into LDS as in the 1x1
+// kernel (each element nine times, once per tap).
+//
+// Epilogue (store_block): out = act( ((acc + conv_bias - mean) * invstd) * (|weight| + eps) + bias [+ residual] ), every term
+// optional: the identity (raw convolution output: the PSP bottleneck's `feats` half, the bottleneck blocks' conv2), conv bias +
+// eval-mode InPlace-ABN + leaky ReLU (the deep-supervision head), eval-mode BN + ReLU, BN + residual + ReLU (a BasicBlock's tail).
 //
 // Grid: XCD-aware panel-major order as in conv1x1.hip -- row panel p lives on XCD p % 8, its column tiles run back to back --
-// so the workgroups resident on an XCD together started together and walk the same K-tiles of the same (at most Cout / 128)
+// so the workgroups resident on an XCD together started together and walk the same K-tiles of the same (at most Cout / TN)
 // weight panels at about the same time: a weight slice is fetched into that L2 once per wave of workgroups, not once per tile.
-// Two accumulator sets (tile_mma).  Two kernels, chosen per launch by launch3g: the TALL one runs 128 x 128 output tiles for the
-// launch's whole rounds and 64 x 128 tiles for the last, partial round, all at two workgroups per CU (one kernel, one register
-// budget); the other runs 64 x 128 tiles throughout at three workgroups per CU and takes the problems that do not fill the
-// chip's two-per-CU slots once.  48 KB of LDS either way.
+// Two accumulator sets (tile_mma).  TN = 128 has two kernels, chosen per launch by launch3g: the TALL one runs 128 x 128 output
+// tiles for the launch's whole rounds and 64 x 128 tiles for the last, partial round, all at two workgroups per CU (one kernel, one
+// register budget); the other runs 64 x 128 tiles throughout at three workgroups per CU and takes the problems that do not fill
+// the chip's two-per-CU slots once.  48 KB of LDS either way.  TN = 64 runs 128 x 64 tiles throughout: two accumulator sets of 32
+// registers each and 42 KB of LDS (a stage is the 768 chunks of A and the 384 of B; k_loop places its second stage kStageChunks
+// behind the first) admit three workgroups per CU.
 #include "conv_split_dev.hpp"
 #include "skd_infer.h"
+#include "skd_narrow.h"
 #include "skd_train.h"
 
 namespace skd {
 namespace {
 
-constexpr int kTileChunks = kOperandChunks;           // one (column tile, K-tile) of packed weights: 768 chunks = 12,288 bytes
-constexpr int kBChunksPerThread = kTileChunks / kThreads;   // 3: thread t copies chunk t of each plane
 constexpr int kDepth3x3 = 2;                          // K-tiles of load look-ahead (k_loop, conv_split_dev.hpp)
+constexpr int kNarrowTN = 64;                         // the column tile of include/skd_narrow.h; kTN = 128 is the others'
+// One (column tile, K-tile) of packed weights, in chunks: 768 = 12,288 bytes, or 384.  Thread t copies chunks t + i * kThreads.
+constexpr int tile_chunks(int TN) { return 3 * 2 * TN; }
+constexpr int b_copies(int TN) { return (tile_chunks(TN) + kThreads - 1) / kThreads; }
+// Whether thread t's copy i exists: a constant for every copy but the last of TN = 64 (t < 128: uniform per wave).
+template <int TN>
+__device__ __forceinline__ bool b_copy_live(int i) {
+  return (i + 1) * kThreads <= tile_chunks(TN) || (int)threadIdx.x < tile_chunks(TN) - i * kThreads;
+}
+constexpr size_t conv3x3_lds(int TN) { return sizeof(uint4) * (kStageChunks + kOperandChunks + tile_chunks(TN)); }
+static_assert(conv3x3_lds(kTN) == kConvLds, "the 128-column form fills both stages");
 
-template <int TM>
+template <int TM, int TN>
 struct Staging3 {
   float4 a[TM / kRPP];
-  uint4 b[kBChunksPerThread];
+  uint4 b[b_copies(TN)];
 };
 
 struct TapCursor {      // the K-tile being staged: tap 0..8, first channel c0, and the tap's address shift in floats
@@ -55,15 +74,18 @@ __device__ __forceinline__ int64_t tap_shift(int tap, int W, int dil, int Cin) {
   return ((int64_t)(ty - 1) * W + (tx - 1)) * dil * Cin;
 }
 
-// The packed weights: every lane loads its three chunks.
-template <int TM>
-__device__ __forceinline__ void stage_load3_b(Staging3<TM> &s, const uint4 *__restrict__ bsrc) {
+// The packed weights: every lane loads its chunks (a copy that does not exist stages zeros, which nothing stores).
+template <int TM, int TN>
+__device__ __forceinline__ void stage_load3_b(Staging3<TM, TN> &s, const uint4 *__restrict__ bsrc) {
 #pragma unroll
-  for (int p = 0; p < kBChunksPerThread; ++p) s.b[p] = bsrc[p * kPlaneChunks];
+  for (int i = 0; i < b_copies(TN); ++i) {
+    s.b[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (b_copy_live<TN>(i)) s.b[i] = bsrc[i * kThreads];
+  }
 }
 // The activations: a lane whose tap is outside the image issues no load and stages an exact zero.
-template <int TM>
-__device__ __forceinline__ void stage_load3_a(Staging3<TM> &s, const float *__restrict__ X, const TapCursor &cur,
+template <int TM, int TN>
+__device__ __forceinline__ void stage_load3_a(Staging3<TM, TN> &s, const float *__restrict__ X, const TapCursor &cur,
                                               const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP]) {
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) {
@@ -72,32 +94,34 @@ __device__ __forceinline__ void stage_load3_a(Staging3<TM> &s, const float *__re
   }
 }
 
-template <int TM>
-__device__ __forceinline__ void stage_store3(const Staging3<TM> &s, uint4 *stage, int srow) {
+template <int TM, int TN>
+__device__ __forceinline__ void stage_store3(const Staging3<TM, TN> &s, uint4 *stage, int srow) {
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) split_store(s.a[h], sa + 2 * kRPP * h);
   uint4 *sb = stage + kOperandChunks + threadIdx.x;
 #pragma unroll
-  for (int p = 0; p < kBChunksPerThread; ++p) sb[p * kPlaneChunks] = s.b[p];
+  for (int i = 0; i < b_copies(TN); ++i)
+    if (b_copy_live<TN>(i)) sb[i * kThreads] = s.b[i];
 }
 
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.  k_loop calls load for kt = 0, 1, 2, ... in order, so the
 // cursor is simply stepped behind every one: it runs as far ahead of the MFMAs as the loads do and crosses a tap boundary
 // wherever that falls.  (Behind the last tile it stands at tap 9, which nothing reads.)
-template <int TM>
+template <int TM, int TN>
 struct Tile3 {
-  typedef Staging3<TM> Stg;
+  typedef Staging3<TM, TN> Stg;
+  static constexpr int WM = wave_blocks_m(TM, TN);
   const float *__restrict__ X;
   const uint4 *__restrict__ bsrc;
   int srow, W, dil, Cin;
   TapCursor cur;
   int64_t abase[TM / kRPP];
   unsigned mask[TM / kRPP];
-  f32x16 (&low)[TM / 64][2], (&acc)[TM / 64][2];
+  f32x16 (&low)[WM][2], (&acc)[WM][2];
   __device__ __forceinline__ void load(Stg &s, int kt) {
-    stage_load3_a<TM>(s, X, cur, abase, mask);
-    stage_load3_b<TM>(s, bsrc + (int64_t)kt * kTileChunks);
+    stage_load3_a<TM, TN>(s, X, cur, abase, mask);
+    stage_load3_b<TM, TN>(s, bsrc + (int64_t)kt * tile_chunks(TN));
     cur.c0 += kBK;
     if (cur.c0 == Cin) {
       cur.c0 = 0;
@@ -105,20 +129,20 @@ struct Tile3 {
       cur.shift = tap_shift(cur.tap, W, dil, Cin);
     }
   }
-  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM>(s, stage, srow); }
-  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM>(stage, low, acc); }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN>(s, stage, srow); }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN>(stage, low, acc); }
 };
 
-// One output tile of TM x 128 pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
+// One output tile of TM x TN pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
 // in front of the activation (store_block): the second convolution of a BasicBlock.
-template <int TM, int ACT, bool HAS_RES>
+template <int TM, int TN, int ACT, bool HAS_RES>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
                                              const float *__restrict__ R,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
                                              const float *__restrict__ var, const float *__restrict__ weight,
                                              const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W,
                                              int Cin, int N, int dil, int64_t m0, int tn, uint4 *lds) {
-  constexpr int WM = TM / 64, kRA = TM / kRPP;
+  constexpr int WM = wave_blocks_m(TM, TN), kRA = TM / kRPP;
   f32x16 acc[WM][2], low[WM][2];      // a0 b0 | the five smaller products (tile_mma): added in the epilogue
 #pragma unroll
   for (int i = 0; i < WM; ++i)
@@ -149,21 +173,21 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
     mask[h] = bits;
     abase[h] = mm * Cin + gkq;
   }
-  const uint4 *bsrc = Bp + (int64_t)tn * nk * kTileChunks + gt;
-  Tile3<TM> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
+  const uint4 *bsrc = Bp + (int64_t)tn * nk * tile_chunks(TN) + gt;
+  Tile3<TM, TN> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
     tile.abase[h] = abase[h];
     tile.mask[h] = mask[h];
   }
   k_loop<kDepth3x3>(tile, nk, lds);
-  // ---- epilogue: (+ conv bias) -> eval-mode InPlace-ABN formula (when there are statistics) -> activation ----
+  // ---- epilogue: (+ conv bias) -> eval-mode InPlace-ABN formula (when there are statistics) -> (+ residual) -> activation ----
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
+  const int wi = (wid / (TN / 64)) * (TM / waves_m(TN)), wj = (wid % (TN / 64)) * 64;      // tile_mma's wave map
   const bool full = m0 + TM <= M;
 #pragma unroll
   for (int bj = 0; bj < 2; ++bj) {
-    const int col = tn * kTN + wj + bj * 32 + (lane & 31);
+    const int col = tn * TN + wj + bj * 32 + (lane & 31);
     const bool bn = mean != nullptr;
     const float mu = bn ? mean[col] : 0.f, is = bn ? inv_std_of(var[col], eps) : 1.f;
     const float ga = bn && weight != nullptr ? fabsf(weight[col]) + eps : 1.f;     // bn.cu:153
@@ -190,78 +214,72 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 // the two accumulator sets of a 128 x 128 tile take 128 VGPRs and the kernel 238 (two staging sets: k_loop), so that form runs two workgroups per CU -- its
 // 64-row panels too: they are the same kernel.  !TALL: every panel is 64 pixels high (p_full = 0), 64 accumulator registers,
 // 148 VGPRs; three workgroups per CU, which is what 48 KB of LDS per workgroup and 168 registers admit.
+// TN = 64 is TALL with every panel 128 pixels high (a 64 x 64 tile would leave a wave 16 rows): 64 accumulator registers again,
+// so three workgroups per CU.
 // The waves-per-SIMD range states those residencies (2, 3) so that the register budget follows from them and not from the
 // launch bound alone (profiles/r15_kernel_resources.md).
-template <int ACT, bool TALL, bool HAS_RES>
-__global__ __launch_bounds__(kThreads, TALL ? 2 : kMinWG) __attribute__((amdgpu_waves_per_eu(TALL ? 2 : kMinWG, TALL ? 2 : kMinWG)))
+constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kMinWG; }
+
+template <int TN, int ACT, bool TALL, bool HAS_RES>
+__global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
+__attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
     const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y, const float *__restrict__ cbias,
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
     const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil, int tiles_n,
     int p_full, const float *__restrict__ R) {
+  static_assert(TALL || TN == kTN, "64-row panels exist for the 128-column form only");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
   const int64_t tm = (int64_t)pl * 8 + xcd;
-  if (TALL && tm < p_full) {
+  if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
-  } else {
+    conv3x3_tile<kTM, TN, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+  } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
-}
-
-// The three bf16 planes of one 16-byte chunk (8 consecutive k of one row) written to their places in the packed image.
-__device__ __forceinline__ void pack_chunk_store(const float (&v)[8], uint4 *__restrict__ pack, int64_t tile, int chunk) {
-  uint2 lo[3], hi[3];
-  split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
-  split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
-#pragma unroll
-  for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * kPlaneChunks + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
 // The weight split, of a frozen network (once) and of the training form (per step, include/skd_train.h): ONE launch writes the
 // image of W (Cout, Cin, 3, 3) for the forward convolution and / or the image of Wd[c][n][ty][tx] = W[n][c][2 - ty][2 - tx]
 // (Cin, Cout, 3, 3) for the data gradient, both read from W through its strides (elements) -- contiguous and channels-last
-// tensors give the same pack, and Wd is index arithmetic, never a tensor.  One workgroup of kPlaneChunks threads per (column tile,
+// tensors give the same pack, and Wd is index arithmetic, never a tensor.  One workgroup of 2 TN threads per (column tile,
 // K-tile) of one image, one thread per 16-byte chunk (the 8 consecutive k of one row, three pieces), so the direction is uniform
 // per workgroup: the first `fwd_tiles` workgroups write the forward image (8 k = one tap, 8 channels of one output channel), the
-// others the backward image.  There the rows of a tile are 128 input channels c and the 8 consecutive k of a chunk are 8 output channels n at stride sn:
+// others the backward image.  There the rows of a tile are TN input channels c and the 8 consecutive k of a chunk are 8 output channels n at stride sn:
 // a wave's 64 lanes are 64 consecutive c, so each of its eight loads reads a run of 64 elements at stride sc -- 256 contiguous
 // bytes of a channels-last weight (sc = 1: the training student's, and the PSP bottleneck's channel slice).
-__global__ __launch_bounds__(kPlaneChunks) void conv3x3_pack_pair_kernel(
+template <int TN>
+__global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
     const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int Cout, int64_t fwd_tiles,
     uint4 *__restrict__ pack_fwd, uint4 *__restrict__ pack_bwd) {
   const int chunk = threadIdx.x;
-  const int kh = chunk >> 7, row = (chunk & 127) ^ (kh * 4);
+  const int kh = chunk / TN, row = (chunk % TN) ^ (kh * 4);
+  const bool fwd = (int64_t)blockIdx.x < fwd_tiles;
+  const int64_t tile = fwd ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - fwd_tiles;      // = column tile * nk + kt
+  const int K9 = fwd ? Cin : Cout;                                                      // channels per tap of this image's K
+  const int nk = 9 * (K9 / kBK);
+  const int kt = (int)(tile % nk), tn = (int)(tile / nk);
+  const int k0 = kt * kBK + kh * 8, tap = k0 / K9, e0 = k0 - tap * K9;
+  const int ty = fwd ? tap / 3 : 2 - tap / 3, tx = fwd ? tap % 3 : 2 - tap % 3;         // backward: the flipped tap
+  const int64_t srow = fwd ? sn : sc, sk = fwd ? sc : sn;                               // backward: rows are c, k runs over n
+  const float *src = Wt + (int64_t)(tn * TN + row) * srow + ty * sy + tx * sx;
   float v[8];
-  if ((int64_t)blockIdx.x < fwd_tiles) {
-    const int64_t tile = blockIdx.x;                      // = tn * nk + kt, K = 9 * Cin
-    const int nk = 9 * (Cin / kBK);
-    const int kt = (int)(tile % nk), tn = (int)(tile / nk);
-    const int k0 = kt * kBK + kh * 8, tap = k0 / Cin, c0 = k0 - tap * Cin;
-    const int ty = tap / 3, tx = tap - 3 * ty;
-    const float *src = Wt + (int64_t)(tn * kTN + row) * sn + ty * sy + tx * sx;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = src[(c0 + i) * sc];
-    pack_chunk_store(v, pack_fwd, tile, chunk);
-  } else {
-    const int64_t tile = (int64_t)blockIdx.x - fwd_tiles;  // = tc * nk + kt, K = 9 * Cout
-    const int nk = 9 * (Cout / kBK);
-    const int kt = (int)(tile % nk), tc = (int)(tile / nk);
-    const int k0 = kt * kBK + kh * 8, tap = k0 / Cout, n0 = k0 - tap * Cout;
-    const int ty = 2 - tap / 3, tx = 2 - tap % 3;         // the flipped tap
-    const float *src = Wt + (int64_t)(tc * kTN + row) * sc + ty * sy + tx * sx;
+  for (int i = 0; i < 8; ++i) v[i] = src[(e0 + i) * sk];
+  uint2 lo[3], hi[3];
+  split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
+  split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
+  uint4 *pack = fwd ? pack_fwd : pack_bwd;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = src[(n0 + i) * sn];
-    pack_chunk_store(v, pack_bwd, tile, chunk);
-  }
+  for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int ACT, bool TALL, bool HAS_RES>
+template <int TN, int ACT, bool TALL, bool HAS_RES>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                    int geometry, hipStream_t st) {
@@ -269,11 +287,11 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<ACT, TALL, HAS_RES>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kConvLds) != hipSuccess) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN)) != hipSuccess) return 0;
     *rdy = true;
   }
-  const int tiles_n = N / kTN;
+  const int tiles_n = N / TN;
   const int64_t tiles_m = cdiv(M, kTM);
   // TALL: 128-row panels p < p_full, 64-row panels behind them.  geometry 1: all 128; geometry 3: 128 for the launch's whole
   // rounds (two workgroups per CU) and 64 for the rest
@@ -285,7 +303,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<ACT, TALL, HAS_RES><<<dim3((unsigned)grid), dim3(kThreads), kConvLds, st>>>(
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN), st>>>(
       X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R);
   return ok();
 }
@@ -295,81 +313,81 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // profiles/r12_conv3x3_isolated.md (tools/conv3x3_bench.py) has every geometry per shape: on the four routed shapes 3 is 6-14 %
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
-template <int ACT, bool HAS_RES>
+// TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
+template <int TN, int ACT, bool HAS_RES>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st) {
-  if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
-  if (geometry == 1 || geometry == 3)
-    return launch3<ACT, true, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
-  return launch3<ACT, false, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+  if constexpr (TN < kTN) {
+    return launch3<TN, ACT, true, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, 1, st);
+  } else {
+    if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
+    if (geometry == 1 || geometry == 3)
+      return launch3<TN, ACT, true, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+    return launch3<TN, ACT, false, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+  }
 }
 
-}  // namespace
-}  // namespace skd
+// ---- the host bodies of the two entry families (TN = 128: skd_conv3x3_split_*, TN = 64: skd_conv3x3_narrow_*) ----
 
-using namespace skd;
-
-extern "C" {
-
-int skd_conv3x3_split_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
-  return Cin > 0 && Cout > 0 && Cin % kBK == 0 && Cout % kTN == 0 && stride == 1 && dilation >= 1 && padding == dilation && groups == 1;
+template <int TN>
+static int supported3(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return Cin > 0 && Cout > 0 && Cin % kBK == 0 && Cout % TN == 0 && stride == 1 && dilation >= 1 && padding == dilation && groups == 1;
 }
 
-int64_t skd_conv3x3_split_pack_bytes(int Cin, int Cout) {
-  if (!skd_conv3x3_split_supported(Cin, Cout, 1, 1, 1, 1)) return 0;
-  return (int64_t)(Cout / kTN) * (9 * (Cin / kBK)) * kTileChunks * (int64_t)sizeof(uint4);
-}
-
-int skd_conv3x3_split_train_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
-  return skd_conv3x3_split_supported(Cin, Cout, stride, padding, dilation, groups) && Cin % kTN == 0;
+template <int TN>
+static int64_t pack_bytes3(int Cin, int Cout) {
+  if (!supported3<TN>(Cin, Cout, 1, 1, 1, 1)) return 0;
+  return (int64_t)(Cout / TN) * (9 * (Cin / kBK)) * tile_chunks(TN) * (int64_t)sizeof(uint4);
 }
 
 // The (column tile, K-tile) count of the image of an (N, K / 9, 3, 3) weight in `pack`, 0 for no image (pack == nullptr), -1
 // for an image that is refused: a direction the core does not take, a buffer too small or not 16-byte aligned.
+template <int TN>
 static int64_t pack_image_tiles(int K9, int N, const void *pack, int64_t pack_bytes) {
   if (!pack) return 0;
-  const int64_t need = skd_conv3x3_split_pack_bytes(K9, N);
+  const int64_t need = pack_bytes3<TN>(K9, N);
   if (need == 0 || pack_bytes < need || (reinterpret_cast<uintptr_t>(pack) & 15)) return -1;
-  return (int64_t)(N / kTN) * (9 * (K9 / kBK));
+  return (int64_t)(N / TN) * (9 * (K9 / kBK));
 }
 
 // Either image or both in one launch (include/skd_train.h); every refusal is decided here, in front of the launch.
-int skd_conv3x3_split_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
-                                int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
-                                skd_stream_t stream) {
+template <int TN>
+static int pack_pair3(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y, int64_t stride_x,
+                      void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes, skd_stream_t stream) {
   if (!w || (!pack_fwd && !pack_bwd)) return 0;
   if (stride_n < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0) return 0;
-  const int64_t fwd_tiles = pack_image_tiles(Cin, Cout, pack_fwd, fwd_bytes);
-  const int64_t bwd_tiles = pack_image_tiles(Cout, Cin, pack_bwd, bwd_bytes);
+  const int64_t fwd_tiles = pack_image_tiles<TN>(Cin, Cout, pack_fwd, fwd_bytes);
+  const int64_t bwd_tiles = pack_image_tiles<TN>(Cout, Cin, pack_bwd, bwd_bytes);
   if (fwd_tiles < 0 || bwd_tiles < 0 || fwd_tiles + bwd_tiles > 2147483647) return 0;
-  conv3x3_pack_pair_kernel<<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(kPlaneChunks), 0, as_stream(stream)>>>(
+  conv3x3_pack_pair_kernel<TN><<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(2 * TN), 0, as_stream(stream)>>>(
       w, stride_n, stride_c, stride_y, stride_x, Cin, Cout, fwd_tiles, static_cast<uint4 *>(pack_fwd),
       static_cast<uint4 *>(pack_bwd));
   return ok();
 }
 
-// The forward image alone (include/skd_eval.h): the same launch without a backward image.
-int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
-                                   int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
-  return skd_conv3x3_split_pack_pair(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
-}
-
-// The shared body of the two entries; residual == nullptr takes the instantiations without the residual read.
-static int conv3x3_split_run(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
-                             const float *residual, const float *conv_bias, const float *mean, const float *var,
-                             const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
-                             skd_stream_t stream) {
-  if (!skd_conv3x3_split_supported(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
-  if (!x || !wpack || !out || (mean == nullptr) != (var == nullptr) || geometry < 0 || geometry > 3) return 0;
+// out = act(ABN_eval(conv3x3(x) + conv_bias) [+ residual]); residual == nullptr takes the instantiations without the residual
+// read.  The kernel reads the residual through a __restrict__ pointer at the offsets it writes, so a residual that overlaps the
+// output is refused, not defined.
+template <int TN>
+static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                const float *residual, const float *conv_bias, const float *mean, const float *var, const float *weight,
+                const float *bias, float eps, int activation, float slope, int geometry, int max_geometry, skd_stream_t stream) {
+  if (!supported3<TN>(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
+  if (!x || !wpack || !out || (mean == nullptr) != (var == nullptr) || geometry < 0 || geometry > max_geometry) return 0;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack)) & 15) return 0;
   if ((int64_t)H * W > 2147483647 || dilation > (1 << 24)) return 0;
   const int64_t M = (int64_t)B * H * W;
+  if (residual != nullptr) {
+    const uintptr_t bytes = (uintptr_t)M * Cout * sizeof(float);
+    const uintptr_t r = reinterpret_cast<uintptr_t>(residual), o = reinterpret_cast<uintptr_t>(out);
+    if (r < o + bytes && o < r + bytes) return 0;
+  }
   hipStream_t st = as_stream(stream);
   const uint4 *bp = static_cast<const uint4 *>(wpack);
 #define SKD_CONV3X3_CASE(ACT)                                                                                                 \
   case ACT:                                                                                                                   \
-    return (residual != nullptr ? launch3g<ACT, true> : launch3g<ACT, false>)(                                               \
+    return (residual != nullptr ? launch3g<TN, ACT, true> : launch3g<TN, ACT, false>)(                                       \
         x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
   switch (activation) {
     SKD_CONV3X3_CASE(SKD_ACT_NONE);
@@ -380,26 +398,70 @@ static int conv3x3_split_run(int B, int H, int W, int Cin, int Cout, int dilatio
 #undef SKD_CONV3X3_CASE
 }
 
+}  // namespace
+}  // namespace skd
+
+using namespace skd;
+
+extern "C" {
+
+int skd_conv3x3_split_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return supported3<kTN>(Cin, Cout, stride, padding, dilation, groups);
+}
+
+int64_t skd_conv3x3_split_pack_bytes(int Cin, int Cout) { return pack_bytes3<kTN>(Cin, Cout); }
+
+int skd_conv3x3_split_train_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return supported3<kTN>(Cin, Cout, stride, padding, dilation, groups) && Cin % kTN == 0;
+}
+
+int skd_conv3x3_split_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
+                                skd_stream_t stream) {
+  return pack_pair3<kTN>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack_fwd, fwd_bytes, pack_bwd, bwd_bytes, stream);
+}
+
+// The forward image alone (include/skd_eval.h): the same launch without a backward image.
+int skd_conv3x3_split_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                   int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
+  return pack_pair3<kTN>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
+}
+
 int skd_conv3x3_split_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
                            const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
                            float eps, int activation, float slope, int geometry, skd_stream_t stream) {
-  return conv3x3_split_run(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation,
-                           slope, geometry, stream);
+  return run3<kTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation, slope,
+                   geometry, 3, stream);
 }
 
-// out = act(ABN_eval(conv3x3(x) + conv_bias) + residual) (include/skd_infer.h).  The kernel reads the residual through a
-// __restrict__ pointer at the offsets it writes, so a residual that overlaps the output is refused, not defined.
+// include/skd_infer.h: the same with the residual pointer.
 int skd_conv3x3_split_res_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
                                const float *residual, const float *conv_bias, const float *mean, const float *var,
                                const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
                                skd_stream_t stream) {
-  if (residual != nullptr && out != nullptr && B >= 1 && H >= 1 && W >= 1 && Cout >= 1) {
-    const uintptr_t bytes = (uintptr_t)B * H * W * Cout * sizeof(float);
-    const uintptr_t r = reinterpret_cast<uintptr_t>(residual), o = reinterpret_cast<uintptr_t>(out);
-    if (r < o + bytes && o < r + bytes) return 0;
-  }
-  return conv3x3_split_run(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation,
-                           slope, geometry, stream);
+  return run3<kTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation, slope,
+                   geometry, 3, stream);
+}
+
+// include/skd_narrow.h: the 64-column form.
+int skd_conv3x3_narrow_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return supported3<kNarrowTN>(Cin, Cout, stride, padding, dilation, groups);
+}
+
+int64_t skd_conv3x3_narrow_pack_bytes(int Cin, int Cout) { return pack_bytes3<kNarrowTN>(Cin, Cout); }
+
+int skd_conv3x3_narrow_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                 int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
+                                 skd_stream_t stream) {
+  return pack_pair3<kNarrowTN>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack_fwd, fwd_bytes, pack_bwd, bwd_bytes, stream);
+}
+
+int skd_conv3x3_narrow_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                            const float *residual, const float *conv_bias, const float *mean, const float *var,
+                            const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
+                            skd_stream_t stream) {
+  return run3<kNarrowTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation,
+                         slope, geometry, 1, stream);
 }
 
 }  // extern "C"

@@ -71,25 +71,32 @@ __device__ __forceinline__ int plane_slot(int row, int gkq) {
 // One K-tile out of LDS: 3 (WM + 2) conflict-free ds_read_b128 (the lane's 8 k of its row, per piece and 32-row block) feed
 // 6 * 2 WM bf16 MFMAs: the six products a_i b_j with i + j <= 2, the three smallest first, the four accumulator blocks of the
 // wave in turn inside every product (no MFMA waits for its predecessor's result).
-// Waves 2 x 2, wave tile (TM / 2) x 64 = WM x 2 blocks of 32 x 32 (WM = TM / 64).
+// The four waves of a TM x TN tile (TN = 128 or 64 columns): TN / 64 across N, the others across M, each a wave tile of
+// (TM / waves across M) x 64 = WM x 2 blocks of 32 x 32 -- waves 2 x 2 and WM = TM / 64 for TN = 128, waves 4 x 1 and WM = TM / 128
+// for TN = 64.  The B image has TN rows: chunk(h, row) = h * TN + (row ^ 4 h), 2 TN chunks per piece.
 // The five products below a0 b0 go into `lo`, a0 b0 into `hi`.  One accumulator for both (conv1x1.hip: lo and hi are the same
 // array) rounds six times per 16 k at the magnitude of the running sum; two accumulators (conv3x3.hip, K up to 18432) round
 // once per 16 k at that magnitude and five times at 2^-8 of it, and are added in the epilogue.
-template <int TM>
-__device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[TM / 64][2], f32x16 (&hi)[TM / 64][2]) {
-  constexpr int WM = TM / 64;
+constexpr int waves_m(int TN) { return 4 / (TN / 64); }                           // waves across M
+constexpr int wave_blocks_m(int TM, int TN) { return TM / waves_m(TN) / 32; }       // WM
+
+template <int TM, int TN = kTN>
+__device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_blocks_m(TM, TN)][2],
+                                         f32x16 (&hi)[wave_blocks_m(TM, TN)][2]) {
+  constexpr int WM = wave_blocks_m(TM, TN);
+  static_assert((TN == 64 || TN == 128) && WM >= 1, "one or two of the four waves across N, a wave tile of at least 32 rows");
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
+  const int wi = (wid / (TN / 64)) * (TM / waves_m(TN)), wj = (wid % (TN / 64)) * 64;
   const int half = lane >> 5, r = lane & 31;
   const uint4 *pa = stage + half * 128 + ((wi + r) ^ (half * 4));
-  const uint4 *pb = stage + kOperandChunks + half * 128 + ((wj + r) ^ (half * 4));
+  const uint4 *pb = stage + kOperandChunks + half * TN + ((wj + r) ^ (half * 4));
   bf16x8 a[WM][3], b[2][3];
 #pragma unroll
   for (int p = 0; p < 3; ++p) {
 #pragma unroll
     for (int i = 0; i < WM; ++i) a[i][p] = __builtin_bit_cast(bf16x8, pa[p * kPlaneChunks + 32 * i]);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(bf16x8, pb[p * kPlaneChunks + 32 * j]);
+    for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(bf16x8, pb[p * 2 * TN + 32 * j]);
   }
   constexpr int kPA[6] = {0, 1, 2, 0, 1, 0}, kPB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll

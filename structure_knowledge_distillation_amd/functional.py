@@ -783,42 +783,27 @@ def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
                        query="skd_conv3x3_split_train_supported", host_ok=True)
 
 
-def _conv3x3_packs(w, owner, attr, entry, both, what, images=None, bytes_entry="skd_conv3x3_split_pack_bytes"):
+def _conv3x3_packs(w, owner, attr, entry, what, images, bytes_entry="skd_conv3x3_split_pack_bytes"):
     """The image(s) of the (Cout, Cin, 3, 3) weight ``w`` that csrc/conv3x3.hip streams into LDS, written by one launch of
     ``entry`` and cached on ``owner`` as ``(key, *packs, storage)`` with ``key = (data_ptr, _version, shape, stride)``.
-    ``images = (forward?, backward?)``: ``entry`` is one of the two pack_pair entries (skd_train.h, skd_narrow.h) and writes the
-    chosen image(s) alone -- ``(pack_fwd, pack_bwd)`` with None for the one not asked for, sized by ``bytes_entry``."""
-    def build_images():
+    ``images`` has one flag per (pointer, bytes) pair that ``entry`` takes, forward image first: ``(True,)`` for
+    skd_conv3x3_split_pack_weights, ``(forward?, backward?)`` for the two pack_pair entries (skd_train.h, skd_narrow.h), which
+    write the chosen image(s) alone.  One pack per flag, None for an image not asked for, each sized by ``bytes_entry`` for its
+    direction; a direction the entry's form does not take (size 0) is a ValueError."""
+    def build():
         _lib.require_device(w)
         cout, cin = int(w.shape[0]), int(w.shape[1])
         lib = _lib.get()
-        if tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32 or not any(images):
-            raise ValueError("%s: unsupported weight %s" % (what, tuple(w.shape)))
         sizes = [int(getattr(lib, bytes_entry)(*dims)) if want else None for want, dims in zip(images, ((cin, cout), (cout, cin)))]
-        if any(n is not None and n <= 0 for n in sizes):
+        if (tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32 or not any(images)
+                or any(n is not None and n <= 0 for n in sizes)):
             raise ValueError("%s: unsupported weight %s" % (what, tuple(w.shape)))
         with torch.no_grad():
             packs = tuple(None if n is None else torch.empty((n,), dtype=torch.uint8, device=w.device) for n in sizes)
             sized = [v for pk, n in zip(packs, sizes) for v in ((None, 0) if pk is None else (pk.data_ptr(), n))]
             _lib.check(getattr(lib, entry)(cin, cout, w.data_ptr(), *(int(v) for v in w.stride()), *sized, _lib.stream_of(w)), entry)
         return packs
-
-    def build():
-        _lib.require_device(w)
-        cout, cin = int(w.shape[0]), int(w.shape[1])
-        lib = _lib.get()
-        nbytes = int(lib.skd_conv3x3_split_pack_bytes(cin, cout))
-        if (nbytes <= 0 or tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32
-                or (both and not lib.skd_conv3x3_split_train_supported(cin, cout, 1, 1, 1, 1))):
-            raise ValueError("%s: unsupported weight %s" % (what, tuple(w.shape)))
-        with torch.no_grad():
-            packs = tuple(torch.empty((nbytes,), dtype=torch.uint8, device=w.device) for _ in range(1 + both))
-            sized = [v for pk in packs for v in (pk.data_ptr(), nbytes)]
-            _lib.check(getattr(lib, entry)(cin, cout, w.data_ptr(), *(int(v) for v in w.stride()), *sized, _lib.stream_of(packs[0])),
-                       entry)
-        return packs
-    return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build if images is None else build_images,
-                   hold=w)
+    return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build, hold=w)
 
 
 def conv3x3_pack_weights(conv, weight=None, owner=None):
@@ -832,8 +817,8 @@ def conv3x3_pack_weights(conv, weight=None, owner=None):
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_pack_weights is for frozen (no-grad) convolutions")
-    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_pack", "skd_conv3x3_split_pack_weights", False,
-                          "conv3x3_pack_weights")[0]
+    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_pack", "skd_conv3x3_split_pack_weights",
+                          "conv3x3_pack_weights", (True,))[0]
 
 
 def conv3x3_train_packs(weight, owner=None):
@@ -843,12 +828,13 @@ def conv3x3_train_packs(weight, owner=None):
     as conv3x3_pack_weights does: one split per weight version, so once per optimizer step -- provided the optimizer advances
     ``_version`` (torch's fused multi-tensor optimizers do not: networks.kd_model.advance_versions_after_step is the step
     post-hook that does it for them)."""
-    return _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack", "skd_conv3x3_split_pack_pair", True, "conv3x3_train_packs")
+    return _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack", "skd_conv3x3_split_pack_pair", "conv3x3_train_packs",
+                          (True, True))
 
 
 _ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
 _RES_ENTRY = "skd_conv3x3_split_res_nhwc"
-# include/skd_narrow.h (csrc/conv3x3_narrow.hip): the 64-column form.  Its one convolution entry takes the residual pointer.
+# include/skd_narrow.h: the 64-column form of csrc/conv3x3.hip.  Its one convolution entry takes the residual pointer.
 _NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
 _NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
 _NARROW_PACK_ATTRS = ("_skd_conv3x3_narrow_pack", "_skd_conv3x3_train_pack_wide", "_skd_conv3x3_train_pack_narrow")
@@ -877,6 +863,17 @@ def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, act
     return out
 
 
+def _residual_cl(x, cout, residual):
+    """The residual of a split-core 3x3 launch on ``x`` with ``cout`` output channels: None, or a (B, cout, H, W) fp32 tensor,
+    returned in channels-last memory (copied when it is not)."""
+    if residual is None:
+        return None
+    want = (x.shape[0], cout) + tuple(x.shape[2:])
+    if tuple(residual.shape) != want or residual.dtype != torch.float32:
+        raise ValueError("residual %s %s != output %s fp32" % (tuple(residual.shape), residual.dtype, want))
+    return _cl(residual)
+
+
 def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0):
     """act(bn_running(conv3x3(x) + conv_bias)) with ``pack = conv3x3_pack_weights(...)`` (inference only; conv3x3_split_supported
     says when).  fp32 in and out, channels-last; the products run on the bf16 MFMA through the three-piece split (csrc/conv3x3.hip):
@@ -899,12 +896,8 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
         raise RuntimeError("conv3x3_split_res_eval is inference-only")
     if not _lib.has_entry(_RES_ENTRY):
         raise NotImplementedError("this back-end has no skd_conv3x3_split_res_nhwc (include/skd_infer.h)")
-    if residual is not None:
-        want = (x.shape[0], cout) + tuple(x.shape[2:])
-        if tuple(residual.shape) != want or residual.dtype != torch.float32:
-            raise ValueError("residual %s %s != output %s fp32" % (tuple(residual.shape), residual.dtype, want))
-        residual = _cl(residual)
-    return _conv3x3_launch(_RES_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry, residual)
+    return _conv3x3_launch(_RES_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
+                           _residual_cl(x, cout, residual))
 
 
 def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None):
@@ -918,7 +911,7 @@ def _conv3x3_narrow_launch(x, pack, cout, dilation, conv_bias=None):
 
 
 def conv3x3_narrow_supported(x, conv, residual=False):
-    """True when the 64-column form of the split-core 3x3 convolution (csrc/conv3x3_narrow.hip, include/skd_narrow.h) takes
+    """True when the 64-column form of the split-core 3x3 convolution (csrc/conv3x3.hip, include/skd_narrow.h) takes
     ``conv(x)`` of a frozen forward: no grad, a back-end that has the four entries (the tests' C double does not: callers then run
     what they ran before), an fp32 channels-last 16-byte-aligned input, a plain 3x3 / stride-1 / padding == dilation / ungrouped
     convolution with Cin a multiple of 16 and Cout of 64.  ``residual``: the one entry takes it, so the answer is the same.
@@ -933,25 +926,21 @@ def conv3x3_narrow_pack_weights(conv, weight=None, owner=None):
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_narrow_pack_weights is for frozen (no-grad) convolutions")
-    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_narrow_pack", _NARROW_PACK_PAIR, False,
-                          "conv3x3_narrow_pack_weights", images=(True, False), bytes_entry="skd_conv3x3_narrow_pack_bytes")[0]
+    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_narrow_pack", _NARROW_PACK_PAIR,
+                          "conv3x3_narrow_pack_weights", (True, False), "skd_conv3x3_narrow_pack_bytes")[0]
 
 
 def conv3x3_narrow_eval(x, pack, cout, dilation, residual=None, conv_bias=None, bn=None, activation="none", geometry=0):
-    """act(bn_running(conv3x3(x) + conv_bias) [+ residual]) in one launch of csrc/conv3x3_narrow.hip (inference only) with
-    ``pack = conv3x3_narrow_pack_weights(...)``: conv3x3_split_eval / conv3x3_split_res_eval for a Cout that is a multiple of 64.
-    The arithmetic of every output element is the wide kernel's, in its order: where both take a convolution they give the same
-    bits.  ``residual`` (B, cout, H, W) fp32 is read in channels-last memory (copied when it is not) and never written."""
+    """act(bn_running(conv3x3(x) + conv_bias) [+ residual]) in one launch of csrc/conv3x3.hip's 64-column form (inference
+    only), with ``pack = conv3x3_narrow_pack_weights(...)``: conv3x3_split_eval / conv3x3_split_res_eval for a Cout that is a
+    multiple of 64.  The arithmetic of every output element is that of the 128-column form, in its order: where both take a
+    convolution they give the same bits.  ``residual`` (B, cout, H, W) fp32 is read in channels-last memory (copied when it is not) and never written."""
     if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
         raise RuntimeError("conv3x3_narrow_eval is inference-only")
     if not _lib.has_entry(_NARROW_ENTRY):
         raise NotImplementedError("this back-end has no skd_conv3x3_narrow_nhwc (include/skd_narrow.h)")
-    if residual is not None:
-        want = (x.shape[0], cout) + tuple(x.shape[2:])
-        if tuple(residual.shape) != want or residual.dtype != torch.float32:
-            raise ValueError("residual %s %s != output %s fp32" % (tuple(residual.shape), residual.dtype, want))
-        residual = _cl(residual)
-    return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry, residual)
+    return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
+                           _residual_cl(x, cout, residual))
 
 
 def conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups):
@@ -974,10 +963,10 @@ def _conv3x3_narrow_train_packs(weight, owner):
         return conv3x3_train_packs(weight, owner) + narrow
     wide = (None, None)
     if not all(narrow):
-        wide = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_wide", "skd_conv3x3_split_pack_pair", False,
-                              "conv3x3_split_train", images=(not narrow[0], not narrow[1]))
-    thin = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_narrow", _NARROW_PACK_PAIR, False, "conv3x3_split_train",
-                          images=narrow, bytes_entry="skd_conv3x3_narrow_pack_bytes")
+        wide = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_wide", "skd_conv3x3_split_pack_pair", "conv3x3_split_train",
+                              (not narrow[0], not narrow[1]))
+    thin = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_narrow", _NARROW_PACK_PAIR, "conv3x3_split_train", narrow,
+                          "skd_conv3x3_narrow_pack_bytes")
     return tuple(t if n else v for t, v, n in zip(thin, wide, narrow)) + narrow
 
 
@@ -1092,7 +1081,7 @@ def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=Fal
     bias is added in the forward's epilogue.  ``wgrad=True`` (opt-in): the weight gradient runs on the split core too
     (conv3x3_split_wgrad) where the back-end has the entries of include/skd_wgrad.h; the bias gradient stays with the library.
     ``narrow=True`` (opt-in; conv3x3_narrow_train_supported says when): each direction is chosen by its N -- Cout for the forward,
-    Cin for the data gradient: the wide kernel for a multiple of 128, csrc/conv3x3_narrow.hip otherwise -- which takes one pack
+    Cin for the data gradient: the 128-column tiles for a multiple of 128, the 64-column ones otherwise -- which takes one pack
     launch per entry and weight version; the weight gradient of a shape with a 64-channel side stays with the library."""
     if narrow:
         pack_fwd, pack_bwd, fwd_narrow, bwd_narrow = _conv3x3_narrow_train_packs(weight, owner)

@@ -175,8 +175,8 @@ class NetModel():
         # args.fused_eval: the student's eval-mode / no-grad forwards (validation between epochs, evaluate_main) take the fused
         # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
         # args.split_narrow (None: SKD_SPLIT_NARROW, default "0"): the 64-channel 3x3 convolutions of the stem and layer1 on the
-        # split core too (csrc/conv3x3_narrow.hip) -- in the fused inference form together with fused_eval, in training together
-        # with split_train; alone it routes nothing.  Off by default (profiles/r21_conv3x3_narrow_isolated.md, profiles/r21_step_ab.md).
+        # split core too (the 64-column form of csrc/conv3x3.hip) -- in the fused inference form together with fused_eval, in
+        # training together with split_train; alone it routes nothing.  Off by default (profiles/r21_conv3x3_narrow_isolated.md, profiles/r21_step_ab.md).
         split_narrow = getattr(args, "split_narrow", None)
         if split_narrow is None:
             split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"

@@ -7,7 +7,7 @@ and ``forward`` returns the same 7-element list ``[logits, dsn, feat_after_psp, 
 stride-1 3x3 convolutions (csrc/conv3x3.hip), the student's 3x3 convolutions in its inference form (fuse_for_inference) and, opt-in,
 the training student's stride-1 3x3 convolutions and their data gradients (route_training_convs; the weight gradients stay on
 MIOpen unless its ``wgrad`` is set: csrc/conv3x3_wgrad.hip; the 64-channel convolutions of the stem and layer1 only with ``narrow``:
-csrc/conv3x3_narrow.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
+the 64-column form of csrc/conv3x3.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
 csrc/abn*.hip (``libs``), applied in place on the conv output.
 """
 import functools
@@ -85,7 +85,7 @@ TRAIN_ROUTING_EXCLUDED = frozenset()
 WGRAD_ROUTING_EXCLUDED = frozenset()
 # The 64-channel convolutions (fuse_for_inference(narrow=True), route_training_convs(narrow=True); a further opt-in on top of either):
 # the stem's conv2 (64 -> 64) and layer1's four convolutions (128 -> 64, then three 64 -> 64) on the 64-column form of the kernel
-# (csrc/conv3x3_narrow.hip), the stem's conv3 (64 -> 128) on the wide kernel in the forward and on the narrow one for its data
+# (csrc/conv3x3.hip with 64-column tiles), the stem's conv3 (64 -> 128) on the wide kernel in the forward and on the narrow one for its data
 # gradient (layer1.0.conv1 the other way round).  These six are chosen by their channel counts -- multiples of 64 on both sides,
 # one of them not a multiple of 128 -- not by ``min_cin``.  A shape
 # that does not measure ahead of the library by more than the spread is listed here as (Cin, Cout, dilation, form), form =
@@ -175,7 +175,7 @@ def _conv3x3_split(x, conv):
 def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False):
     """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, for a call one of the
     SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names).  ``narrow``: the
-    64-column form (csrc/conv3x3_narrow.hip) on its own pack, for a call SF.conv3x3_narrow_supported accepted."""
+    64-column form (the same file, include/skd_narrow.h) on its own pack, for a call SF.conv3x3_narrow_supported accepted."""
     if narrow:
         return SF.conv3x3_narrow_eval(x, SF.conv3x3_narrow_pack_weights(conv), conv.out_channels, conv.dilation[0], residual, conv.bias,
                                       bn, activation)
@@ -556,7 +556,7 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
     every evaluation behind the first runs on stale packs.  The weights that
     are routed and already on the device are packed here, so a graph captured later allocates nothing for them.
     ``narrow=True`` (a further opt-in): the 64-channel convolutions as well, in the same kind of forward -- layer1's four on the
-    64-column form of the kernel (csrc/conv3x3_narrow.hip; BN + ReLU, and BN + residual + ReLU, in the epilogue), the stem's
+    64-column form of the kernel (include/skd_narrow.h; BN + ReLU, and BN + residual + ReLU, in the epilogue), the stem's
     conv2 on it with bn2 + ReLU in the epilogue, the stem's conv3 (64 -> 128) raw on the existing kernel in front of
     max_pool_stem and bn3 -- except the shapes of NARROW_ROUTING_EXCLUDED.  The stem is flagged on the ResNet itself.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
@@ -605,7 +605,7 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     csrc/conv3x3_wgrad.hip) except for the shapes of WGRAD_ROUTING_EXCLUDED; on a back-end without the entries of
     include/skd_wgrad.h they stay with the library.
     ``narrow=True``: the stem's conv2 / conv3 and layer1's four convolutions too (SF.conv3x3_split_train(..., narrow=True): each
-    direction on the wide kernel where its N is a multiple of 128, on csrc/conv3x3_narrow.hip otherwise; their weight gradients
+    direction on the 128-column form of the kernel where its N is a multiple of 128, on the 64-column one otherwise; their weight gradients
     stay with the library) except for the shapes of NARROW_ROUTING_EXCLUDED.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""

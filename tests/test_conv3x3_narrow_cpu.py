@@ -487,4 +487,4 @@ def test_netmodel_split_narrow_flag(monkeypatch):
 
 
 def test_docs_name_the_narrow_form():
-    assert "conv3x3_narrow.hip" in PC.__doc__ and "narrow" in PC.fuse_for_inference.__doc__ and "narrow" in PC.route_training_convs.__doc__
+    assert "conv3x3.hip" in PC.__doc__ and "64-column" in PC.__doc__ and "narrow" in PC.fuse_for_inference.__doc__ and "narrow" in PC.route_training_convs.__doc__

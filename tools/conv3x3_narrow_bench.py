@@ -1,6 +1,6 @@
 """GPU tool: the student's 64-channel 3x3 convolutions, isolated -- writes the tables of profiles/r21_conv3x3_narrow_isolated.md.
 Inference (batch 1, the shapes of a 1024 x 2048 forward): the MIOpen convolution followed by the library's eval-mode ABN pass (with
-the residual where the block has one) against ONE launch of the split core with that epilogue -- csrc/conv3x3_narrow.hip for
+the residual where the block has one) against ONE launch of the split core with that epilogue -- csrc/conv3x3.hip's 64-column form for
 Cout = 64, the existing kernel for the stem's conv3 (64 -> 128, raw).  Training (batch 8, the shapes of a 512 x 512 step): the
 forward (``F.conv2d``) and the data gradient (``aten.convolution_backward``, input only) against one launch each of the entry
 that direction's N chooses, plus the pack launches the training form pays once per step and weight.

@@ -2,7 +2,7 @@
 profiles/r21_conv3x3_narrow_accuracy.md -- per case of that test, on the test's own seeded inputs, max |got - want| / max |want|
 against ``F.conv2d`` (and its autograd) in float64 on the CPU of (a) the parent path: MIOpen's fp32 ``F.conv2d`` on the GPU
 followed by the library's eval-mode ABN pass (with the residual) where the case has an epilogue, MIOpen's backward-data kernel
-for the data gradients, and (b) the 64-column form of the split core (csrc/conv3x3_narrow.hip).
+for the data gradients, and (b) the 64-column form of the split core (csrc/conv3x3.hip, include/skd_narrow.h).
     python tools/conv3x3_narrow_parent_err.py
 """
 import os

@@ -1,5 +1,7 @@
 """GPU tool: the split-operand core's timed shapes (the four bottleneck-tail GEMMs, the nine reduce / down-sample GEMMs, the
-3x3 convolutions of tools/conv3x3_bench.py, all at batch 8) through the C ABI of one or more builds of libskd_hip.so, on the same
+3x3 convolutions of tools/conv3x3_bench.py, all at batch 8; in the conv3x3 set also one of those with BN + residual + ReLU, the
+64-column form at the five batch-1 inference shapes of tools/conv3x3_narrow_bench.py with their epilogues, and the weight images
+of both pack_pair entries) through the C ABI of one or more builds of libskd_hip.so, on the same
 seeded inputs: one SHA-256 of the output buffer per (shape, library) -- a change of the K loop's schedule must not move one --
 and, with --ms, HIP-event timings, the libraries taking turns inside every repeat.
 
@@ -27,6 +29,12 @@ REDUCE = [(1024, 256, 33800), (2048, 512, 33800), (512, 128, 33800), (1024, 512,
 CONV3 = [(256, 256, 65, 2, False), (2048, 512, 65, 1, False), (512, 512, 65, 4, False), (1024, 512, 65, 1, True),
          (128, 128, 65, 1, False)]                                                                     # (Cin, Cout, HW, dilation, bias)
 B = 8
+SPLIT, SPLIT_RES, NARROW = "skd_conv3x3_split", "skd_conv3x3_split_res", "skd_conv3x3_narrow"          # entry families
+# (entry, batch, H, W, Cin, Cout, dilation, epilogue): epilogue "bn" = BN + ReLU, "res" = BN + residual + ReLU, "raw" = none
+CONV3_EPI = [(SPLIT_RES, B, 65, 65, 256, 256, 2, "res"),
+             (NARROW, 1, 257, 513, 128, 64, 1, "bn"), (NARROW, 1, 257, 513, 64, 64, 1, "bn"), (NARROW, 1, 257, 513, 64, 64, 1, "res"),
+             (NARROW, 1, 512, 1024, 64, 64, 1, "bn"), (NARROW, 1, 512, 1024, 64, 128, 1, "raw")]
+PACKS = [(SPLIT, 128, 128), (SPLIT, 512, 256), (NARROW, 64, 64), (NARROW, 64, 128), (NARROW, 128, 64)]    # (entry, Cin, Cout): both images
 
 
 def main():
@@ -109,12 +117,46 @@ def main():
                                                                           None, None, 0.0, 0, 0.01, 0, None) or sys.exit("launch refused"))
         measure("conv3x3 %d->%d %dx%d d%d%s" % (cin, cout, hw, hw, d, " bias" if bias else ""), calls, out)
 
+    def conv3_epi(entry, b, h, w, cin, cout, d, epi):
+        """The entries that take the residual pointer (None unless epi == "res"), with the epilogue `epi`."""
+        torch.manual_seed(h + cin + cout + d)
+        x = torch.relu(rnd(b, h, w, cin))                                   # channels-last
+        wt = rnd(cout, cin, 3, 3) * (2.0 / (9 * cin)) ** 0.5
+        bn = [None] * 4 if epi == "raw" else [rnd(cout) * 0.3, torch.rand(cout, device=dev) + 0.5, rnd(cout), rnd(cout)]
+        r = rnd(b * h * w, cout) if epi == "res" else None
+        out = torch.empty(b * h * w, cout, device=dev)
+        calls, keep = [], []
+        for lib in libs:                                                    # every library packs for itself
+            nbytes = getattr(lib, entry.replace("_res", "") + "_pack_bytes")(cin, cout)
+            pk = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            assert getattr(lib, entry.replace("_res", "") + "_pack_pair")(cin, cout, p(wt), *wt.stride(), p(pk), nbytes, None, 0, None)
+            keep.append(pk)
+            calls.append(lambda run=getattr(lib, entry + "_nhwc"), pk=pk: run(
+                b, h, w, cin, cout, d, p(x), p(pk), p(out), p(r), None, *(p(t) for t in bn), 1e-5, 0 if epi == "raw" else RELU, 0.01, 0,
+                None) or sys.exit("launch refused"))
+        measure("%s %d->%d %dx%dx%d d%d %s" % (entry[4:], cin, cout, b, h, w, d, epi), calls, out)
+
+    def packs(entry, cin, cout):
+        """Both weight images of one pack_pair launch, forward image first, in one buffer."""
+        torch.manual_seed(cin * 3 + cout)
+        wt = rnd(cout, cin, 3, 3)
+        nf, nb = (getattr(libs[0], entry + "_pack_bytes")(*dims) for dims in ((cin, cout), (cout, cin)))
+        assert nf > 0 and nb > 0 and nf % 16 == 0
+        out = torch.empty(nf + nb, dtype=torch.uint8, device=dev)
+        mk = lambda lib: lambda: getattr(lib, entry + "_pack_pair")(cin, cout, p(wt), *wt.stride(), p(out), nf, p(out) + nf, nb,
+                                                                      None) or sys.exit("launch refused")
+        measure("%s_pack_pair %d->%d" % (entry[4:], cin, cout), [mk(lib) for lib in libs], out)
+
     for k, n, m in TAIL if args.only in ("", "tail") else []:
         gemm(k, n, m, True)
     for k, n, m in REDUCE if args.only in ("", "reduce") else []:
         gemm(k, n, m, False)
     for c in CONV3 if args.only in ("", "conv3x3") else []:
         conv3(*c)
+    for c in CONV3_EPI if args.only in ("", "conv3x3") else []:
+        conv3_epi(*c)
+    for c in PACKS if args.only in ("", "conv3x3") else []:
+        packs(*c)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ csrc/conv3x3.hip with that epilogue (``conv3x3_split_eval`` / ``conv3x3_split_re
 Whole forward -- the seeded student, batch 1 at 1024 x 2048, and the five-scale flip set of tools/multiscale_eval_bench.py (five
 batches of 2), each without ``fuse_for_inference`` and with it at every ``--min-cin`` (default: the frozen teacher's 256 and the
 shipped FUSED_EVAL_MIN_CIN), and with ``narrow=True`` on top of the shipped policy (the row "fused, narrow": the stem and layer1 on
-the split core too, csrc/conv3x3_narrow.hip).
+the split core too, the 64-column form of csrc/conv3x3.hip).
 
     python tools/student_infer_bench.py [--rounds 3] [--min-cin 256 128] [--skip-launches] [--out FILE]
 
