@@ -19,6 +19,7 @@ INFER_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_i
 TRAIN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_train.h"))
 WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_wgrad.h"))
 NARROW_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow.h"))
+NARROW_WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow_wgrad.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -209,6 +210,16 @@ NARROW_SIGNATURES = {
     "skd_conv3x3_narrow_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
 }
 
+# Entry points declared in include/skd_narrow_wgrad.h (csrc/conv3x3_wgrad.hip, the 128 x 64 tile form): the weight gradient of the
+# convolutions with a 64-channel side, extension entries in a table of their own like the six above
+# (tests/test_conv3x3_narrow_wgrad_cpu.py checks header <-> table <-> exported symbols, tests/test_conv3x3_narrow_wgrad_gpu.py
+# holds the guard-band cases).  A back-end without them leaves those weight gradients on the library: nothing raises.
+NARROW_WGRAD_SIGNATURES = {
+    "skd_conv3x3_narrow_wgrad_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "skd_conv3x3_narrow_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "skd_conv3x3_narrow_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -239,7 +250,7 @@ def load(path=None):
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
-                  WGRAD_SIGNATURES, NARROW_SIGNATURES):
+                  WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -60,6 +60,14 @@ __device__ __forceinline__ void split_store(float4 v, uint2 *dst) {
   dst[2 * kPlaneChunks] = p1;
   dst[4 * kPlaneChunks] = p2;
 }
+// ... the same for an image whose pieces lie `plane` 8-byte slots apart (a TN = 64 B image: 2 * 128)
+__device__ __forceinline__ void split_store(float4 v, uint2 *dst, int plane) {
+  uint2 p0, p1, p2;
+  split4(v, p0, p1, p2);
+  dst[0] = p0;
+  dst[plane] = p1;
+  dst[2 * plane] = p2;
+}
 
 // 8-byte slot, in uint2 units, of (row `row` < 64 + what the caller adds, k quad `gkq` = 0, 4, 8, 12) inside a plane; rows 64
 // apart are 128 slots apart.
@@ -74,13 +82,15 @@ __device__ __forceinline__ int plane_slot(int row, int gkq) {
 // The four waves of a TM x TN tile (TN = 128 or 64 columns): TN / 64 across N, the others across M, each a wave tile of
 // (TM / waves across M) x 64 = WM x 2 blocks of 32 x 32 -- waves 2 x 2 and WM = TM / 64 for TN = 128, waves 4 x 1 and WM = TM / 128
 // for TN = 64.  The B image has TN rows: chunk(h, row) = h * TN + (row ^ 4 h), 2 TN chunks per piece.
+// SWAP: the piece tables change sides -- product t is a_kPB[t] b_kPA[t] -- for a caller whose operands have changed sides
+// (conv3x3_wgrad.hip's 128 x 64 form: x is A, g is B) and whose sums must see the pieces in the other caller's order.
 // The five products below a0 b0 go into `lo`, a0 b0 into `hi`.  One accumulator for both (conv1x1.hip: lo and hi are the same
 // array) rounds six times per 16 k at the magnitude of the running sum; two accumulators (conv3x3.hip, K up to 18432) round
 // once per 16 k at that magnitude and five times at 2^-8 of it, and are added in the epilogue.
 constexpr int waves_m(int TN) { return 4 / (TN / 64); }                           // waves across M
 constexpr int wave_blocks_m(int TM, int TN) { return TM / waves_m(TN) / 32; }       // WM
 
-template <int TM, int TN = kTN>
+template <int TM, int TN = kTN, bool SWAP = false>
 __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_blocks_m(TM, TN)][2],
                                          f32x16 (&hi)[wave_blocks_m(TM, TN)][2]) {
   constexpr int WM = wave_blocks_m(TM, TN);
@@ -106,7 +116,7 @@ __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_b
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         f32x16 &dst = t < 5 ? lo[i][j] : hi[i][j];
-        dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][kPA[t]], b[j][kPB[t]], dst, 0, 0, 0);
+        dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SWAP ? kPB[t] : kPA[t]], b[j][SWAP ? kPA[t] : kPB[t]], dst, 0, 0, 0);
       }
 }
 template <int TM>

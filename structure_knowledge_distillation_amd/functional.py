@@ -1003,6 +1003,31 @@ def _non_overlapping_and_dense(t):
     return True
 
 
+def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilation, slices):
+    """The body conv3x3_split_wgrad and conv3x3_narrow_wgrad share: the checks, the plan call, the workspace, the layout of ``dw``
+    and the launch entry, on the pair of entries ``plan_entry`` / ``run_entry`` (skd_wgrad.h or skd_narrow_wgrad.h)."""
+    _lib.require_device(x, g)
+    lib = _lib.get()
+    b, cin, h, w = (int(v) for v in x.shape)
+    cout = int(g.shape[1])
+    if tuple(weight_like.shape) != (cout, cin, 3, 3) or tuple(g.shape) != (b, cout, h, w):
+        raise ValueError("%s: x %s, g %s, weight %s" % (what, tuple(x.shape), tuple(g.shape), tuple(weight_like.shape)))
+    if not (_fp32_cl_map(x, True) and _fp32_cl_map(g, True)):
+        raise ValueError("%s: fp32 channels-last maps expected" % what)
+    plan = (ctypes.c_int64 * 3)()
+    _lib.check(getattr(lib, plan_entry)(b, h, w, cin, cout, int(slices), _cus_of(x.device), ctypes.cast(plan, ctypes.c_void_p)),
+               plan_entry)
+    ws = torch.empty((int(plan[2]),), dtype=torch.uint8, device=x.device)
+    if _non_overlapping_and_dense(weight_like):
+        dw = torch.empty_strided(tuple(weight_like.shape), tuple(weight_like.stride()), dtype=torch.float32, device=x.device)
+    else:
+        dw = torch.empty(tuple(weight_like.shape), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _lib.check(getattr(lib, run_entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), g.data_ptr(), dw.data_ptr(),
+                                       *(int(v) for v in dw.stride()), ws.data_ptr(), int(plan[2]), int(plan[0]),
+                                       _lib.stream_of(x)), run_entry)
+    return dw
+
+
 def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
     """The weight gradient of the same-size 3x3 convolution ``F.conv2d(x, w, None, 1, dilation, dilation)`` for the output gradient
     ``g``, on the split core (csrc/conv3x3_wgrad.hip: both operands split in the loop, split-K over the pixels into a workspace,
@@ -1010,26 +1035,28 @@ def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
     (B, Cout, H, W): fp32, channels-last, 16-byte aligned.  ``weight_like`` gives shape, device and layout of the result: its own
     strides when it is non-overlapping and dense, channels-last otherwise (a channel slice of a wider weight).  ``slices``: 0 =
     the plan's choice for the tensor's device."""
-    _lib.require_device(x, g)
-    lib = _lib.get()
-    b, cin, h, w = (int(v) for v in x.shape)
-    cout = int(g.shape[1])
-    if tuple(weight_like.shape) != (cout, cin, 3, 3) or tuple(g.shape) != (b, cout, h, w):
-        raise ValueError("conv3x3_split_wgrad: x %s, g %s, weight %s" % (tuple(x.shape), tuple(g.shape), tuple(weight_like.shape)))
-    if not (_fp32_cl_map(x, True) and _fp32_cl_map(g, True)):
-        raise ValueError("conv3x3_split_wgrad: fp32 channels-last maps expected")
-    plan = (ctypes.c_int64 * 3)()
-    _lib.check(lib.skd_conv3x3_split_wgrad_plan(b, h, w, cin, cout, int(slices), _cus_of(x.device),
-                                                ctypes.cast(plan, ctypes.c_void_p)), "skd_conv3x3_split_wgrad_plan")
-    ws = torch.empty((int(plan[2]),), dtype=torch.uint8, device=x.device)
-    if _non_overlapping_and_dense(weight_like):
-        dw = torch.empty_strided(tuple(weight_like.shape), tuple(weight_like.stride()), dtype=torch.float32, device=x.device)
-    else:
-        dw = torch.empty(tuple(weight_like.shape), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _lib.check(lib.skd_conv3x3_split_wgrad_nhwc(b, h, w, cin, cout, int(dilation), x.data_ptr(), g.data_ptr(), dw.data_ptr(),
-                                                *(int(v) for v in dw.stride()), ws.data_ptr(), int(plan[2]), int(plan[0]),
-                                                _lib.stream_of(x)), "skd_conv3x3_split_wgrad_nhwc")
-    return dw
+    return _conv3x3_wgrad_launch("conv3x3_split_wgrad", _WGRAD_ENTRIES[1], _WGRAD_ENTRIES[2], x, g, weight_like, dilation, slices)
+
+
+_NARROW_WGRAD_ENTRIES = ("skd_conv3x3_narrow_wgrad_supported", "skd_conv3x3_narrow_wgrad_plan", "skd_conv3x3_narrow_wgrad_nhwc")
+
+
+def conv3x3_narrow_wgrad_supported(x, weight, stride, padding, dilation, groups):
+    """True when conv3x3_narrow_wgrad takes the weight gradient of ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)``:
+    a back-end that has the three entries of include/skd_narrow_wgrad.h (the tests' C double does not: the gradient then comes from
+    the library, as before), everything conv3x3_narrow_train_supported asks, and Cin and Cout multiples of 64."""
+    return (all(_lib.has_entry(n) for n in _NARROW_WGRAD_ENTRIES)
+            and conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups)
+            and bool(_lib.get().skd_conv3x3_narrow_wgrad_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride),
+                                                                   int(padding), int(dilation), int(groups))))
+
+
+def conv3x3_narrow_wgrad(x, g, weight_like, dilation, slices=0):
+    """conv3x3_split_wgrad for channel counts that are multiples of 64: the 128 x 64 tile form of the same kernel
+    (csrc/conv3x3_wgrad.hip, include/skd_narrow_wgrad.h) -- the same arguments, the same result layout, the same numerics; for a
+    shape both take and the same slice count, the same bits."""
+    return _conv3x3_wgrad_launch("conv3x3_narrow_wgrad", _NARROW_WGRAD_ENTRIES[1], _NARROW_WGRAD_ENTRIES[2], x, g, weight_like,
+                                 dilation, slices)
 
 
 class _Conv3x3SplitTrain(Function):
@@ -1037,7 +1064,8 @@ class _Conv3x3SplitTrain(Function):
     data gradient -- the same kind of convolution of the output gradient with the flipped, transposed weight -- on the
     ``pack_bwd`` THIS forward was given (kept in ctx: an optimizer step in between changes the cache, not this node).  The
     weight gradient (and the bias gradient) are the library's, as before -- with ``wgrad`` the weight gradient is
-    conv3x3_split_wgrad's where the back-end has its entries, and the library computes the bias gradient alone."""
+    conv3x3_split_wgrad's where the back-end has its entries, and the library computes the bias gradient alone; ``"narrow"`` in
+    its place (conv3x3_split_train's ``narrow_wgrad``) asks for conv3x3_narrow_wgrad's in the same way."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, *wgrad):
@@ -1045,6 +1073,7 @@ class _Conv3x3SplitTrain(Function):
         ctx.save_for_backward(x, weight)
         ctx.pack_bwd, ctx.dilation, ctx.has_bias = pack_bwd, int(dilation), bias is not None
         ctx.wgrad, ctx.n_inputs = bool(wgrad and wgrad[0]), 6 + len(wgrad)
+        ctx.narrow_wgrad = bool(wgrad) and wgrad[0] == "narrow"
         # (forward?, backward?) on the narrow entry: the third optional argument (conv3x3_split_train's ``narrow``)
         fwd_narrow, ctx.bwd_narrow = wgrad[1] if len(wgrad) > 1 else (False, False)
         if fwd_narrow:
@@ -1063,8 +1092,8 @@ class _Conv3x3SplitTrain(Function):
         if ctx.needs_input_grad[0]:
             dx = (_conv3x3_narrow_launch if ctx.bwd_narrow else _conv3x3_split_launch)(g, ctx.pack_bwd, int(weight.shape[1]), d)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.wgrad and need_w and all(_lib.has_entry(n) for n in _WGRAD_ENTRIES):
-            dw = conv3x3_split_wgrad(x, g, weight, d)
+        if ctx.wgrad and need_w and all(_lib.has_entry(n) for n in (_NARROW_WGRAD_ENTRIES if ctx.narrow_wgrad else _WGRAD_ENTRIES)):
+            dw = (conv3x3_narrow_wgrad if ctx.narrow_wgrad else conv3x3_split_wgrad)(x, g, weight, d)
             need_w = False
         if need_w or need_b:
             _, lw, db = torch.ops.aten.convolution_backward(g, x, weight, [int(weight.shape[0])] if ctx.has_bias else None,
@@ -1073,7 +1102,7 @@ class _Conv3x3SplitTrain(Function):
         return (dx, dw, db) + (None,) * (ctx.n_inputs - 3)
 
 
-def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False):
+def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False):
     """``F.conv2d(x, weight, bias, 1, dilation, dilation)`` for a call conv3x3_train_supported accepted, differentiable: forward
     and data gradient are one launch each of the split-core implicit GEMM (csrc/conv3x3.hip: fp32 in and out, three bf16 pieces,
     six products, fp32 accumulation; the numerics of conv3x3_split_eval in both directions), the weight and bias gradients come
@@ -1082,11 +1111,14 @@ def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=Fal
     (conv3x3_split_wgrad) where the back-end has the entries of include/skd_wgrad.h; the bias gradient stays with the library.
     ``narrow=True`` (opt-in; conv3x3_narrow_train_supported says when): each direction is chosen by its N -- Cout for the forward,
     Cin for the data gradient: the 128-column tiles for a multiple of 128, the 64-column ones otherwise -- which takes one pack
-    launch per entry and weight version; the weight gradient of a shape with a 64-channel side stays with the library."""
+    launch per entry and weight version; the weight gradient of a shape with a 64-channel side stays with the library (``wgrad``
+    is ignored for it) unless ``narrow_wgrad=True`` (a further opt-in, effective only with ``narrow``): then it is
+    conv3x3_narrow_wgrad's where the back-end has the entries of include/skd_narrow_wgrad.h, the bias gradient the library's."""
     if narrow:
         pack_fwd, pack_bwd, fwd_narrow, bwd_narrow = _conv3x3_narrow_train_packs(weight, owner)
         if fwd_narrow or bwd_narrow:
-            return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, False, (fwd_narrow, bwd_narrow))
+            return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, "narrow" if narrow_wgrad else False,
+                                            (fwd_narrow, bwd_narrow))
     pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
     if wgrad:
         return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, True)

@@ -195,13 +195,23 @@ class NetModel():
         self.split_train = bool(split_train)
         # args.split_wgrad (None: SKD_SPLIT_WGRAD, default "0"): with split_train, the weight gradients of those convolutions run
         # on the split core as well (csrc/conv3x3_wgrad.hip); without split_train it routes nothing.  Off by default
-        # (isolated: profiles/r20_conv3x3_wgrad_isolated.md; the step A/B of profiles/r20_step_ab.md has not been run yet).
+        # (isolated: profiles/r20_conv3x3_wgrad_isolated.md; the step A/B is in profiles/r23_step_ab.md: -1.55 ms per step).
         split_wgrad = getattr(args, "split_wgrad", None)
         if split_wgrad is None:
             split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
         self.split_wgrad = bool(split_wgrad) and self.split_train
+        # args.split_narrow_wgrad (None: SKD_SPLIT_NARROW_WGRAD, default "0"): with split_train and split_narrow, the weight
+        # gradients of the six 64-channel convolutions run on the split core too (the 128 x 64 form of csrc/conv3x3_wgrad.hip);
+        # without either it routes nothing, and it does not depend on split_wgrad.  Off by default
+        # (profiles/r23_conv3x3_narrow_wgrad_isolated.md, profiles/r23_step_ab.md).
+        split_narrow_wgrad = getattr(args, "split_narrow_wgrad", None)
+        if split_narrow_wgrad is None:
+            split_narrow_wgrad = os.environ.get("SKD_SPLIT_NARROW_WGRAD", "0") == "1"
+        self.split_narrow_wgrad = bool(split_narrow_wgrad) and self.split_train and self.split_narrow
         if self.split_train:
             extra = dict(narrow=True) if self.split_narrow else {}
+            if self.split_narrow_wgrad:
+                extra["narrow_wgrad"] = True
             if self.split_wgrad:
                 route_training_convs(student, wgrad=True, **extra)
             else:
@@ -859,7 +869,7 @@ def default_args(**overrides):
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
-        split_wgrad=None, split_narrow=None)
+        split_wgrad=None, split_narrow=None, split_narrow_wgrad=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
@@ -868,4 +878,6 @@ def default_args(**overrides):
         a.split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
     if a.split_narrow is None:         # effective only together with fused_eval (inference) or split_train (training)
         a.split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"
+    if a.split_narrow_wgrad is None:   # effective only together with split_train and split_narrow
+        a.split_narrow_wgrad = os.environ.get("SKD_SPLIT_NARROW_WGRAD", "0") == "1"
     return a

@@ -91,6 +91,13 @@ WGRAD_ROUTING_EXCLUDED = frozenset()
 # that does not measure ahead of the library by more than the spread is listed here as (Cin, Cout, dilation, form), form =
 # "infer" or "train", and keeps the library (profiles/r21_conv3x3_narrow_isolated.md has every shape).
 NARROW_ROUTING_EXCLUDED = frozenset()
+# The weight gradient of a convolution ``narrow`` routes on the split core too (route_training_convs(narrow_wgrad=True); a fourth
+# opt-in, on top of ``narrow``): SF.conv3x3_narrow_wgrad (the 128 x 64 tile form of csrc/conv3x3_wgrad.hip) instead of the
+# library's kernels.  A shape whose two launches do not measure ahead of the library by more than the spread is listed here as
+# (Cin, Cout, dilation) and keeps the library for its weight gradient (profiles/r23_conv3x3_narrow_wgrad_isolated.md has every shape).
+# Measured on the MI355X at batch 8: all six convolutions of the step are 0.68 - 0.85 x the library's speed, so all three of their
+# shapes are listed, and the opt-in routes nothing until a kernel measures ahead.
+NARROW_WGRAD_ROUTING_EXCLUDED = frozenset({(64, 64, 1), (64, 128, 1), (128, 64, 1)})
 
 
 def _narrow_shape(conv):
@@ -145,6 +152,9 @@ def _train_conv(module, conv, x):
             return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=True)
         return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv)
     if _narrow_train_routed(module, x, conv):
+        if (getattr(module, "_skd_train_narrow_wgrad", False)
+                and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in NARROW_WGRAD_ROUTING_EXCLUDED):
+            return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, narrow=True, narrow_wgrad=True)
         return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, narrow=True)
     return conv(x)
 
@@ -589,7 +599,7 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
     return model
 
 
-def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False, narrow=False):
+def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False, narrow=False, narrow_wgrad=False):
     """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
 
     A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
@@ -607,6 +617,9 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     ``narrow=True``: the stem's conv2 / conv3 and layer1's four convolutions too (SF.conv3x3_split_train(..., narrow=True): each
     direction on the 128-column form of the kernel where its N is a multiple of 128, on the 64-column one otherwise; their weight gradients
     stay with the library) except for the shapes of NARROW_ROUTING_EXCLUDED.
+    ``narrow_wgrad=True``: the weight gradients of the convolutions ``narrow`` routes run on the split core as well
+    (SF.conv3x3_narrow_wgrad, the 128 x 64 form of csrc/conv3x3_wgrad.hip) except for the shapes of NARROW_WGRAD_ROUTING_EXCLUDED;
+    without ``narrow`` it routes nothing, and on a back-end without the entries of include/skd_narrow_wgrad.h they stay with the library.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
     for m in model.modules():
@@ -615,6 +628,7 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
         m._skd_train_min_cin = int(min_cin) if enable else None
         m._skd_train_wgrad = bool(wgrad and enable)
         m._skd_train_narrow = bool(narrow and enable)
+        m._skd_train_narrow_wgrad = bool(narrow_wgrad and enable)
         if enable:
             continue
         owners = ((m.conv1, m.conv2) if isinstance(m, BasicBlock) else (m.dsn[0], m.conv2, m.conv3) if isinstance(m, ResNet)

@@ -6,7 +6,9 @@ groups of 10 back-to-back launches), ``--rounds`` interleaved rounds parent, spl
 median of one side's rounds, the larger of the two sides.  ``--slices a,b,c``: further slice counts timed beside the plan's own
 (one extra column each, timed once) -- how the shipped rule of skd_conv3x3_split_wgrad_plan was chosen.  ``--lib PATH``: another
 build of the library (say, one compiled with -DSKD_WGRAD_GRID_ORDER=1) timed in the same rounds, one more column.
-    python tools/conv3x3_wgrad_bench.py [--rounds 3] [--slices 1,2,4,8] [--lib other/libskd_hip.so]
+``--narrow``: the six 64-channel convolutions of the stem (256 x 256) and layer1 (129 x 129) on skd_conv3x3_narrow_wgrad_nhwc
+instead -- the table of profiles/r23_conv3x3_narrow_wgrad_isolated.md; ``--hw`` is ignored.
+    python tools/conv3x3_wgrad_bench.py [--rounds 3] [--slices 1,2,4,8] [--lib other/libskd_hip.so] [--narrow]
 """
 import argparse
 import ctypes
@@ -27,6 +29,12 @@ PROBLEMS = [  # (name, Cin, Cout, dilation, convolutions of this shape per stude
     ("dsn[0] 256->128 d1", 256, 128, 1, 1),
     ("psp half 512->128 d1", 512, 128, 1, 1),
 ]
+NARROW_PROBLEMS = [  # (name, Cin, Cout, dilation, convolutions of this shape per student step, map size)
+    ("stem conv2 64->64 d1 256x256", 64, 64, 1, 1, 256),
+    ("stem conv3 64->128 d1 256x256", 64, 128, 1, 1, 256),
+    ("layer1.0.conv1 128->64 d1 129x129", 128, 64, 1, 1, 129),
+    ("layer1 64->64 d1 129x129", 64, 64, 1, 3, 129),
+]
 
 
 def main():
@@ -36,6 +44,7 @@ def main():
     ap.add_argument("--hw", type=int, default=65)
     ap.add_argument("--slices", default="")
     ap.add_argument("--lib", default=None)
+    ap.add_argument("--narrow", action="store_true")
     a = ap.parse_args()
     import torch
     import structure_knowledge_distillation_amd as _skd
@@ -50,7 +59,8 @@ def main():
     extra = [int(s) for s in a.slices.split(",") if s]
     med = statistics.median
     fmt = lambda runs: " / ".join("%.1f" % (1e3 * t) for t in runs)
-    print("%d compute units; batch %d, %d x %d" % (cus, B, hw, hw))
+    form = "narrow" if a.narrow else "split"
+    print("%d compute units; batch %d, %s" % (cus, B, "the step's map sizes" if a.narrow else "%d x %d" % (hw, hw)))
     print()
     print("| convolution | per step | slices (K-tiles each) | parent us (runs) | split us (runs) | parent / split | spread | verdict |"
           + (" --lib us (runs) |" if other else "") + "".join(" %d slices us |" % s for s in extra))
@@ -58,7 +68,8 @@ def main():
     total_p = total_s = 0.0
     plan = (ctypes.c_int64 * 3)()
     with torch.no_grad():
-        for name, cin, cout, d, count in PROBLEMS:
+        for name, cin, cout, d, count, *size in (NARROW_PROBLEMS if a.narrow else PROBLEMS):
+            hw = size[0] if size else a.hw
             torch.manual_seed(cin + cout + d)
             x = torch.relu(torch.randn(B, cin, hw, hw, device=dev)).contiguous(memory_format=torch.channels_last)
             g = torch.randn(B, cout, hw, hw, device=dev).contiguous(memory_format=torch.channels_last)
@@ -67,13 +78,13 @@ def main():
             st = _lib.stream_of(x)
 
             def split_side(slices, lib=lib):
-                assert lib.skd_conv3x3_split_wgrad_plan(B, hw, hw, cin, cout, slices, cus, ctypes.cast(plan, ctypes.c_void_p))
+                assert getattr(lib, "skd_conv3x3_%s_wgrad_plan" % form)(B, hw, hw, cin, cout, slices, cus, ctypes.cast(plan, ctypes.c_void_p))
                 used, per_slice, nbytes = int(plan[0]), int(plan[1]), int(plan[2])
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
                 def run():
-                    assert lib.skd_conv3x3_split_wgrad_nhwc(B, hw, hw, cin, cout, d, x.data_ptr(), g.data_ptr(), dw.data_ptr(),
-                                                            *dw.stride(), ws.data_ptr(), nbytes, used, st)
+                    assert getattr(lib, "skd_conv3x3_%s_wgrad_nhwc" % form)(B, hw, hw, cin, cout, d, x.data_ptr(), g.data_ptr(),
+                                                                            dw.data_ptr(), *dw.stride(), ws.data_ptr(), nbytes, used, st)
                 return run, used, per_slice
             run_s, used, per_slice = split_side(0)
             run_p = lambda: torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [d, d], [d, d], False, [0, 0], 1,
