@@ -21,6 +21,7 @@ WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_w
 NARROW_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow.h"))
 NARROW_WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow_wgrad.h"))
 SHORTCUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_shortcut.h"))
+SPLIT2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_split2.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -235,6 +236,18 @@ SHORTCUT_SIGNATURES = {
     "skd_conv1x1_train_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _P]),
 }
 
+# Entry points declared in include/skd_split2.h (csrc/conv3x3.hip, csrc/conv1x1.hip with two pieces per operand): the frozen
+# teacher's reduced-precision mode, extension entries in a table of their own like the nine above (tests/test_split2_cpu.py checks
+# header <-> table <-> exported symbols, tests/test_split2_gpu.py holds the guard-band cases).  A back-end without them leaves the
+# teacher on three pieces (pspnet_combine.set_teacher_pieces warns): nothing raises.
+SPLIT2_SIGNATURES = {
+    "skd_conv3x3_split2_pack_bytes": (_L, [_I, _I]),
+    "skd_conv3x3_split2_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
+    "skd_conv3x3_split2_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+    "skd_conv1x1_abn2_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _P]),
+    "skd_conv1x1_abn2_pro_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _F, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -265,7 +278,7 @@ def load(path=None):
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
-                  WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES):
+                  WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

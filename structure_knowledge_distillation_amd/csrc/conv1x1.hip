@@ -46,6 +46,7 @@
 #include <stdlib.h>
 
 #include "conv_split_dev.hpp"
+#include "skd_split2.h"
 
 namespace skd {
 namespace {
@@ -83,10 +84,10 @@ __device__ __forceinline__ float pro_one(float x, float m, float is, float g, fl
 }
 
 // `srow`: this thread's 8-byte slot inside a plane, in uint2 units (see conv1x1_tile); rows 64 apart are 128 slots apart.
-template <bool PRO, int TM>
+template <bool PRO, int TM, int PIECES>
 __device__ __forceinline__ void stage_store(const Staging<TM> &s, uint4 *stage, int srow, const float *ptab, int K, int kq) {
   constexpr int kRA = TM / kRPP;
-  uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow, *sb = reinterpret_cast<uint2 *>(stage + kOperandChunks) + srow;
+  uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow, *sb = reinterpret_cast<uint2 *>(stage + operand_chunks(PIECES)) + srow;
   if (PRO) {   // ptab (LDS copy of ppack): mean | invstd | gamma | beta, each K floats; kq = first of this thread's four k
     ProParams pp;
     pp.pm = *reinterpret_cast<const float4 *>(ptab + kq);
@@ -100,18 +101,18 @@ __device__ __forceinline__ void stage_store(const Staging<TM> &s, uint4 *stage, 
       v.y = pro_one(v.y, pp.pm.y, pp.pi.y, pp.pg.y, pp.pb.y);
       v.z = pro_one(v.z, pp.pm.z, pp.pi.z, pp.pg.z, pp.pb.z);
       v.w = pro_one(v.w, pp.pm.w, pp.pi.w, pp.pg.w, pp.pb.w);
-      split_store(v, sa + 2 * kRPP * h);
+      split_store<PIECES>(v, sa + 2 * kRPP * h);
     }
   } else {
 #pragma unroll
-    for (int h = 0; h < kRA; ++h) split_store(s.a[h], sa + 2 * kRPP * h);
+    for (int h = 0; h < kRA; ++h) split_store<PIECES>(s.a[h], sa + 2 * kRPP * h);
   }
 #pragma unroll
-  for (int h = 0; h < kRB; ++h) split_store(s.b[h], sb + 2 * kRPP * h);
+  for (int h = 0; h < kRB; ++h) split_store<PIECES>(s.b[h], sb + 2 * kRPP * h);
 }
 
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.
-template <bool PRO, int TM>
+template <bool PRO, int TM, int PIECES = 3>
 struct Tile1 {
   typedef Staging<TM> Stg;
   const float *__restrict__ X, *__restrict__ Wt;
@@ -121,13 +122,13 @@ struct Tile1 {
   f32x16 (&acc)[TM / 64][2];
   __device__ __forceinline__ void load(Stg &s, int kt) const { stage_load<PRO, TM>(s, X, Wt, kt * kBK, gkq, arow, wrow0, K); }
   __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int kt) const {
-    stage_store<PRO, TM>(s, stage, srow, ptab, K, kt * kBK + gkq);
+    stage_store<PRO, TM, PIECES>(s, stage, srow, ptab, K, kt * kBK + gkq);
   }
-  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM>(stage, acc); }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, PIECES>(stage, acc); }
 };
 
 // One output tile of TM x 128: K loop through the double-buffered LDS ring, then the epilogue.
-template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT>
+template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3>
 __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R,
                                              float *__restrict__ Y, const float *__restrict__ mean, const float *__restrict__ var,
                                              const float *__restrict__ weight, const float *__restrict__ bias,
@@ -151,15 +152,15 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
     arow[h] = (m > M - 1 ? M - 1 : m) * K;
   }
   const int64_t wrow0 = (int64_t)(n0 + grow) * K;
-  float *ptab = reinterpret_cast<float *>(lds + 2 * kStageChunks);   // PRO: the (4, K) parameter table, K <= kProMaxK
+  float *ptab = reinterpret_cast<float *>(lds + 2 * stage_chunks(PIECES));   // PRO: the (4, K) parameter table, K <= kProMaxK
   if (PRO) {
     for (int i = gt * 4; i < 4 * K; i += kThreads * 4) *reinterpret_cast<float4 *>(ptab + i) = *reinterpret_cast<const float4 *>(ppack + i);
     __syncthreads();
   }
-  Tile1<PRO, TM> tile = {X, Wt, ptab, K, gkq, srow, wrow0, {}, acc};
+  Tile1<PRO, TM, PIECES> tile = {X, Wt, ptab, K, gkq, srow, wrow0, {}, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) tile.arow[h] = arow[h];
-  k_loop<kDepth1x1>(tile, nk, lds);
+  k_loop<kDepth1x1, PIECES, PIECES == 2 && !PRO>(tile, nk, lds);
   // ---- epilogue: the eval-mode InPlace-ABN formula on the accumulator (+ residual) + activation ----
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
@@ -243,7 +244,9 @@ __host__ __device__ __forceinline__ TileOf conv1x1_tile_of(unsigned block, int64
   return TileOf{m0, kTM / 2, tn * kTN};
 }
 
-template <int ACT, bool HAS_RES, bool PRO, bool NT>
+// PIECES = 2 (include/skd_split2.h): two pieces per operand, the three products a0 b1, a1 b0, a0 b0 into the one accumulator; the
+// grid, the tile order and the half-height round are those of the three-piece launch (32 KB of LDS + the prologue's table).
+template <int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3>
 __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
     const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R, float *__restrict__ Y,
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
@@ -272,9 +275,9 @@ __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
   // workgroups of half the duration fill the last round's slots (p_full is a multiple of 8: whole XCD rows).
   const TileOf t = conv1x1_tile_of(blockIdx.x, M, tiles_n, pm, ct, p_full);
   if (t.rows == kTM)
-    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT, PIECES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
   else if (t.rows == kTM / 2)
-    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT, PIECES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
 }
 
 __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, const float *__restrict__ var,
@@ -288,7 +291,7 @@ __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, c
   pack[3 * (int64_t)K + k] = bias != nullptr ? bias[k] : 0.f;
 }
 
-template <int ACT, bool HAS_RES, bool PRO, bool NT = false>
+template <int ACT, bool HAS_RES, bool PRO, int PIECES = 3, bool NT = false>
 static int launch(const float *X, const float *Wt, const float *R, float *Y, const float *mean, const float *var,
                   const float *weight, const float *bias, const float *ppack, float eps, float slope, int64_t M, int K, int N,
                   hipStream_t st) {
@@ -296,15 +299,15 @@ static int launch(const float *X, const float *Wt, const float *R, float *Y, con
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kConvLds + sizeof(float) * 4 * kProMaxK)) != hipSuccess) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(conv_lds(PIECES) + sizeof(float) * 4 * kProMaxK)) != hipSuccess) return 0;
     *rdy = true;
   }
-  const size_t lds_bytes = kConvLds + (PRO ? sizeof(float) * 4 * (size_t)K : 0);
+  const size_t lds_bytes = conv_lds(PIECES) + (PRO ? sizeof(float) * 4 * (size_t)K : 0);
   Geometry g;
   if (!conv1x1_geometry(M, K, N, cu_count(st), g)) return 0;
-  if (g.nt && !NT) return launch<ACT, HAS_RES, PRO, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
-  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
+  if (g.nt && !NT) return launch<ACT, HAS_RES, PRO, PIECES, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
+  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
       X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, g.tiles_n, g.pm, g.ct, (int)g.p_full);
   return ok();
 }
@@ -342,6 +345,10 @@ int skd_conv1x1_abn_tile_of(int64_t M, int K, int N, int cus, int64_t block, int
   return 1;
 }
 
+}  // extern "C"
+
+// The host body of the four GEMM entries below: every refusal, then the instantiation that (activation, residual, prologue) name.
+template <int PIECES>
 static int conv1x1_dispatch(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
                             const float *mean, const float *var, const float *weight, const float *bias, const float *ppack,
                             float eps, int activation, float slope, skd_stream_t stream) {
@@ -350,10 +357,10 @@ static int conv1x1_dispatch(int64_t M, int K, int N, const float *x, const float
   hipStream_t st = as_stream(stream);
 #define SKD_C11(A)                                                                                                        \
   if (ppack != nullptr)                                                                                                   \
-    return residual ? launch<A, true, true>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st)   \
-                    : launch<A, false, true>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st); \
-  return residual ? launch<A, true, false>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st) \
-                  : launch<A, false, false>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st)
+    return residual ? launch<A, true, true, PIECES>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st)   \
+                    : launch<A, false, true, PIECES>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st); \
+  return residual ? launch<A, true, false, PIECES>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st) \
+                  : launch<A, false, false, PIECES>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st)
   switch (activation) {
     case SKD_ACT_NONE: SKD_C11(SKD_ACT_NONE);
     case SKD_ACT_RELU: SKD_C11(SKD_ACT_RELU);
@@ -363,10 +370,12 @@ static int conv1x1_dispatch(int64_t M, int K, int N, const float *x, const float
 #undef SKD_C11
 }
 
+extern "C" {
+
 int skd_conv1x1_abn_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
                          const float *mean, const float *var, const float *weight, const float *bias, float eps,
                          int activation, float slope, skd_stream_t stream) {
-  return conv1x1_dispatch(M, K, N, x, w, residual, out, mean, var, weight, bias, nullptr, eps, activation, slope, stream);
+  return conv1x1_dispatch<3>(M, K, N, x, w, residual, out, mean, var, weight, bias, nullptr, eps, activation, slope, stream);
 }
 
 // pack (4, K) = [mean | invstd(var, eps) | |weight| + eps (1 when NULL) | bias (0 when NULL)]: the per-channel constants of an
@@ -386,7 +395,21 @@ int skd_conv1x1_abn_pro_nhwc(int64_t M, int K, int N, const float *x, const floa
                              const float *mean, const float *var, const float *weight, const float *bias, float eps,
                              const float *ppack, int activation, float slope, skd_stream_t stream) {
   if (!ppack || K > kProMaxK) return 0;
-  return conv1x1_dispatch(M, K, N, x, w, residual, out, mean, var, weight, bias, ppack, eps, activation, slope, stream);
+  return conv1x1_dispatch<3>(M, K, N, x, w, residual, out, mean, var, weight, bias, ppack, eps, activation, slope, stream);
+}
+
+// include/skd_split2.h: the same two entries on two pieces per operand (three products).
+int skd_conv1x1_abn2_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
+                          const float *mean, const float *var, const float *weight, const float *bias, float eps,
+                          int activation, float slope, skd_stream_t stream) {
+  return conv1x1_dispatch<2>(M, K, N, x, w, residual, out, mean, var, weight, bias, nullptr, eps, activation, slope, stream);
+}
+
+int skd_conv1x1_abn2_pro_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
+                              const float *mean, const float *var, const float *weight, const float *bias, float eps,
+                              const float *ppack, int activation, float slope, skd_stream_t stream) {
+  if (!ppack || K > kProMaxK) return 0;
+  return conv1x1_dispatch<2>(M, K, N, x, w, residual, out, mean, var, weight, bias, ppack, eps, activation, slope, stream);
 }
 
 }  // extern "C"

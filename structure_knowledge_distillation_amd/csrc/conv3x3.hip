@@ -40,6 +40,7 @@
 #include "conv_split_dev.hpp"
 #include "skd_infer.h"
 #include "skd_narrow.h"
+#include "skd_split2.h"
 #include "skd_train.h"
 
 namespace skd {
@@ -48,20 +49,25 @@ namespace {
 constexpr int kDepth3x3 = 2;                          // K-tiles of load look-ahead (k_loop, conv_split_dev.hpp)
 constexpr int kNarrowTN = 64;                         // the column tile of include/skd_narrow.h; kTN = 128 is the others'
 // One (column tile, K-tile) of packed weights, in chunks: 768 = 12,288 bytes, or 384.  Thread t copies chunks t + i * kThreads.
-constexpr int tile_chunks(int TN) { return 3 * 2 * TN; }
-constexpr int b_copies(int TN) { return (tile_chunks(TN) + kThreads - 1) / kThreads; }
+// PIECES (conv_split_dev.hpp) = 2: the two-plane image of include/skd_split2.h, 512 chunks = 8,192 bytes at TN = 128 -- two
+// copies per thread.
+constexpr int tile_chunks(int TN, int PIECES = 3) { return PIECES * 2 * TN; }
+constexpr int b_copies(int TN, int PIECES = 3) { return (tile_chunks(TN, PIECES) + kThreads - 1) / kThreads; }
 // Whether thread t's copy i exists: a constant for every copy but the last of TN = 64 (t < 128: uniform per wave).
-template <int TN>
+template <int TN, int PIECES = 3>
 __device__ __forceinline__ bool b_copy_live(int i) {
-  return (i + 1) * kThreads <= tile_chunks(TN) || (int)threadIdx.x < tile_chunks(TN) - i * kThreads;
+  return (i + 1) * kThreads <= tile_chunks(TN, PIECES) || (int)threadIdx.x < tile_chunks(TN, PIECES) - i * kThreads;
 }
-constexpr size_t conv3x3_lds(int TN) { return sizeof(uint4) * (kStageChunks + kOperandChunks + tile_chunks(TN)); }
+constexpr size_t conv3x3_lds(int TN, int PIECES = 3) {
+  return sizeof(uint4) * (stage_chunks(PIECES) + operand_chunks(PIECES) + tile_chunks(TN, PIECES));
+}
 static_assert(conv3x3_lds(kTN) == kConvLds, "the 128-column form fills both stages");
+static_assert(conv3x3_lds(kTN, 2) == conv_lds(2) && tile_chunks(kTN, 2) == 2 * kThreads, "... of two pieces too: 32 KB, two copies");
 
-template <int TM, int TN>
+template <int TM, int TN, int PIECES = 3>
 struct Staging3 {
   float4 a[TM / kRPP];
-  uint4 b[b_copies(TN)];
+  uint4 b[b_copies(TN, PIECES)];
 };
 
 struct TapCursor {      // the K-tile being staged: tap 0..8, first channel c0, and the tap's address shift in floats
@@ -75,17 +81,17 @@ __device__ __forceinline__ int64_t tap_shift(int tap, int W, int dil, int Cin) {
 }
 
 // The packed weights: every lane loads its chunks (a copy that does not exist stages zeros, which nothing stores).
-template <int TM, int TN>
-__device__ __forceinline__ void stage_load3_b(Staging3<TM, TN> &s, const uint4 *__restrict__ bsrc) {
+template <int TM, int TN, int PIECES>
+__device__ __forceinline__ void stage_load3_b(Staging3<TM, TN, PIECES> &s, const uint4 *__restrict__ bsrc) {
 #pragma unroll
-  for (int i = 0; i < b_copies(TN); ++i) {
+  for (int i = 0; i < b_copies(TN, PIECES); ++i) {
     s.b[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (b_copy_live<TN>(i)) s.b[i] = bsrc[i * kThreads];
+    if (b_copy_live<TN, PIECES>(i)) s.b[i] = bsrc[i * kThreads];
   }
 }
 // The activations: a lane whose tap is outside the image issues no load and stages an exact zero.
-template <int TM, int TN>
-__device__ __forceinline__ void stage_load3_a(Staging3<TM, TN> &s, const float *__restrict__ X, const TapCursor &cur,
+template <int TM, int TN, int PIECES>
+__device__ __forceinline__ void stage_load3_a(Staging3<TM, TN, PIECES> &s, const float *__restrict__ X, const TapCursor &cur,
                                               const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP]) {
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) {
@@ -94,23 +100,23 @@ __device__ __forceinline__ void stage_load3_a(Staging3<TM, TN> &s, const float *
   }
 }
 
-template <int TM, int TN>
-__device__ __forceinline__ void stage_store3(const Staging3<TM, TN> &s, uint4 *stage, int srow) {
+template <int TM, int TN, int PIECES>
+__device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES> &s, uint4 *stage, int srow) {
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
 #pragma unroll
-  for (int h = 0; h < TM / kRPP; ++h) split_store(s.a[h], sa + 2 * kRPP * h);
-  uint4 *sb = stage + kOperandChunks + threadIdx.x;
+  for (int h = 0; h < TM / kRPP; ++h) split_store<PIECES>(s.a[h], sa + 2 * kRPP * h);
+  uint4 *sb = stage + operand_chunks(PIECES) + threadIdx.x;
 #pragma unroll
-  for (int i = 0; i < b_copies(TN); ++i)
-    if (b_copy_live<TN>(i)) sb[i * kThreads] = s.b[i];
+  for (int i = 0; i < b_copies(TN, PIECES); ++i)
+    if (b_copy_live<TN, PIECES>(i)) sb[i * kThreads] = s.b[i];
 }
 
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.  k_loop calls load for kt = 0, 1, 2, ... in order, so the
 // cursor is simply stepped behind every one: it runs as far ahead of the MFMAs as the loads do and crosses a tap boundary
 // wherever that falls.  (Behind the last tile it stands at tap 9, which nothing reads.)
-template <int TM, int TN>
+template <int TM, int TN, int PIECES = 3>
 struct Tile3 {
-  typedef Staging3<TM, TN> Stg;
+  typedef Staging3<TM, TN, PIECES> Stg;
   static constexpr int WM = wave_blocks_m(TM, TN);
   const float *__restrict__ X;
   const uint4 *__restrict__ bsrc;
@@ -120,8 +126,8 @@ struct Tile3 {
   unsigned mask[TM / kRPP];
   f32x16 (&low)[WM][2], (&acc)[WM][2];
   __device__ __forceinline__ void load(Stg &s, int kt) {
-    stage_load3_a<TM, TN>(s, X, cur, abase, mask);
-    stage_load3_b<TM, TN>(s, bsrc + (int64_t)kt * tile_chunks(TN));
+    stage_load3_a<TM, TN, PIECES>(s, X, cur, abase, mask);
+    stage_load3_b<TM, TN, PIECES>(s, bsrc + (int64_t)kt * tile_chunks(TN, PIECES));
     cur.c0 += kBK;
     if (cur.c0 == Cin) {
       cur.c0 = 0;
@@ -129,13 +135,13 @@ struct Tile3 {
       cur.shift = tap_shift(cur.tap, W, dil, Cin);
     }
   }
-  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN>(s, stage, srow); }
-  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN>(stage, low, acc); }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES>(s, stage, srow); }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES>(stage, low, acc); }
 };
 
 // One output tile of TM x TN pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
 // in front of the activation (store_block): the second convolution of a BasicBlock.
-template <int TM, int TN, int ACT, bool HAS_RES>
+template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
                                              const float *__restrict__ R,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
@@ -143,7 +149,7 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
                                              const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W,
                                              int Cin, int N, int dil, int64_t m0, int tn, uint4 *lds) {
   constexpr int WM = wave_blocks_m(TM, TN), kRA = TM / kRPP;
-  f32x16 acc[WM][2], low[WM][2];      // a0 b0 | the five smaller products (tile_mma): added in the epilogue
+  f32x16 acc[WM][2], low[WM][2];      // a0 b0 | the five (PIECES = 2: two) smaller products (tile_mma): added in the epilogue
 #pragma unroll
   for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -173,14 +179,14 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
     mask[h] = bits;
     abase[h] = mm * Cin + gkq;
   }
-  const uint4 *bsrc = Bp + (int64_t)tn * nk * tile_chunks(TN) + gt;
-  Tile3<TM, TN> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
+  const uint4 *bsrc = Bp + (int64_t)tn * nk * tile_chunks(TN, PIECES) + gt;
+  Tile3<TM, TN, PIECES> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
     tile.abase[h] = abase[h];
     tile.mask[h] = mask[h];
   }
-  k_loop<kDepth3x3>(tile, nk, lds);
+  k_loop<kDepth3x3, PIECES>(tile, nk, lds);
   // ---- epilogue: (+ conv bias) -> eval-mode InPlace-ABN formula (when there are statistics) -> (+ residual) -> activation ----
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int wi = (wid / (TN / 64)) * (TM / waves_m(TN)), wj = (wid % (TN / 64)) * 64;      // tile_mma's wave map
@@ -220,7 +226,8 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 // launch bound alone (profiles/r15_kernel_resources.md).
 constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kMinWG; }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES>
+// PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h).
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
@@ -229,6 +236,7 @@ void conv3x3_split_kernel(
     const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil, int tiles_n,
     int p_full, const float *__restrict__ R) {
   static_assert(TALL || TN == kTN, "64-row panels exist for the 128-column form only");
+  static_assert(PIECES == 3 || (TN == kTN && !HAS_RES), "two pieces: the 128-column forward family without the residual");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -236,11 +244,11 @@ void conv3x3_split_kernel(
   if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, TN, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -253,7 +261,8 @@ void conv3x3_split_kernel(
 // others the backward image.  There the rows of a tile are TN input channels c and the 8 consecutive k of a chunk are 8 output channels n at stride sn:
 // a wave's 64 lanes are 64 consecutive c, so each of its eight loads reads a run of 64 elements at stride sc -- 256 contiguous
 // bytes of a channels-last weight (sc = 1: the training student's, and the PSP bottleneck's channel slice).
-template <int TN>
+// PIECES = 2 (include/skd_split2.h): the first two planes alone, 4 TN chunks per (column tile, K-tile).
+template <int TN, int PIECES = 3>
 __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
     const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int Cout, int64_t fwd_tiles,
     uint4 *__restrict__ pack_fwd, uint4 *__restrict__ pack_bwd) {
@@ -271,15 +280,17 @@ __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
   float v[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) v[i] = src[(e0 + i) * sk];
+  // the three-piece split for either PIECES: its first two pieces ARE the two-piece split (the third is dropped unused), so the
+  // two-plane image is planes 0 and 1 of the other bit for bit; the two-piece split4 overload serves split_store<2> alone
   uint2 lo[3], hi[3];
   split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
   split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
   uint4 *pack = fwd ? pack_fwd : pack_bwd;
 #pragma unroll
-  for (int p = 0; p < 3; ++p) pack[(tile * 3 + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
+  for (int p = 0; p < PIECES; ++p) pack[(tile * PIECES + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                    int geometry, hipStream_t st) {
@@ -287,8 +298,8 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN)) != hipSuccess) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN, PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
   const int tiles_n = N / TN;
@@ -303,7 +314,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN), st>>>(
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
       X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R);
   return ok();
 }
@@ -314,7 +325,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
 // TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
-template <int TN, int ACT, bool HAS_RES>
+template <int TN, int ACT, bool HAS_RES, int PIECES = 3>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st) {
@@ -323,8 +334,8 @@ static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, c
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
-      return launch3<TN, ACT, true, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
-    return launch3<TN, ACT, false, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+      return launch3<TN, ACT, true, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+    return launch3<TN, ACT, false, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
   }
 }
 
@@ -335,32 +346,32 @@ static int supported3(int Cin, int Cout, int stride, int padding, int dilation, 
   return Cin > 0 && Cout > 0 && Cin % kBK == 0 && Cout % TN == 0 && stride == 1 && dilation >= 1 && padding == dilation && groups == 1;
 }
 
-template <int TN>
+template <int TN, int PIECES = 3>
 static int64_t pack_bytes3(int Cin, int Cout) {
   if (!supported3<TN>(Cin, Cout, 1, 1, 1, 1)) return 0;
-  return (int64_t)(Cout / TN) * (9 * (Cin / kBK)) * tile_chunks(TN) * (int64_t)sizeof(uint4);
+  return (int64_t)(Cout / TN) * (9 * (Cin / kBK)) * tile_chunks(TN, PIECES) * (int64_t)sizeof(uint4);
 }
 
 // The (column tile, K-tile) count of the image of an (N, K / 9, 3, 3) weight in `pack`, 0 for no image (pack == nullptr), -1
 // for an image that is refused: a direction the core does not take, a buffer too small or not 16-byte aligned.
-template <int TN>
+template <int TN, int PIECES = 3>
 static int64_t pack_image_tiles(int K9, int N, const void *pack, int64_t pack_bytes) {
   if (!pack) return 0;
-  const int64_t need = pack_bytes3<TN>(K9, N);
+  const int64_t need = pack_bytes3<TN, PIECES>(K9, N);
   if (need == 0 || pack_bytes < need || (reinterpret_cast<uintptr_t>(pack) & 15)) return -1;
   return (int64_t)(N / TN) * (9 * (K9 / kBK));
 }
 
 // Either image or both in one launch (include/skd_train.h); every refusal is decided here, in front of the launch.
-template <int TN>
+template <int TN, int PIECES = 3>
 static int pack_pair3(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y, int64_t stride_x,
                       void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes, skd_stream_t stream) {
   if (!w || (!pack_fwd && !pack_bwd)) return 0;
   if (stride_n < 0 || stride_c < 0 || stride_y < 0 || stride_x < 0) return 0;
-  const int64_t fwd_tiles = pack_image_tiles<TN>(Cin, Cout, pack_fwd, fwd_bytes);
-  const int64_t bwd_tiles = pack_image_tiles<TN>(Cout, Cin, pack_bwd, bwd_bytes);
+  const int64_t fwd_tiles = pack_image_tiles<TN, PIECES>(Cin, Cout, pack_fwd, fwd_bytes);
+  const int64_t bwd_tiles = pack_image_tiles<TN, PIECES>(Cout, Cin, pack_bwd, bwd_bytes);
   if (fwd_tiles < 0 || bwd_tiles < 0 || fwd_tiles + bwd_tiles > 2147483647) return 0;
-  conv3x3_pack_pair_kernel<TN><<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(2 * TN), 0, as_stream(stream)>>>(
+  conv3x3_pack_pair_kernel<TN, PIECES><<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(2 * TN), 0, as_stream(stream)>>>(
       w, stride_n, stride_c, stride_y, stride_x, Cin, Cout, fwd_tiles, static_cast<uint4 *>(pack_fwd),
       static_cast<uint4 *>(pack_bwd));
   return ok();
@@ -369,7 +380,7 @@ static int pack_pair3(int Cin, int Cout, const float *w, int64_t stride_n, int64
 // out = act(ABN_eval(conv3x3(x) + conv_bias) [+ residual]); residual == nullptr takes the instantiations without the residual
 // read.  The kernel reads the residual through a __restrict__ pointer at the offsets it writes, so a residual that overlaps the
 // output is refused, not defined.
-template <int TN>
+template <int TN, int PIECES = 3>
 static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
                 const float *residual, const float *conv_bias, const float *mean, const float *var, const float *weight,
                 const float *bias, float eps, int activation, float slope, int geometry, int max_geometry, skd_stream_t stream) {
@@ -387,8 +398,12 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
   const uint4 *bp = static_cast<const uint4 *>(wpack);
 #define SKD_CONV3X3_CASE(ACT)                                                                                                 \
   case ACT:                                                                                                                   \
-    return (residual != nullptr ? launch3g<TN, ACT, true> : launch3g<TN, ACT, false>)(                                       \
-        x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
+    if constexpr (PIECES == 3)                                                                                                \
+      return (residual != nullptr ? launch3g<TN, ACT, true> : launch3g<TN, ACT, false>)(                                     \
+          x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);   \
+    else                                                                                                                      \
+      return residual != nullptr ? 0 : launch3g<TN, ACT, false, PIECES>(                                                      \
+          x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
   switch (activation) {
     SKD_CONV3X3_CASE(SKD_ACT_NONE);
     SKD_CONV3X3_CASE(SKD_ACT_RELU);
@@ -441,6 +456,21 @@ int skd_conv3x3_split_res_nhwc(int B, int H, int W, int Cin, int Cout, int dilat
                                skd_stream_t stream) {
   return run3<kTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation, slope,
                    geometry, 3, stream);
+}
+
+// include/skd_split2.h: the 128-column forward family on two pieces per operand (three products), and its two-plane weight image.
+int64_t skd_conv3x3_split2_pack_bytes(int Cin, int Cout) { return pack_bytes3<kTN, 2>(Cin, Cout); }
+
+int skd_conv3x3_split2_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                    int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
+  return pack_pair3<kTN, 2>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
+}
+
+int skd_conv3x3_split2_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                            const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                            float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+  return run3<kTN, 2>(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation,
+                      slope, geometry, 3, stream);
 }
 
 // include/skd_narrow.h: the 64-column form.

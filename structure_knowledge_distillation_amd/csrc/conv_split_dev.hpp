@@ -25,10 +25,14 @@ constexpr int kRB = kTN / kRPP;                            // float4 of the B pa
 //   chunk(h, row) = h * 128 + (row ^ 4 h),   h = k / 8
 // so the 32 lanes of a fragment read's lane half fetch 512 contiguous bytes (ds_read_b128, conflict-free), and the XOR puts the
 // 8-byte stores of the four threads that own one row's 16 k (two per h) on distinct banks within a store's 16-lane group.
+// PIECES = how many bf16 pieces an operand is split into: 3 (six products, fp32 accuracy) everywhere but in the two-piece forms
+// of include/skd_split2.h (PIECES = 2: a0 | a1, three products, a stage of 1024 chunks = 16,384 bytes).
 constexpr int kPlaneChunks = 2 * 128;                      // one piece of one operand: 4 KB
-constexpr int kOperandChunks = 3 * kPlaneChunks;           // a0 | a1 | a2
-constexpr int kStageChunks = 2 * kOperandChunks;           // A | B: 1536 chunks = 24,576 bytes
-constexpr size_t kConvLds = sizeof(uint4) * 2 * kStageChunks;
+constexpr int operand_chunks(int PIECES) { return PIECES * kPlaneChunks; }        // a0 | a1 | a2
+constexpr int stage_chunks(int PIECES) { return 2 * operand_chunks(PIECES); }     // A | B: 1536 chunks = 24,576 bytes
+constexpr size_t conv_lds(int PIECES) { return sizeof(uint4) * 2 * stage_chunks(PIECES); }
+constexpr int kOperandChunks = operand_chunks(3), kStageChunks = stage_chunks(3);
+constexpr size_t kConvLds = conv_lds(3);
 
 __device__ __forceinline__ float inv_std_of(float var, float eps) { return (var != 0.f || eps != 0.f) ? 1.f / sqrtf(var + eps) : 0.f; }
 
@@ -52,13 +56,24 @@ __device__ __forceinline__ void split4(float4 v, uint2 &p0, uint2 &p1, uint2 &p2
   p2.x = pack_bf16(v.x, v.y);
   p2.y = pack_bf16(v.z, v.w);
 }
-// ... written to the thread's 8-byte slot `dst` of the three planes of one operand's LDS image
+// The two-piece split: the first two of those pieces, the second residual v - p0 - p1 dropped (include/skd_split2.h).
+__device__ __forceinline__ void split4(float4 v, uint2 &p0, uint2 &p1) {
+  p0.x = pack_bf16(v.x, v.y);
+  p0.y = pack_bf16(v.z, v.w);
+  v.x -= bf16_lo(p0.x); v.y -= bf16_hi(p0.x); v.z -= bf16_lo(p0.y); v.w -= bf16_hi(p0.y);
+  p1.x = pack_bf16(v.x, v.y);
+  p1.y = pack_bf16(v.z, v.w);
+}
+// ... written to the thread's 8-byte slot `dst` of the PIECES planes of one operand's LDS image
+template <int PIECES = 3>
 __device__ __forceinline__ void split_store(float4 v, uint2 *dst) {
+  static_assert(PIECES == 2 || PIECES == 3, "two or three pieces");
   uint2 p0, p1, p2;
-  split4(v, p0, p1, p2);
+  if constexpr (PIECES == 3) split4(v, p0, p1, p2);
+  else split4(v, p0, p1);
   dst[0] = p0;
   dst[2 * kPlaneChunks] = p1;
-  dst[4 * kPlaneChunks] = p2;
+  if constexpr (PIECES == 3) dst[4 * kPlaneChunks] = p2;
 }
 // ... the same for an image whose pieces lie `plane` 8-byte slots apart (a TN = 64 B image: 2 * 128)
 __device__ __forceinline__ void split_store(float4 v, uint2 *dst, int plane) {
@@ -90,7 +105,20 @@ __device__ __forceinline__ int plane_slot(int row, int gkq) {
 constexpr int waves_m(int TN) { return 4 / (TN / 64); }                           // waves across M
 constexpr int wave_blocks_m(int TM, int TN) { return TM / waves_m(TN) / 32; }       // WM
 
-template <int TM, int TN = kTN, bool SWAP = false>
+// PIECES = 2 (include/skd_split2.h): 2 (WM + 2) reads feed 3 * 2 WM MFMAs, the three products a0 b1, a1 b0 (into `lo`), a0 b0
+// (into `hi`): the same two-set rule.
+template <int PIECES>
+struct Products;
+template <>
+struct Products<3> {
+  static constexpr int kN = 6, kPA[6] = {0, 1, 2, 0, 1, 0}, kPB[6] = {2, 1, 0, 1, 0, 0};
+};
+template <>
+struct Products<2> {
+  static constexpr int kN = 3, kPA[3] = {0, 1, 0}, kPB[3] = {1, 0, 0};
+};
+
+template <int TM, int TN = kTN, bool SWAP = false, int PIECES = 3>
 __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_blocks_m(TM, TN)][2],
                                          f32x16 (&hi)[wave_blocks_m(TM, TN)][2]) {
   constexpr int WM = wave_blocks_m(TM, TN);
@@ -99,28 +127,30 @@ __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_b
   const int wi = (wid / (TN / 64)) * (TM / waves_m(TN)), wj = (wid % (TN / 64)) * 64;
   const int half = lane >> 5, r = lane & 31;
   const uint4 *pa = stage + half * 128 + ((wi + r) ^ (half * 4));
-  const uint4 *pb = stage + kOperandChunks + half * TN + ((wj + r) ^ (half * 4));
-  bf16x8 a[WM][3], b[2][3];
+  const uint4 *pb = stage + operand_chunks(PIECES) + half * TN + ((wj + r) ^ (half * 4));
+  bf16x8 a[WM][PIECES], b[2][PIECES];
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {
+  for (int p = 0; p < PIECES; ++p) {
 #pragma unroll
     for (int i = 0; i < WM; ++i) a[i][p] = __builtin_bit_cast(bf16x8, pa[p * kPlaneChunks + 32 * i]);
 #pragma unroll
     for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(bf16x8, pb[p * 2 * TN + 32 * j]);
   }
-  constexpr int kPA[6] = {0, 1, 2, 0, 1, 0}, kPB[6] = {2, 1, 0, 1, 0, 0};
+  typedef Products<PIECES> P;
 #pragma unroll
-  for (int t = 0; t < 6; ++t)
+  for (int t = 0; t < P::kN; ++t)
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        f32x16 &dst = t < 5 ? lo[i][j] : hi[i][j];
-        dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SWAP ? kPB[t] : kPA[t]], b[j][SWAP ? kPA[t] : kPB[t]], dst, 0, 0, 0);
+        f32x16 &dst = t < P::kN - 1 ? lo[i][j] : hi[i][j];
+        dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SWAP ? P::kPB[t] : P::kPA[t]], b[j][SWAP ? P::kPA[t] : P::kPB[t]], dst, 0, 0, 0);
       }
 }
-template <int TM>
-__device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 64][2]) { tile_mma<TM>(stage, acc, acc); }
+template <int TM, int PIECES = 3>
+__device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 64][2]) {
+  tile_mma<TM, kTN, false, PIECES>(stage, acc, acc);
+}
 
 // The K loop of one output tile through the two LDS stages, shared by both kernels.  `Tile` supplies
 //   Stg                       the staging registers of one K-tile (every member written by load)
@@ -136,13 +166,17 @@ __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 
 // two trips so that the two staging sets and the two stages are named, not indexed: nothing is copied at the back edge.  Its
 // steady state (STEADY: the caller knows kt + 2 < nk) has no branch, so the compiler's count of the loads in flight is exact
 // there (a guard inside the loop made it wait for the loads it had just issued); the last one to three trips carry the guards.
-template <int DEPTH, bool STEADY, class Tile>
+// FENCE: the trip's MFMAs (and their fragment reads) are scheduled behind its split and stores, not among them.  Set by the
+// two-piece 1x1 kernel without prologue alone, whose fragment reads the scheduler otherwise hoists above the split at the price of
+// 8 registers more than its three-piece twin takes (profiles/r25_kernel_resources.md).
+template <int DEPTH, bool STEADY, bool FENCE, class Tile>
 __device__ __forceinline__ void k_trip(Tile &t, typename Tile::Stg &fill, typename Tile::Stg &next, const uint4 *cur, uint4 *nxt,
                                        int kt, int nk) {
   static_assert(DEPTH == 1 || DEPTH == 2, "load look-ahead of one or two K-tiles");
   if (DEPTH == 2) {
     if (STEADY || kt + 2 < nk) t.load(fill, kt + 2);       // `fill` held tile kt: stored one trip ago
     if (STEADY || kt + 1 < nk) t.store(next, nxt, kt + 1);
+    if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
     t.mma(cur);
   } else {
     if (STEADY || kt + 1 < nk) t.load(next, kt + 1);
@@ -151,22 +185,22 @@ __device__ __forceinline__ void k_trip(Tile &t, typename Tile::Stg &fill, typena
   }
   __syncthreads();
 }
-template <int DEPTH, class Tile>
+template <int DEPTH, int PIECES = 3, bool FENCE = false, class Tile>
 __device__ __forceinline__ void k_loop(Tile &t, int nk, uint4 *lds) {
   typename Tile::Stg s0, s1;                     // tiles of even / odd index
-  uint4 *const l0 = lds, *const l1 = lds + kStageChunks;
+  uint4 *const l0 = lds, *const l1 = lds + stage_chunks(PIECES);
   t.load(s0, 0);
   if (DEPTH == 2 && nk > 1) t.load(s1, 1);
   t.store(s0, l0, 0);
   __syncthreads();
   int kt = 0;
   for (; kt + 3 < nk; kt += 2) {
-    k_trip<DEPTH, true>(t, s0, s1, l0, l1, kt, nk);
-    k_trip<DEPTH, true>(t, s1, s0, l1, l0, kt + 1, nk);
+    k_trip<DEPTH, true, FENCE>(t, s0, s1, l0, l1, kt, nk);
+    k_trip<DEPTH, true, FENCE>(t, s1, s0, l1, l0, kt + 1, nk);
   }
-  k_trip<DEPTH, false>(t, s0, s1, l0, l1, kt, nk);                        // one to three trips left, kt even
-  if (kt + 1 < nk) k_trip<DEPTH, false>(t, s1, s0, l1, l0, kt + 1, nk);
-  if (kt + 2 < nk) k_trip<DEPTH, false>(t, s0, s1, l0, l1, kt + 2, nk);
+  k_trip<DEPTH, false, FENCE>(t, s0, s1, l0, l1, kt, nk);                        // one to three trips left, kt even
+  if (kt + 1 < nk) k_trip<DEPTH, false, FENCE>(t, s1, s0, l1, l0, kt + 1, nk);
+  if (kt + 2 < nk) k_trip<DEPTH, false, FENCE>(t, s0, s1, l0, l1, kt + 2, nk);
 }
 
 // Epilogue of one 32 x 32 accumulator block: rows row0 + frag_row(q), column col.  FULL: every row of the tile exists (all

@@ -253,11 +253,11 @@ def _cached(owner, attr, key, build, hold=None):
 
 
 def drop_conv3x3_packs(owner):
-    """Forget the weight packs conv3x3_pack_weights / conv3x3_train_packs / conv3x3_narrow_pack_weights / conv3x3_split_train's
-    narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under "pack3x3" /
-    "pack3x3_train")."""
+    """Forget the weight packs conv3x3_pack_weights (both piece counts) / conv3x3_train_packs / conv3x3_narrow_pack_weights /
+    conv3x3_split_train's narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under
+    "pack3x3" / "pack3x3_2" / "pack3x3_train")."""
     slot = owner if isinstance(owner, dict) else vars(owner)
-    for attr in ("_skd_conv3x3_pack", "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_train") + _NARROW_PACK_ATTRS:
+    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_2", "pack3x3_train") + _NARROW_PACK_ATTRS:
         slot.pop(attr, None)
 
 
@@ -461,7 +461,7 @@ def ppm_fold_supported(feats, sizes):
         and _is_cl(feats) and 3 * sum(sizes) <= 64 and len(sizes) <= 4
 
 
-def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False):
+def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False, pieces=3):
     """conv3x3(cat([upsample(p) for p in priors] + [feats], 1), weight, padding=1) (pspnet_combine.py:104-111) without
     the concatenated tensor and without convolving the priors' channels: the feature-map slice of the weight goes through
     the convolution, the priors through a (B s^2) x Cm x 9 Cout GEMM each and the fold kernel (csrc/ppm.hip).
@@ -470,7 +470,10 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
     convolution on csrc/conv3x3.hip when conv3x3_split_supported-style conditions hold (no grad; weights packed once in `cache`).
     `split_train`: the same for a network in training, where conv3x3_train_supported says so (conv3x3_split_train on the strided
     slice of the weight, so that autograd carries its gradient back into the full weight; packs once per weight version in `cache`).
-    `split_wgrad`: with `split_train`, the weight gradient of that slice on the split core too (conv3x3_split_train's ``wgrad``)."""
+    `split_wgrad`: with `split_train`, the weight gradient of that slice on the split core too (conv3x3_split_train's ``wgrad``).
+    `pieces` = 2: with `split3x3`, the frozen feature-map convolution on the two-piece core (conv3x3_split_eval's ``pieces``), its
+    pack under a key of its own in `cache`; the fold's matrix products and the training form are what they were."""
+    _check_pieces(pieces)
     import torch.nn.functional as F
     cm = priors[0].shape[1]
     n_prior = len(priors) * cm
@@ -490,7 +493,11 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
         extra = dict(wgrad=True) if split_wgrad else {}
         base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}), **extra)
     elif split3x3 and cache is not None and _conv3x3_ok(feats, weight[:, n_prior:], 1, 1, 1, 1, **_FROZEN):
-        base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3", {})), cout)
+        if pieces == 2:
+            base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3_2", {}), pieces=2),
+                                      cout, pieces=2)
+        else:
+            base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3", {})), cout)
     else:
         base = F.conv2d(feats, wf, None, 1, 1)
     # ONE GEMM of all levels' priors against all levels' weight blocks (only the diagonal blocks are used: 4x the
@@ -679,8 +686,20 @@ def abn_pack_eval_params(bn):
     return _cached(bn, "_skd_eval_pack", _version_key((bn.running_mean, bn.running_var, bn.weight, bn.bias), float(bn.eps)), build)[0]
 
 
+def _check_pieces(pieces):
+    """``pieces``: 3 (the six products of the three-piece split) or 2 (include/skd_split2.h: three products of two pieces)."""
+    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
+        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
+    return pieces
+
+
+def _need_split2_entry(name):
+    if not _lib.has_entry(name):
+        raise NotImplementedError("the active back-end does not provide %s (include/skd_split2.h)" % name)
+
+
 def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
-                     residual=None, pro=None):
+                     residual=None, pro=None, pieces=3):
     """act(bn_running(conv1x1(x)) [+ residual]) as ONE GEMM with the normalisation in its epilogue (inference only;
     networks/pspnet_combine.py:65-84 for the frozen teacher).  fp32 in and out; the products run on the bf16 MFMA with both
     operands split into three bf16 pieces and the six leading products accumulated in fp32 (csrc/conv1x1.hip): within 4 x of
@@ -689,7 +708,12 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
     GEMM's own error: profiles/r13_conv1x1_reduce_accuracy.md), exact on integer data; inputs beyond +-3.39e38 or infinite give NaN.  x (B, Cin, H, W)
     and residual / result (B, Cout, H, W) in channels-last memory; conv_weight (Cout, Cin, 1, 1).
     ``pro`` = ``abn_pack_eval_params(bn)`` of an eval-mode BatchNorm + ReLU that PRECEDES the convolution
-    (bn2 -> relu -> conv3, pspnet_combine.py:71-75): applied to x on its way into the GEMM, x itself is left untouched."""
+    (bn2 -> relu -> conv3, pspnet_combine.py:71-75): applied to x on its way into the GEMM, x itself is left untouched.
+    ``pieces`` = 2: the reduced-precision form of include/skd_split2.h -- two bf16 pieces per operand and the three products
+    a0 b1, a1 b0, a0 b0: about 4e-6 of the output's largest magnitude per product instead of 3e-7 (tests/split2_ref.py is its model,
+    tests/test_split2_gpu.py the comparison; profiles/r25_split2_accuracy.md); a back-end without the entries raises, the call is
+    never downgraded."""
+    pieces = _check_pieces(pieces)
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
         raise RuntimeError("conv1x1_abn_eval is inference-only")
     _lib.require_device(x, conv_weight, running_mean, running_var, weight, bias, residual)
@@ -708,14 +732,20 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
         _lib.require_device(pro)
         if pro.dtype != torch.float32 or tuple(pro.shape) != (4, k) or not pro.is_contiguous():
             raise ValueError("pro must be the (4, Cin) fp32 pack of abn_pack_eval_params")
-        _lib.check(_lib.get().skd_conv1x1_abn_pro_nhwc(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
-                                                       running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight),
-                                                       _lib.ptr(bias), float(eps), pro.data_ptr(), act, float(slope),
-                                                       _lib.stream_of(x)), "skd_conv1x1_abn_pro_nhwc")
+        entry = "skd_conv1x1_abn_pro_nhwc" if pieces == 3 else "skd_conv1x1_abn2_pro_nhwc"
+        if pieces == 2:
+            _need_split2_entry(entry)
+        _lib.check(getattr(_lib.get(), entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
+                                              running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight),
+                                              _lib.ptr(bias), float(eps), pro.data_ptr(), act, float(slope),
+                                              _lib.stream_of(x)), entry)
         return out
-    _lib.check(_lib.get().skd_conv1x1_abn_nhwc(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
-                                               running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
-                                               float(eps), act, float(slope), _lib.stream_of(x)), "skd_conv1x1_abn_nhwc")
+    entry = "skd_conv1x1_abn_nhwc" if pieces == 3 else "skd_conv1x1_abn2_nhwc"
+    if pieces == 2:
+        _need_split2_entry(entry)
+    _lib.check(getattr(_lib.get(), entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
+                                          running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
+                                          float(eps), act, float(slope), _lib.stream_of(x)), entry)
     return out
 
 
@@ -806,17 +836,25 @@ def _conv3x3_packs(w, owner, attr, entry, what, images, bytes_entry="skd_conv3x3
     return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build, hold=w)
 
 
-def conv3x3_pack_weights(conv, weight=None, owner=None):
+def conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3):
     """The three bf16 planes of a frozen 3x3 convolution's weight in the layout csrc/conv3x3.hip streams into LDS (6 bytes per
     weight), cached on ``owner`` (default: the conv module) like abn_pack_eval_params and rebuilt when the weight is written or
     moved -- by THE RULE above _version_key: a fused optimizer's step counts as a write only with
     ``kd_model.advance_versions_after_step`` registered on it (NetModel's has it; a caller who trains with a fused optimizer of
     their own registers it themselves).  ``weight`` (default ``conv.weight``) may be any strided (Cout, Cin, 3, 3) view -- the PSP
     bottleneck packs the feature-map slice of its weight -- and either memory format gives the same pack.  The first call
-    allocates: a frozen network makes it in its eager warm-up steps, before any graph capture."""
+    allocates: a frozen network makes it in its eager warm-up steps, before any graph capture.
+    ``pieces`` = 2: the two-plane image of include/skd_split2.h (4 bytes per weight: the first two planes of the other), for
+    ``conv3x3_split_eval(..., pieces=2)``; cached under the same rule in a slot of its own, so both packs of one module coexist."""
+    pieces = _check_pieces(pieces)
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_pack_weights is for frozen (no-grad) convolutions")
+    if pieces == 2:
+        for name in (_PACK2_ENTRY, _PACK2_BYTES):
+            _need_split2_entry(name)
+        return _conv3x3_packs(w, conv if owner is None else owner, _PACK2_ATTR, _PACK2_ENTRY, "conv3x3_pack_weights", (True,),
+                              _PACK2_BYTES)[0]
     return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_pack", "skd_conv3x3_split_pack_weights",
                           "conv3x3_pack_weights", (True,))[0]
 
@@ -834,6 +872,9 @@ def conv3x3_train_packs(weight, owner=None):
 
 _ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
 _RES_ENTRY = "skd_conv3x3_split_res_nhwc"
+# include/skd_split2.h: the two-piece form of the frozen 128-column convolution, its pack entry, its size query, its cache slot
+_SPLIT2_ENTRY, _PACK2_ENTRY, _PACK2_BYTES = "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_pack_bytes"
+_PACK2_ATTR = "_skd_conv3x3_pack2"
 # include/skd_narrow.h: the 64-column form of csrc/conv3x3.hip.  Its one convolution entry takes the residual pointer.
 _NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
 _NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
@@ -842,11 +883,12 @@ _NARROW_PACK_ATTRS = ("_skd_conv3x3_narrow_pack", "_skd_conv3x3_train_pack_wide"
 
 def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0, residual=None):
     """The one launcher of the split-core 3x3 forms: act(bn_running(conv3x3(x) + conv_bias) [+ residual]) by ``entry`` --
-    skd_conv3x3_split_nhwc, or skd_conv3x3_split_res_nhwc / skd_conv3x3_narrow_nhwc, which take the ``residual`` pointer (None
+    skd_conv3x3_split_nhwc, its two-piece twin skd_conv3x3_split2_nhwc, or skd_conv3x3_split_res_nhwc / skd_conv3x3_narrow_nhwc, which take the ``residual`` pointer (None
     included)."""
     lib = _lib.get()
     b, cin, h, w = x.shape
-    pack_bytes = lib.skd_conv3x3_narrow_pack_bytes if entry == _NARROW_ENTRY else lib.skd_conv3x3_split_pack_bytes
+    pack_bytes = (lib.skd_conv3x3_narrow_pack_bytes if entry == _NARROW_ENTRY
+                  else getattr(lib, _PACK2_BYTES) if entry == _SPLIT2_ENTRY else lib.skd_conv3x3_split_pack_bytes)
     if pack.numel() != pack_bytes(cin, cout):
         raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
     mean = var = gamma = beta = None
@@ -874,14 +916,22 @@ def _residual_cl(x, cout, residual):
     return _cl(residual)
 
 
-def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0):
+def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0, pieces=3):
     """act(bn_running(conv3x3(x) + conv_bias)) with ``pack = conv3x3_pack_weights(...)`` (inference only; conv3x3_split_supported
     says when).  fp32 in and out, channels-last; the products run on the bf16 MFMA through the three-piece split (csrc/conv3x3.hip):
     within 4 x of the fp32 convolution's error against a float64 result and never above 2e-5 of the output's largest magnitude
     (tests/test_conv3x3_split_gpu.py), exact on integer data.  ``bn``: an eval-mode InPlace-ABN module (or None) whose running
-    statistics and affine parameters go into the epilogue; ``activation``: 'none' / 'relu' / 'leaky_relu' (slope: ``bn.slope``)."""
+    statistics and affine parameters go into the epilogue; ``activation``: 'none' / 'relu' / 'leaky_relu' (slope: ``bn.slope``).
+    ``pieces`` = 2: the reduced-precision form of include/skd_split2.h with ``pack = conv3x3_pack_weights(..., pieces=2)`` -- two
+    pieces per operand, the products a0 b1, a1 b0, a0 b0: within 2e-5 of its float64 model (tests/split2_ref.py), which itself is
+    about 4e-6 of the output's largest magnitude from the exact product (profiles/r25_split2_accuracy.md).  A back-end without the
+    entry raises; the call is never downgraded."""
+    pieces = _check_pieces(pieces)
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_split_eval is inference-only")
+    if pieces == 2:
+        _need_split2_entry(_SPLIT2_ENTRY)
+        return _conv3x3_launch(_SPLIT2_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry)
     return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias, bn, activation, geometry)
 
 

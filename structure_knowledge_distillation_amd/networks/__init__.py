@@ -3,3 +3,4 @@ pspnet_combine (student / teacher PSPNet), sagan_models (holistic discriminator)
 (spectral norm on the gfx950 kernel) and kd_model (NetModel, the step orchestrator)."""
 from .pspnet_combine import fuse_for_inference  # noqa: E402,F401  (the student's fused inference form)
 from .pspnet_combine import route_training_convs  # noqa: E402,F401  (the student's training form on the split core)
+from .pspnet_combine import set_teacher_pieces  # noqa: E402,F401  (the frozen teacher on two bf16 pieces, an accuracy trade)

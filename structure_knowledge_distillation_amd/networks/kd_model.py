@@ -31,7 +31,7 @@ from ..utils import parallel as parallel_old
 from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
 from ..utils.utils import print_model_parm_nums, to_tuple_str  # noqa: F401
-from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_training_convs
+from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_training_convs, set_teacher_pieces
 from .sagan_models import Discriminator
 
 
@@ -232,6 +232,13 @@ class NetModel():
         print_model_parm_nums(teacher, "teacher_model")
         for p in teacher.parameters():
             p.requires_grad_(False)
+        # args.teacher_pieces (None: SKD_TEACHER_PIECES, default "3"): 2 = the frozen teacher's split-core convolutions on two bf16
+        # pieces per operand and three products (pspnet_combine.set_teacher_pieces, include/skd_split2.h) -- an ACCURACY trade: its
+        # outputs move by about 1.5e-5 of their largest magnitude (profiles/r25_split2_accuracy.md).  Independent of the five student
+        # switches; off by default.  Set here, before any warm-up step or teacher-graph capture sees the network.
+        self.teacher_pieces = _teacher_pieces(getattr(args, "teacher_pieces", None))
+        if self.teacher_pieces == 2:
+            set_teacher_pieces(teacher, 2)
         self.parallel_teacher = self.DataParallelModelProcess(teacher, 2, "eval", device)
         self.teacher = teacher
         parallel_old.broadcast_module(teacher)
@@ -866,6 +873,15 @@ def advance_versions_after_step(optimizer, args=None, kwargs=None):
         torch.autograd.graph.increment_version(written)      # one host call for all of them
 
 
+def _teacher_pieces(value):
+    """``value`` (None: the environment's SKD_TEACHER_PIECES, default "3") as 2 or 3; anything else is a ValueError."""
+    if value is None:
+        value = os.environ.get("SKD_TEACHER_PIECES", "3")
+    if isinstance(value, bool) or str(value).strip() not in ("2", "3"):
+        raise ValueError("teacher_pieces / SKD_TEACHER_PIECES must be 2 or 3, not %r" % (value,))
+    return int(str(value).strip())
+
+
 def default_args(**overrides):
     """The flag defaults of utils/train_options.py:18-63 that shape the step, as a namespace
     (``run_train_val.sh`` overrides: weight_decay 5e-4, lambda_pa 0.5)."""
@@ -879,7 +895,7 @@ def default_args(**overrides):
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
-        split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None)
+        split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
@@ -892,4 +908,5 @@ def default_args(**overrides):
         a.split_narrow_wgrad = os.environ.get("SKD_SPLIT_NARROW_WGRAD", "0") == "1"
     if a.split_shortcut is None:       # effective only together with split_train
         a.split_shortcut = os.environ.get("SKD_SPLIT_SHORTCUT", "0") == "1"
+    a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     return a

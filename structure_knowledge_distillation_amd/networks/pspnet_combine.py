@@ -107,6 +107,22 @@ NARROW_WGRAD_ROUTING_EXCLUDED = frozenset({(64, 64, 1), (64, 128, 1), (128, 64, 
 # a 64-channel side (the 128 x 64 tile form, one tile per slice) are 0.19 x and 0.39 x the library's speed -- their second launch
 # sums up to 768 slices on 2048 threads and is bound by the latency of that chain -- so these two keep the library.
 SHORTCUT_ROUTING_EXCLUDED = frozenset({(128, 64, 1, "wgrad"), (64, 128, 2, "wgrad")})
+# The frozen teacher on TWO bf16 pieces per operand and three products (set_teacher_pieces(model, 2), below; a sixth opt-in, an
+# ACCURACY trade: include/skd_split2.h): the calls of a marked Bottleneck network that run on the split core today -- the 1x1
+# reduce / down-sample GEMMs and the fused tail (csrc/conv1x1.hip), the routed 3x3 convolutions, dsn[0] and the feature half of
+# the PSP bottleneck (csrc/conv3x3.hip) -- take the two-piece entries.  A shape that measures behind its three-piece twin by more
+# than the spread is listed here as ("1x1", K, N) or ("3x3", Cin, Cout, dilation) and keeps three pieces
+# (profiles/r25_split2_isolated.md has every shape).
+SPLIT2_ROUTING_EXCLUDED = frozenset()
+_SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
+                   "skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn2_pro_nhwc")
+
+
+def _pieces(module, *shape):
+    """The piece count of a frozen split-core call of ``module``: its mark (set_teacher_pieces; 3 without one), and 3 for a
+    ``shape`` that SPLIT2_ROUTING_EXCLUDED lists."""
+    pieces = getattr(module, "_skd_teacher_pieces", 3)
+    return 3 if pieces == 3 or shape in SPLIT2_ROUTING_EXCLUDED else pieces
 
 
 def _narrow_shape(conv):
@@ -193,13 +209,15 @@ def _blas_tail(module, x):
     return BLAS_TAILS and not module.training and not torch.is_grad_enabled()
 
 
-def _conv1x1_bn_eval(x, conv, bn, relu):
+def _conv1x1_bn_eval(x, conv, bn, relu, owner=None):
     """relu?(bn(conv1x1(x))) of the frozen network for a call blas_1x1_bn_supported accepted: the split-core GEMM of csrc/conv1x1.hip
-    where SPLIT_REDUCE routes it there, the library GEMM with the folded BN otherwise."""
+    where SPLIT_REDUCE routes it there -- on two pieces where ``owner`` (the calling block) is marked by set_teacher_pieces -- the
+    library GEMM with the folded BN otherwise."""
     if (SPLIT_REDUCE and not (conv.in_channels == 512 and conv.out_channels == 128)      # the library wins 512 -> 128 (r11)
             and getattr(bn, "activation", None) == "none" and SF.conv1x1_abn_supported(x, conv)):
+        extra = dict(pieces=2) if _pieces(owner, "1x1", conv.in_channels, conv.out_channels) == 2 else {}
         return SF.conv1x1_abn_eval(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps,
-                                   "relu" if relu else "none")
+                                   "relu" if relu else "none", **extra)
     return SF.conv1x1_bn_blas(x, conv, bn, relu=relu)
 
 
@@ -208,10 +226,16 @@ def _conv3x3_split(x, conv):
             and SF.conv3x3_split_supported(x, conv))
 
 
-def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False):
+def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False, owner=None):
     """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, for a call one of the
     SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names).  ``narrow``: the
-    64-column form (the same file, include/skd_narrow.h) on its own pack, for a call SF.conv3x3_narrow_supported accepted."""
+    64-column form (the same file, include/skd_narrow.h) on its own pack, for a call SF.conv3x3_narrow_supported accepted.
+    ``owner``: the calling module of a frozen teacher; where set_teacher_pieces marked it, the wide form without residual runs on
+    two pieces (its own pack)."""
+    if (not narrow and residual is None
+            and _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]) == 2):
+        return SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv, pieces=2), conv.out_channels, conv.dilation[0], conv.bias, bn,
+                                     activation, pieces=2)
     if narrow:
         return SF.conv3x3_narrow_eval(x, SF.conv3x3_narrow_pack_weights(conv), conv.out_channels, conv.dilation[0], residual, conv.bias,
                                       bn, activation)
@@ -352,11 +376,11 @@ class Bottleneck(nn.Module):
         if _fused(self, x):
             blas = _blas_tail(self, x)
             if blas and SF.blas_1x1_bn_supported(x, self.conv1):
-                out = _conv1x1_bn_eval(x, self.conv1, self.bn1, relu=True)
+                out = _conv1x1_bn_eval(x, self.conv1, self.bn1, relu=True, owner=self)
             else:
                 out = self.bn1.forward_relu(self.conv1(x))
             # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
-            c2 = _split_conv(out, self.conv2) if _conv3x3_split(out, self.conv2) else self.conv2(out)
+            c2 = _split_conv(out, self.conv2, owner=self) if _conv3x3_split(out, self.conv2) else self.conv2(out)
             tail = (not self.training and _fused_tail(x) and SF.conv1x1_abn_supported(c2, self.conv3) and self.conv3.in_channels <= 512
                     and getattr(self.bn2, "activation", None) == "none" and getattr(self.bn3, "activation", None) == "none")
             if not tail:
@@ -365,13 +389,14 @@ class Bottleneck(nn.Module):
                 residual = x
             elif (blas and len(self.downsample) == 2 and SF.blas_1x1_bn_supported(x, self.downsample[0])
                   and getattr(self.downsample[1], "activation", None) == "none"):
-                residual = _conv1x1_bn_eval(x, self.downsample[0], self.downsample[1], relu=False)
+                residual = _conv1x1_bn_eval(x, self.downsample[0], self.downsample[1], relu=False, owner=self)
             else:
                 residual = self.downsample(x)
             if tail:
+                extra = dict(pieces=2) if _pieces(self, "1x1", self.conv3.in_channels, self.conv3.out_channels) == 2 else {}
                 return SF.conv1x1_abn_eval(c2, self.conv3.weight, self.bn3.running_mean, self.bn3.running_var, self.bn3.weight,
                                            self.bn3.bias, self.bn3.eps, "relu", residual=residual,
-                                           pro=SF.abn_pack_eval_params(self.bn2))
+                                           pro=SF.abn_pack_eval_params(self.bn2), **extra)
             return self.bn3.forward_relu(self.conv3(out), residual)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -437,6 +462,8 @@ class PSPModule(nn.Module):
                     self._fold_cache = {}
                 min_cin = getattr(self, "_skd_train_min_cin", None)
                 extra = dict(split_wgrad=True) if _wgrad_routed(self, feats.shape[1], conv.out_channels, 1) else {}
+                if not self.training and _pieces(self, "3x3", feats.shape[1], conv.out_channels, 1) == 2:
+                    extra["pieces"] = 2        # the frozen feature half on two pieces (set_teacher_pieces)
                 out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache,
                                              split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
                                              split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
@@ -503,7 +530,7 @@ class ResNet(nn.Module):
         conv, bn = self.dsn[0], self.dsn[1]
         if (not self.training and not torch.is_grad_enabled() and getattr(bn, "activation", None) in ("none", "relu", "leaky_relu")
                 and hasattr(bn, "running_mean") and _conv3x3_split(x3, conv)):
-            return self.dsn[3](_split_conv(x3, conv, bn, bn.activation))
+            return self.dsn[3](_split_conv(x3, conv, bn, bn.activation, owner=self))
         if _train_routed(self, x3, conv):      # the training form: the same sequence with dsn[0] (bias in the epilogue) on the split core
             return self.dsn[3](self.dsn[2](bn(_train_conv(self, conv, x3))))
         return self.dsn(x3)
@@ -622,6 +649,44 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
                     SF.conv3x3_narrow_pack_weights(conv)
                 elif how:
                     SF.conv3x3_pack_weights(conv)
+    return model
+
+
+def set_teacher_pieces(model, pieces=2):
+    """Mark ``model`` (a frozen Bottleneck network: the teacher) for ``pieces`` bf16 pieces per operand on the split core and
+    return it.
+
+    ``pieces=2`` -- an ACCURACY trade, opt-in: every call of the network that runs on the split core today takes the two-piece
+    entries of include/skd_split2.h (three bf16 products instead of six): the Bottlenecks' reduce and stride-1 down-sample 1x1 GEMMs
+    (_conv1x1_bn_eval), their fused tails, their routed 3x3 convolutions (_split_conv), the ResNet's dsn[0] and the feature half of
+    the PSP bottleneck -- except the shapes of SPLIT2_ROUTING_EXCLUDED.  The outputs move by about 1.5e-5 of their largest magnitude
+    (profiles/r25_split2_accuracy.md; three pieces: 1e-6).  The marks sit on the Bottlenecks, the ResNet and the PSPModule;
+    BasicBlocks (the student), the 64-column form, anything under grad or in training mode, the library GEMM for 512 -> 128, the
+    PSP fold's matrix products and the heads are what they were.  Call it before the network's first forward, warm-up step or
+    graph capture, so that the two-plane packs are made eagerly.
+    ``pieces=3`` clears the marks and drops the two-plane packs.  On a back-end without the entries ``pieces=2`` warns
+    (RuntimeWarning) and leaves three pieces."""
+    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
+        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
+    if pieces == 2 and not all(_lib.has_entry(n) for n in _SPLIT2_ENTRIES):
+        import warnings
+        warnings.warn("set_teacher_pieces: this back-end lacks the two-piece entries (include/skd_split2.h); the teacher stays on "
+                      "three pieces", RuntimeWarning, stacklevel=2)
+        pieces = 3
+    teacher = any(isinstance(m, Bottleneck) for m in model.modules())      # a BasicBlock network (the student) is left untouched
+    for m in model.modules():
+        if not isinstance(m, (Bottleneck, ResNet, PSPModule)):
+            continue
+        if pieces == 2:
+            if teacher:
+                m._skd_teacher_pieces = 2
+            continue
+        vars(m).pop("_skd_teacher_pieces", None)
+        owners = ((m.conv2,) if isinstance(m, Bottleneck) else (m.dsn[0],) if isinstance(m, ResNet) else (getattr(m, "_fold_cache", {}),))
+        for owner in owners:
+            slot = owner if isinstance(owner, dict) else vars(owner)
+            for attr in ("_skd_conv3x3_pack2", "pack3x3_2"):
+                slot.pop(attr, None)
     return model
 
 

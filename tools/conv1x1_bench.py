@@ -4,7 +4,7 @@
   (b) one fp32-MFMA GEMM with the ABN / residual / ReLU epilogue (csrc/conv1x1.hip)
   (c) torch.ops.aten.miopen_convolution_relu / miopen_convolution_add_relu with the BN folded into weight + bias
       (MIOpen's own fusion; probed, may be unsupported for fp32 NHWC on this build)
-    python tools/conv1x1_bench.py [reps]
+    python tools/conv1x1_bench.py [reps] [--pieces {2,3}]     # --pieces 2: (b) on the two-piece core (include/skd_split2.h)
 """
 import json
 import os
@@ -28,6 +28,14 @@ def main():
     import importlib
     IA = importlib.import_module("structure_knowledge_distillation_amd.libs.inplace_abn")
     _lib.load()
+    pieces = 3
+    if "--pieces" in sys.argv:
+        i = sys.argv.index("--pieces")
+        pieces = int(sys.argv[i + 1])
+        if pieces not in (2, 3):
+            raise SystemExit("--pieces takes 2 or 3")
+        del sys.argv[i:i + 2]
+    pk = dict(pieces=2) if pieces == 2 else {}
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     dev = torch.device("cuda", 0)
     B = 8
@@ -54,11 +62,11 @@ def main():
         with torch.no_grad():
             t_conv = timed(lambda: conv(x))
             t_a = timed(lambda: IA.abn_eval_fused(conv(x), w, b, rm, rv, 1e-5, "relu", 0.01, res))
-            row = {"cin": cin, "cout": cout, "hw": hw, "count": count, "residual": has_res, "gflop": round(flop / 1e9, 1),
+            row = {"pieces": pieces, "cin": cin, "cout": cout, "hw": hw, "count": count, "residual": has_res, "gflop": round(flop / 1e9, 1),
                    "conv_only_us": round(t_conv * 1e3, 1), "conv_only_tflops": round(flop / t_conv / 1e9, 1),
                    "conv_plus_abn_us": round(t_a * 1e3, 1)}
             if SF.conv1x1_abn_supported(x, conv):
-                t_b = timed(lambda: SF.conv1x1_abn_eval(x, conv.weight, rm, rv, w, b, 1e-5, "relu", 0.01, res))
+                t_b = timed(lambda: SF.conv1x1_abn_eval(x, conv.weight, rm, rv, w, b, 1e-5, "relu", 0.01, res, **pk))
                 row.update({"fused_gemm_us": round(t_b * 1e3, 1), "fused_gemm_tflops": round(flop / t_b / 1e9, 1),
                             "fused_gemm_frac_fp32_mfma": round(flop / t_b / 1e9 / 157.3, 3), "speedup_vs_conv_plus_abn": round(t_a / t_b, 3)})
                 tot["conv_plus_abn_ms"] += count * t_a

@@ -2,7 +2,7 @@
 against the split-core implicit GEMM of csrc/conv3x3.hip in each tile geometry (0 = shipped choice, 1 = 128-pixel tiles,
 2 = 64-pixel tiles, 3 = 128 for the whole rounds + 64 for the rest).  HIP events around `reps` back-to-back calls after >= 30 ms
 of warm-up launches, three repeats; one JSON line per problem.
-    python tools/conv3x3_bench.py [reps]
+    python tools/conv3x3_bench.py [reps] [--pieces {2,3}]     # --pieces 2: the split side on the two-piece core (include/skd_split2.h)
     python tools/conv3x3_bench.py pmc      # two launches of each path per problem and nothing else: for counter-only rocprofv3 --pmc runs
     python tools/conv3x3_bench.py pmc-summary <counter_collection.csv> [...]    # mean counter value per kernel and grid
 """
@@ -29,6 +29,14 @@ def main():
     _skd.configure_miopen()
     from structure_knowledge_distillation_amd import _lib, functional as SF
     _lib.load()
+    pieces = 3
+    if "--pieces" in sys.argv:
+        i = sys.argv.index("--pieces")
+        pieces = int(sys.argv[i + 1])
+        if pieces not in (2, 3):
+            raise SystemExit("--pieces takes 2 or 3")
+        del sys.argv[i:i + 2]
+    pk = dict(pieces=2) if pieces == 2 else {}
     pmc = len(sys.argv) > 1 and sys.argv[1] == "pmc"
     reps = int(sys.argv[1]) if len(sys.argv) > 1 and not pmc else 20
     dev = torch.device("cuda", 0)
@@ -67,28 +75,29 @@ def main():
             x = torch.relu(torch.randn(B, cin, hw, hw, device=dev)).contiguous(memory_format=torch.channels_last)
             conv = torch.nn.Conv2d(cin, cout, 3, 1, d, d, bias=bias).to(dev).to(memory_format=torch.channels_last).eval()
             flop = 2.0 * B * hw * hw * 9 * cin * cout
-            row = {"problem": name, "cin": cin, "cout": cout, "hw": hw, "dilation": d, "count": count, "gflop": round(flop / 1e9, 1)}
+            row = {"problem": name, "pieces": pieces, "cin": cin, "cout": cout, "hw": hw, "dilation": d, "count": count, "gflop": round(flop / 1e9, 1)}
             if pmc:
-                pack = SF.conv3x3_pack_weights(conv)
+                pack = SF.conv3x3_pack_weights(conv, **pk)
                 for _ in range(2):
                     F.conv2d(x, conv.weight, conv.bias, 1, d, d)
-                    SF.conv3x3_split_eval(x, pack, cout, d, conv.bias)
+                    SF.conv3x3_split_eval(x, pack, cout, d, conv.bias, **pk)
                 torch.cuda.synchronize()
                 row["algorithmic_mb"] = {"x": round(x.numel() * 4 / 1e6, 1), "w_fp32": round(conv.weight.numel() * 4 / 1e6, 1),
-                                         "w_pack": round(conv.weight.numel() * 6 / 1e6, 1), "y": round(B * hw * hw * cout * 4 / 1e6, 1)}
+                                         "w_pack": round(conv.weight.numel() * 2 * pieces / 1e6, 1), "y": round(B * hw * hw * cout * 4 / 1e6, 1)}
                 print(json.dumps(row), flush=True)
                 continue
             row["miopen_us"] = timed(lambda: F.conv2d(x, conv.weight, conv.bias, 1, d, d))
             assert SF.conv3x3_split_supported(x, conv)
-            pack = SF.conv3x3_pack_weights(conv)
+            pack = SF.conv3x3_pack_weights(conv, **pk)
             for g in (0, 1, 2, 3):
-                row["split_g%d_us" % g] = timed(lambda: SF.conv3x3_split_eval(x, pack, cout, d, conv.bias, geometry=g))
+                row["split_g%d_us" % g] = timed(lambda: SF.conv3x3_split_eval(x, pack, cout, d, conv.bias, geometry=g, **pk))
             want = F.conv2d(x, conv.weight, conv.bias, 1, d, d)
-            got = SF.conv3x3_split_eval(x, pack, cout, d, conv.bias)
+            got = SF.conv3x3_split_eval(x, pack, cout, d, conv.bias, **pk)
             row["max_abs_diff_over_max"] = float((got - want).abs().max() / want.abs().max())
             t_m, t_s = min(row["miopen_us"]), min(row["split_g0_us"])
             row["split_tflops_algorithmic"] = round(flop / t_s / 1e6, 1)
-            row["split_frac_of_six_product_bound"] = round(6 * flop / 2.5e15 / (t_s * 1e-6), 3)
+            row["split_frac_of_%s_product_bound" % ("six" if pieces == 3 else "three")] = round(
+                pieces * (pieces + 1) // 2 * flop / 2.5e15 / (t_s * 1e-6), 3)
             row["speedup"] = round(t_m / t_s, 3)
             if "not routed" not in name:
                 total["miopen_ms"] += count * t_m / 1e3
