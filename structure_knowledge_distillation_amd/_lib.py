@@ -22,6 +22,7 @@ NARROW_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_
 NARROW_WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow_wgrad.h"))
 SHORTCUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_shortcut.h"))
 SPLIT2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_split2.h"))
+BNSTATS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_bnstats.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -248,6 +249,18 @@ SPLIT2_SIGNATURES = {
     "skd_conv1x1_abn2_pro_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _F, _P]),
 }
 
+# Entry points declared in include/skd_bnstats.h (csrc/conv3x3.hip with STATS, csrc/abn_nhwc.hip): the training forward of the
+# student's 3x3 convolutions with the batch-norm statistics records from its epilogue, and their finalize, extension entries in a
+# table of their own like the ten above (tests/test_conv3x3_bnstats_cpu.py checks header <-> table <-> exported symbols,
+# tests/test_conv3x3_bnstats_gpu.py holds the guard-band cases).  A back-end without them leaves the convolutions and the ABN
+# forward behind them where they were: nothing raises.
+BNSTATS_SIGNATURES = {
+    "skd_conv3x3_bnstats_floats": (_L, [_L, _I]),
+    "skd_conv3x3_split_stats_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "skd_conv3x3_narrow_stats_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "skd_abn_stats_from_partials_nhwc": (_I, [_L, _I, _P, _L, _P, _P, _P, _P, _F, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -278,7 +291,8 @@ def load(path=None):
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
-                  WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES):
+                  WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES,
+                  BNSTATS_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -3,6 +3,7 @@
 // ticket-counter pool, and the two-launch entries.  The register-resident one-launch passes on top of them are in
 // abn_fused.hip, the planar NCHW passes in abn.hip, the shared device helpers and geometries in abn_dev.hpp.
 #include "abn_dev.hpp"
+#include "skd_bnstats.h"
 
 namespace skd {
 namespace {
@@ -388,6 +389,68 @@ static int launch_apply_nhwc(int64_t rows, int C, float *x, const float *res, co
   return known ? ok() : 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Finalize of the statistics a convolution's epilogue emitted (include/skd_bnstats.h; csrc/conv3x3.hip, block_stats): per
+// channel, nb = ceil(rows / 32) records (mean, M2) of 32 rows each (the last: rows - 32 (nb - 1)) at part[(b * C + c) * 2].
+// A workgroup of 1024 threads owns 8 channels: thread (run r = t / 8, channel t % 8) -- 8 lanes read 64 contiguous bytes of one
+// block -- takes the blocks r, r + 128, r + 256, ... in ONE pass, in double, as sums shifted by the pivot K = the mean of the
+// channel's block 0 (a block mean sits within the channel's spread of its mean, and the finished records are there to take it
+// from -- which the epilogue that wrote them had not):  S1 = sum n_b (mean_b - K),  S2 = sum M2_b + n_b (mean_b - K)^2, the way
+// abn_stats_nhwc2_kernel's finisher sums its partial rows.  The 128 runs of a channel are added in a fixed order: a butterfly over
+// the 8 runs of a wave, then the 16 waves in turn.  mean = K + S1 / rows, M2 = S2 - S1^2 / rows.  Fixed assignment, fixed order,
+// no atomics: the same bits on every call; a constant channel gives S1 = S2 = 0 and its value back exactly.  mean / biased var
+// and the running update are abn_stats_nhwc2_kernel's, statement for statement.
+// ---------------------------------------------------------------------------------------------
+constexpr int kFinCh = 8, kFinRuns = 128, kFinThreads = kFinCh * kFinRuns;
+
+__global__ __launch_bounds__(kFinThreads) void abn_stats_from_partials_kernel(
+    const float *__restrict__ part, float *__restrict__ mean, float *__restrict__ var, float *running_mean, float *running_var,
+    int64_t rows, int C, float momentum) {
+  __shared__ double s_1[kFinThreads / kWave][kFinCh], s_2[kFinThreads / kWave][kFinCh];
+  const int t = threadIdx.x, cl = t % kFinCh, r = t / kFinCh;
+  const int c = blockIdx.x * kFinCh + cl;
+  const int64_t nb = (rows + 31) / 32;
+  const float2 *rec = reinterpret_cast<const float2 *>(part) + c;
+  const double last = (double)(rows - 32 * (nb - 1));       // rows of the last block
+  const double K = (double)rec[0].x;
+  double a1 = 0.0, a2 = 0.0;
+#pragma unroll 4
+  for (int64_t b = r; b < nb; b += kFinRuns) {
+    const float2 v = rec[b * C];
+    const double nbk = b == nb - 1 ? last : 32.0;
+    const double d = (double)v.x - K;
+    a1 += nbk * d;
+    a2 += (double)v.y + nbk * d * d;
+  }
+#pragma unroll
+  for (int m = kFinCh; m < kWave; m *= 2) {                 // the 8 runs of this wave that share the channel
+    a1 += __shfl_xor(a1, m, kWave);
+    a2 += __shfl_xor(a2, m, kWave);
+  }
+  const int lane = t & (kWave - 1), wid = t / kWave;
+  if (lane < kFinCh) {
+    s_1[wid][lane] = a1;
+    s_2[wid][lane] = a2;
+  }
+  __syncthreads();
+  if (t < kFinCh) {
+    double S1 = 0.0, S2 = 0.0;
+#pragma unroll
+    for (int w = 0; w < kFinThreads / kWave; ++w) {
+      S1 += s_1[w][t];
+      S2 += s_2[w][t];
+    }
+    const double cnt = (double)rows, d = S1 / cnt;
+    double v = (S2 - S1 * d) / cnt;
+    if (v < 0.0) v = 0.0;
+    const float m_f = (float)(K + d), v_f = (float)v;
+    mean[c] = m_f;
+    var[c] = v_f;
+    if (running_mean != nullptr) running_mean[c] = running_mean[c] * (1.f - momentum) + momentum * m_f;
+    if (running_var != nullptr) running_var[c] = running_var[c] * (1.f - momentum) + momentum * unbiased_of(v_f, (float)rows);
+  }
+}
+
 constexpr int kStatsU = 8, kGrad0U = 8, kGrad1U = 4;
 
 #define SKD_RED_DISPATCH(U_, KERNEL_EXPR)                   \
@@ -483,6 +546,16 @@ int skd_abn_stats_nhwc(int64_t rows, int C, const float *x, float *mean, float *
   NhwcGeom g;
   if (!make_nhwc_geom(rows, C, g) || !x || !mean || !var || !workspace || !aligned16(x)) return 0;
   return launch_stats_nhwc2(rows, C, x, mean, var, nullptr, nullptr, 0.f, workspace, as_stream(stream));
+}
+
+// include/skd_bnstats.h: mean / biased var (+ running update) from the records a convolution's epilogue wrote
+int skd_abn_stats_from_partials_nhwc(int64_t rows, int C, const float *stats, int64_t stats_floats, float *mean, float *var,
+                                     float *running_mean, float *running_var, float momentum, skd_stream_t stream) {
+  if (rows < 1 || rows > (int64_t)1 << 40 || C < 16 || C % 16 != 0 || !stats || !mean || !var) return 0;
+  if ((reinterpret_cast<uintptr_t>(stats) & 7) || stats_floats < cdiv(rows, 32) * C * 2) return 0;
+  abn_stats_from_partials_kernel<<<dim3((unsigned)(C / kFinCh)), dim3(kFinThreads), 0, as_stream(stream)>>>(
+      stats, mean, var, running_mean, running_var, rows, C, momentum);
+  return ok();
 }
 
 int skd_abn_apply_nhwc_to(int64_t rows, int C, const float *x, const float *residual, float *out,

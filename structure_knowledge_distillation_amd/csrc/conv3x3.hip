@@ -27,6 +27,8 @@
 // Epilogue (store_block): out = act( ((acc + conv_bias - mean) * invstd) * (|weight| + eps) + bias [+ residual] ), every term
 // optional: the identity (raw convolution output: the PSP bottleneck's `feats` half, the bottleneck blocks' conv2), conv bias +
 // eval-mode InPlace-ABN + leaky ReLU (the deep-supervision head), eval-mode BN + ReLU, BN + residual + ReLU (a BasicBlock's tail).
+// STATS (include/skd_bnstats.h; the raw epilogue of the training forward alone): behind its stores a block also writes the
+// batch-norm statistics record of what it stored (block_stats); STATS = false is the code without it.
 //
 // Grid: XCD-aware panel-major order as in conv1x1.hip -- row panel p lives on XCD p % 8, its column tiles run back to back --
 // so the workgroups resident on an XCD together started together and walk the same K-tiles of the same (at most Cout / TN)
@@ -38,6 +40,7 @@
 // registers each and 42 KB of LDS (a stage is the 768 chunks of A and the 384 of B; k_loop places its second stage kStageChunks
 // behind the first) admit three workgroups per CU.
 #include "conv_split_dev.hpp"
+#include "skd_bnstats.h"
 #include "skd_infer.h"
 #include "skd_narrow.h"
 #include "skd_split2.h"
@@ -139,11 +142,42 @@ struct Tile3 {
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES>(stage, low, acc); }
 };
 
+// STATS (include/skd_bnstats.h): the batch-norm statistics record of one 32 x 32 accumulator block, from the fp32 values
+// store_block has just stored (ACT = none, no BN terms: the stored value IS acc[q]).  Column `col` of the block lives in lanes l and
+// l ^ 32, sixteen rows each (store_block's row map), so a record is an in-lane sum, one exchange with the other half, the
+// block's own mean, the in-lane sum of the squared deviations about it and a second exchange: two passes, no pivot, no LDS, no
+// barrier, no atomics.  Rows >= M are left out; the count min(32, M - row0) is implied by (M, block) and never stored.  The
+// additions are written as one chain per lane and a + b of the two halves (commutative: both halves hold the same bits), the
+// multiply-adds as explicit fmaf, so every tile form runs the same operations on the same values in the same order: the record
+// of (block, channel) is a function of Y alone.  Record (mean, M2) at stats[(block * N + col) * 2], block = row0 / 32 -- row0 is a
+// multiple of 32 in every tile form (m0 of 64, the wave offset of 32) -- written by the lower half as 32 consecutive float2.
+__device__ __forceinline__ void block_stats(const f32x16 &acc, float *__restrict__ stats, int64_t row0, int col, int64_t M, int N) {
+  if (row0 >= M) return;                                   // a block beyond the last row has no record (wave-uniform)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t left = M - row0;                           // rows of this block that exist, if < 32
+  const float cnt = left < 32 ? (float)left : 32.f;
+  bool live[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) live[q] = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5) < left;
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) s += live[q] ? acc[q] : 0.f;
+  const float mean = (s + __shfl_xor(s, 32, kWave)) / cnt;
+  float m2 = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const float d = live[q] ? acc[q] - mean : 0.f;
+    m2 = __builtin_fmaf(d, d, m2);
+  }
+  m2 += __shfl_xor(m2, 32, kWave);
+  if (lane < 32) *reinterpret_cast<float2 *>(stats + ((row0 >> 5) * N + col) * 2) = make_float2(mean, m2);
+}
+
 // One output tile of TM x TN pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
 // in front of the activation (store_block): the second convolution of a BasicBlock.
-template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3>
+template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
-                                             const float *__restrict__ R,
+                                             const float *__restrict__ R, float *__restrict__ stats,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
                                              const float *__restrict__ var, const float *__restrict__ weight,
                                              const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W,
@@ -212,6 +246,7 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
         store_block<ACT, HAS_RES, true, false>(acc[bi][bj], R, Y, row0, col, M, N, mu, is, ga, be, slope);
       else
         store_block<ACT, HAS_RES, false, false>(acc[bi][bj], R, Y, row0, col, M, N, mu, is, ga, be, slope);
+      if constexpr (STATS) block_stats(acc[bi][bj], stats, row0, col, M, N);
     }
   }
 }
@@ -227,15 +262,16 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kMinWG; }
 
 // PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h).
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
     const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y, const float *__restrict__ cbias,
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
     const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil, int tiles_n,
-    int p_full, const float *__restrict__ R) {
+    int p_full, const float *__restrict__ R, float *__restrict__ stats) {
   static_assert(TALL || TN == kTN, "64-row panels exist for the 128-column form only");
+  static_assert(!STATS || (ACT == SKD_ACT_NONE && !HAS_RES && PIECES == 3), "statistics: the training forward's raw epilogue alone");
   static_assert(PIECES == 3 || (TN == kTN && !HAS_RES), "two pieces: the 128-column forward family without the residual");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -244,11 +280,11 @@ void conv3x3_split_kernel(
   if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -290,15 +326,15 @@ __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
   for (int p = 0; p < PIECES; ++p) pack[(tile * PIECES + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
-                   int geometry, hipStream_t st) {
+                   int geometry, hipStream_t st, float *stats = nullptr) {
   static PerDeviceFlag ready;          // per instantiation AND per device
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN, PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
@@ -314,8 +350,8 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
-      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R);
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
+      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R, stats);
   return ok();
 }
 
@@ -325,17 +361,17 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
 // TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
-template <int TN, int ACT, bool HAS_RES, int PIECES = 3>
+template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
-                    int geometry, hipStream_t st) {
+                    int geometry, hipStream_t st, float *stats = nullptr) {
   if constexpr (TN < kTN) {
-    return launch3<TN, ACT, true, HAS_RES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, 1, st);
+    return launch3<TN, ACT, true, HAS_RES, 3, STATS>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, 1, st, stats);
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
-      return launch3<TN, ACT, true, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
-    return launch3<TN, ACT, false, HAS_RES, PIECES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st);
+      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
   }
 }
 
@@ -400,7 +436,8 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
   case ACT:                                                                                                                   \
     if constexpr (PIECES == 3)                                                                                                \
       return (residual != nullptr ? launch3g<TN, ACT, true> : launch3g<TN, ACT, false>)(                                     \
-          x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st);   \
+          x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st,    \
+          nullptr);                                                                                                           \
     else                                                                                                                      \
       return residual != nullptr ? 0 : launch3g<TN, ACT, false, PIECES>(                                                      \
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
@@ -411,6 +448,30 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
     default: return 0;
   }
 #undef SKD_CONV3X3_CASE
+}
+
+// include/skd_bnstats.h: floats of the statistics workspace of an (M, Cout) output -- one (mean, M2) per 32-row block and
+// channel -- or 0 for sizes no entry takes.
+static int64_t bnstats_floats(int64_t M, int Cout) {
+  if (M < 1 || Cout < 1 || Cout % kNarrowTN != 0 || M > (int64_t)1 << 40) return 0;
+  return cdiv(M, (int64_t)32) * Cout * 2;
+}
+
+// out = conv3x3(x) + conv_bias, raw (the training forward: no BN terms, no activation, no residual), and the statistics records
+// of `out`.  Everything run3 refuses is refused; so are a NULL or misaligned (8 bytes: the records are float2) or short `stats`.
+template <int TN>
+static int run3_stats(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                      const float *conv_bias, int geometry, int max_geometry, float *stats, int64_t stats_floats,
+                      skd_stream_t stream) {
+  if (!supported3<TN>(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
+  if (!x || !wpack || !out || geometry < 0 || geometry > max_geometry) return 0;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack)) & 15) return 0;
+  if ((int64_t)H * W > 2147483647 || dilation > (1 << 24)) return 0;
+  const int64_t M = (int64_t)B * H * W, need = bnstats_floats(M, Cout);
+  if (!stats || (reinterpret_cast<uintptr_t>(stats) & 7) || need == 0 || stats_floats < need) return 0;
+  return launch3g<TN, SKD_ACT_NONE, false, 3, true>(x, static_cast<const uint4 *>(wpack), out, nullptr, conv_bias, nullptr, nullptr,
+                                                    nullptr, nullptr, 0.f, 0.f, M, H, W, Cin, Cout, dilation, geometry,
+                                                    as_stream(stream), stats);
 }
 
 }  // namespace
@@ -492,6 +553,21 @@ int skd_conv3x3_narrow_nhwc(int B, int H, int W, int Cin, int Cout, int dilation
                             skd_stream_t stream) {
   return run3<kNarrowTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation,
                          slope, geometry, 1, stream);
+}
+
+// include/skd_bnstats.h: the training forward with the batch-norm statistics records from its epilogue (the finalize kernel
+// that reads them: csrc/abn_nhwc.hip).
+int64_t skd_conv3x3_bnstats_floats(int64_t M, int Cout) { return bnstats_floats(M, Cout); }
+
+int skd_conv3x3_split_stats_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                                 const float *conv_bias, int geometry, float *stats, int64_t stats_floats, skd_stream_t stream) {
+  return run3_stats<kTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, conv_bias, geometry, 3, stats, stats_floats, stream);
+}
+
+int skd_conv3x3_narrow_stats_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack,
+                                  float *out, const float *conv_bias, int geometry, float *stats, int64_t stats_floats,
+                                  skd_stream_t stream) {
+  return run3_stats<kNarrowTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, conv_bias, geometry, 1, stats, stats_floats, stream);
 }
 
 }  // extern "C"

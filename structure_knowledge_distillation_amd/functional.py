@@ -960,6 +960,35 @@ def _conv3x3_narrow_launch(x, pack, cout, dilation, conv_bias=None):
     return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias)
 
 
+# include/skd_bnstats.h: the training forward that also emits the batch-norm statistics records of its output, and their finalize
+_BNSTATS_ENTRIES = ("skd_conv3x3_bnstats_floats", "skd_conv3x3_split_stats_nhwc", "skd_conv3x3_narrow_stats_nhwc",
+                    "skd_abn_stats_from_partials_nhwc")
+
+
+def conv3x3_bnstats_supported():
+    """True when the back-end has the four entries of include/skd_bnstats.h (the tests' C double does not: conv3x3_split_train is
+    then not asked for statistics and the ABN forward behind it runs what it ran before)."""
+    return all(_lib.has_entry(n) for n in _BNSTATS_ENTRIES)
+
+
+def _conv3x3_stats_launch(narrow, x, pack, cout, dilation, conv_bias=None):
+    """``(conv3x3(x) + conv_bias, partials)``: _conv3x3_split_launch / _conv3x3_narrow_launch by the entry of include/skd_bnstats.h
+    that writes the same bits and, from its epilogue, one (mean, M2) per 32-row block and channel of the output into ``partials``
+    (fp32, skd_conv3x3_bnstats_floats long, every element written)."""
+    lib = _lib.get()
+    entry = "skd_conv3x3_narrow_stats_nhwc" if narrow else "skd_conv3x3_split_stats_nhwc"
+    b, cin, h, w = x.shape
+    if pack.numel() != (lib.skd_conv3x3_narrow_pack_bytes if narrow else lib.skd_conv3x3_split_pack_bytes)(cin, cout):
+        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
+    _lib.require_device(x, pack, conv_bias)
+    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    n = int(lib.skd_conv3x3_bnstats_floats(b * h * w, cout))
+    partials = torch.empty((max(n, 1),), dtype=torch.float32, device=x.device)
+    _lib.check(getattr(lib, entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                   _lib.ptr(conv_bias), 0, partials.data_ptr(), n, _lib.stream_of(x)), entry)
+    return out, partials
+
+
 def conv3x3_narrow_supported(x, conv, residual=False):
     """True when the 64-column form of the split-core 3x3 convolution (csrc/conv3x3.hip, include/skd_narrow.h) takes
     ``conv(x)`` of a frozen forward: no grad, a back-end that has the four entries (the tests' C double does not: callers then run
@@ -1115,7 +1144,9 @@ class _Conv3x3SplitTrain(Function):
     ``pack_bwd`` THIS forward was given (kept in ctx: an optimizer step in between changes the cache, not this node).  The
     weight gradient (and the bias gradient) are the library's, as before -- with ``wgrad`` the weight gradient is
     conv3x3_split_wgrad's where the back-end has its entries, and the library computes the bias gradient alone; ``"narrow"`` in
-    its place (conv3x3_split_train's ``narrow_wgrad``) asks for conv3x3_narrow_wgrad's in the same way."""
+    its place (conv3x3_split_train's ``narrow_wgrad``) asks for conv3x3_narrow_wgrad's in the same way.  A fourth optional argument
+    (conv3x3_split_train's ``stats``) makes the forward return ``(y, partials)`` -- the same ``y`` and the statistics records of
+    include/skd_bnstats.h, marked non-differentiable; the backward is the same."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, *wgrad):
@@ -1126,13 +1157,17 @@ class _Conv3x3SplitTrain(Function):
         ctx.narrow_wgrad = bool(wgrad) and wgrad[0] == "narrow"
         # (forward?, backward?) on the narrow entry: the third optional argument (conv3x3_split_train's ``narrow``)
         fwd_narrow, ctx.bwd_narrow = wgrad[1] if len(wgrad) > 1 else (False, False)
+        if len(wgrad) > 2 and wgrad[2]:
+            y, partials = _conv3x3_stats_launch(fwd_narrow, x, pack_fwd, int(weight.shape[0]), dilation, bias)
+            ctx.mark_non_differentiable(partials)
+            return y, partials
         if fwd_narrow:
             return _conv3x3_narrow_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
         return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g):
+    def backward(ctx, g, *_partials_grad):
         x, weight = ctx.saved_tensors         # a weight written since the forward raises autograd's version error here
         d = ctx.dilation
         g = _cl(g.to(torch.float32))
@@ -1152,7 +1187,7 @@ class _Conv3x3SplitTrain(Function):
         return (dx, dw, db) + (None,) * (ctx.n_inputs - 3)
 
 
-def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False):
+def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False):
     """``F.conv2d(x, weight, bias, 1, dilation, dilation)`` for a call conv3x3_train_supported accepted, differentiable: forward
     and data gradient are one launch each of the split-core implicit GEMM (csrc/conv3x3.hip: fp32 in and out, three bf16 pieces,
     six products, fp32 accumulation; the numerics of conv3x3_split_eval in both directions), the weight and bias gradients come
@@ -1163,13 +1198,23 @@ def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=Fal
     Cin for the data gradient: the 128-column tiles for a multiple of 128, the 64-column ones otherwise -- which takes one pack
     launch per entry and weight version; the weight gradient of a shape with a 64-channel side stays with the library (``wgrad``
     is ignored for it) unless ``narrow_wgrad=True`` (a further opt-in, effective only with ``narrow``): then it is
-    conv3x3_narrow_wgrad's where the back-end has the entries of include/skd_narrow_wgrad.h, the bias gradient the library's."""
+    conv3x3_narrow_wgrad's where the back-end has the entries of include/skd_narrow_wgrad.h, the bias gradient the library's.
+    ``stats=True`` (opt-in; conv3x3_bnstats_supported says when, a back-end without the entries raises): returns
+    ``(y, partials)`` -- ``y`` bit for bit what the call returns without it, and ``partials``, the batch-norm statistics records the
+    forward's epilogue wrote (include/skd_bnstats.h: one (mean, M2) per 32-row block of B * H * W and output channel), not
+    differentiable, for ``abn_relu_train(y, ..., partials=partials)``.  The backward, and ``wgrad`` / ``narrow`` /
+    ``narrow_wgrad``, are what they are without it."""
+    if stats and not conv3x3_bnstats_supported():
+        raise NotImplementedError("this back-end has no include/skd_bnstats.h entries")
     if narrow:
         pack_fwd, pack_bwd, fwd_narrow, bwd_narrow = _conv3x3_narrow_train_packs(weight, owner)
         if fwd_narrow or bwd_narrow:
+            tail = (True,) if stats else ()
             return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, "narrow" if narrow_wgrad else False,
-                                            (fwd_narrow, bwd_narrow))
+                                            (fwd_narrow, bwd_narrow), *tail)
     pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
+    if stats:
+        return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), True)
     if wgrad:
         return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, True)
     return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd)

@@ -410,10 +410,14 @@ class _ABNRelu(autograd.Function):
     ``out + residual`` in between (networks/pspnet_combine.py:36-43, 68-82) -- keeping z and relu(z) alive.  Here the
     convolution output x is kept instead of z (y is recomputed from x, mean, var in backward) and ``out`` is the
     ReLU output, so the same two tensors per layer live on while the separate ReLU / add passes disappear.
-    Works on NCHW and on channels-last tensors; cross-replica statistics exactly as in _InPlaceABN."""
+    Works on NCHW and on channels-last tensors; cross-replica statistics exactly as in _InPlaceABN.
+    ``partials``: the statistics records the convolution that produced ``x`` wrote from its epilogue
+    (functional.conv3x3_split_train(..., stats=True), include/skd_bnstats.h).  A call that is not replicated then finishes them
+    (skd_abn_stats_from_partials_nhwc: mean, var, running update) and applies -- two launches, none of which reduces ``x``; a
+    replicated call ignores them.  What is saved for backward is the same either way."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, residual, momentum, eps, group):
+    def forward(ctx, x, weight, bias, running_mean, running_var, residual, momentum, eps, group, partials=None):
         _lib.require_device(x, weight, bias, running_mean, running_var, residual)
         if x.dtype != torch.float32:
             raise TypeError("InPlaceABN kernels are fp32 only (got %s)" % x.dtype)
@@ -432,9 +436,17 @@ class _ABNRelu(autograd.Function):
             raise RuntimeError("abn_relu: misaligned output allocation")
         stat = x.new_empty((2, c))
         mean, var = stat[0], stat[1]
-        ws = geo.workspace(lib, x)
         relu = _EVAL_ACT_CODE[ACT_RELU]
-        if ctx.group is None:
+        ws = geo.workspace(lib, x) if (partials is None or ctx.group is not None) else None
+        if ws is None:           # the convolution's epilogue has reduced x already: finish its records, then a pure streaming apply
+            if not geo.nhwc:
+                raise ValueError("abn_relu: statistics partials come with a channels-last convolution output")
+            _lib.require_device(partials)
+            _lib.check(lib.skd_abn_stats_from_partials_nhwc(geo.rows, c, partials.data_ptr(), partials.numel(), mean.data_ptr(),
+                                                            var.data_ptr(), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                                            float(momentum), st), "skd_abn_stats_from_partials_nhwc")
+            geo.apply_to(lib, x, residual, out, mean, var, weight, bias, ctx.eps, relu, 0.0, st)
+        elif ctx.group is None:
             geo.forward_train(lib, x, residual, out, weight, bias, running_mean, running_var, mean, var, float(momentum),
                               ctx.eps, relu, 0.0, ws, st)
         else:
@@ -484,7 +496,7 @@ class _ABNRelu(autograd.Function):
                                                       eydz.data_ptr(), dx.data_ptr(), _lib.ptr(dres), _lib.ptr(dweight),
                                                       _lib.ptr(dbias), ctx.eps, 0, ws.data_ptr(), st),
                        "skd_abn_relu_backward_nhwc")
-            return (dx if need_dx else None), dweight, dbias, None, None, dres, None, None, None
+            return (dx if need_dx else None), dweight, dbias, None, None, dres, None, None, None, None
         mb = _mailbox_for(geo, ctx.group, x) if ctx.group is not None else None
         if mb is not None:
             from ..utils.parallel import comm_timer
@@ -494,12 +506,12 @@ class _ABNRelu(autograd.Function):
                 _lib.ptr(bias), edz.data_ptr(), eydz.data_ptr(), dx.data_ptr(), _lib.ptr(dres), _lib.ptr(dweight), _lib.ptr(dbias),
                 _lib.ptr(_replica_weights(ctx.group)), ctx.eps, 0, ws.data_ptr(), st), "skd_abn_relu_backward_nhwc_sync")
             comm_timer.end(tok)
-            return (dx if need_dx else None), dweight, dbias, None, None, dres, None, None, None
+            return (dx if need_dx else None), dweight, dbias, None, None, dres, None, None, None, None
         geo.relu_backward_reduce(lib, x, out, dout, mean, var, edz, eydz, ctx.eps, ws, st, weight=weight, bias=bias)
         if ctx.group is not None:
             _sync_grad_stats(stat, ctx.group)
         geo.relu_backward_dx(lib, x, out, dout, mean, var, weight, edz, eydz, dx, dres, dweight, dbias, ctx.eps, st, bias=bias)
-        return (dx if need_dx else None), dweight, dbias, None, None, dres, None, None, None
+        return (dx if need_dx else None), dweight, dbias, None, None, dres, None, None, None, None
 
 
 def _nhwc_unsupported(x):
@@ -535,16 +547,29 @@ def _via_nchw(fn, x, *rest, residual=None, inplace=False):
     return out.contiguous(memory_format=torch.channels_last)
 
 
+def abn_relu_replicated(group=None, sync=True):
+    """Whether abn_relu_train(..., group=group, sync=sync) would synchronise its statistics over more than this replica -- the
+    calls that ignore ``partials``, so that their convolution need not be asked for statistics."""
+    if not sync:
+        return False
+    return _replicated(_default_group() if group is None else group)
+
+
 def abn_relu_train(x, weight, bias, running_mean, running_var, residual=None, momentum=0.1, eps=1e-05, group=None,
-                   sync=True):
+                   sync=True, partials=None):
     """relu(bn_batch(x) [+ residual]) with running-statistics update: the training-time fusion of
     InPlace-ABN(activation='none') -> [+ residual] -> ReLU.  Differentiable (first order) w.r.t. x, weight,
     bias and residual.  ``sync``: synchronise the statistics over ``group`` (default group when None and
-    torch.distributed is initialised) like InPlaceABNSync; False = this replica only (InPlaceABN)."""
+    torch.distributed is initialised) like InPlaceABNSync; False = this replica only (InPlaceABN).
+    ``partials``: the statistics records of ``x`` from the epilogue of the convolution that wrote it
+    (functional.conv3x3_split_train(..., stats=True)); a call that is not replicated takes mean and var from them instead of
+    reducing ``x`` (see _ABNRelu), a replicated one ignores them."""
     if not sync:
         group = None
     elif group is None:
         group = _default_group()
+    if partials is not None and not _nhwc_unsupported(x):
+        return _ABNRelu.apply(x, weight, bias, running_mean, running_var, residual, momentum, eps, group, partials)
     if _nhwc_unsupported(x):
         return _via_nchw(lambda xc, r=None: _ABNRelu.apply(xc, weight, bias, running_mean, running_var, r, momentum, eps, group),
                          x, residual=residual)

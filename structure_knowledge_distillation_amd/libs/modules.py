@@ -6,8 +6,8 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
-from .inplace_abn import (abn_eval_fused, abn_relu_maxpool_supported, abn_relu_maxpool_train, abn_relu_train, inplace_abn,
-                          inplace_abn_sync)
+from .inplace_abn import (abn_eval_fused, abn_relu_maxpool_supported, abn_relu_maxpool_train, abn_relu_replicated, abn_relu_train,
+                          inplace_abn, inplace_abn_sync)
 
 _sync_group = {"group": None, "explicit": False}
 
@@ -63,15 +63,28 @@ class _ABNBase(nn.Module):
         return abn_eval_fused(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
                               activation, self.slope, residual)
 
-    def forward_relu(self, x, residual=None):
+    def takes_partials(self):
+        """Whether ``forward_relu(x, partials=...)`` would use the statistics records of the convolution in front of it: a
+        training-mode ``activation='none'`` module whose call is not replicated (a replicated call ignores them)."""
+        if self.activation != "none" or not self.training:
+            return False
+        sync = isinstance(self, InPlaceABNSync)
+        group = _sync_group["group"] if (sync and _sync_group["explicit"]) else None
+        return not abn_relu_replicated(group, sync)
+
+    def forward_relu(self, x, residual=None, partials=None):
         """``relu(self(x) [+ residual])`` for an ``activation='none'`` module -- BatchNorm2d followed by nn.ReLU in
         networks/pspnet_combine.py -- as one fused op: training -> abn_relu_train, inference (no grad) ->
-        abn_eval_fused, anything else -> the plain op sequence."""
+        abn_eval_fused, anything else -> the plain op sequence.  ``partials``: the statistics records of ``x`` from the epilogue
+        of the convolution that wrote it (abn_relu_train); used in training alone."""
         if self.activation != "none":
             raise ValueError("forward_relu fuses BN(activation='none') + ReLU; this module has activation=%r" % self.activation)
         if self.training:
             sync = isinstance(self, InPlaceABNSync)
             group = _sync_group["group"] if (sync and _sync_group["explicit"]) else None
+            if partials is not None:
+                return abn_relu_train(x, self.weight, self.bias, self.running_mean, self.running_var, residual,
+                                      self.momentum, self.eps, group, sync=sync, partials=partials)
             return abn_relu_train(x, self.weight, self.bias, self.running_mean, self.running_var, residual,
                                   self.momentum, self.eps, group, sync=sync)
         if not torch.is_grad_enabled():

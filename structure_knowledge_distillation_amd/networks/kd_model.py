@@ -216,8 +216,19 @@ class NetModel():
         if split_shortcut is None:
             split_shortcut = os.environ.get("SKD_SPLIT_SHORTCUT", "0") == "1"
         self.split_shortcut = bool(split_shortcut) and self.split_train
+        # args.split_bnstats (None: SKD_SPLIT_BNSTATS, default "0"): with split_train, the routed 3x3 convolutions of the student's
+        # BasicBlocks emit the batch-norm statistics of their output from the epilogue and the ABN forward behind them finishes
+        # those and applies (csrc/conv3x3.hip's STATS form, include/skd_bnstats.h); without split_train it routes nothing.  Single
+        # replica only: a synchronised normalisation ignores it.  Off by default
+        # (profiles/r26_conv3x3_bnstats_isolated.md, profiles/r26_step_ab.md).
+        split_bnstats = getattr(args, "split_bnstats", None)
+        if split_bnstats is None:
+            split_bnstats = os.environ.get("SKD_SPLIT_BNSTATS", "0") == "1"
+        self.split_bnstats = bool(split_bnstats) and self.split_train
         if self.split_train:
             extra = dict(narrow=True) if self.split_narrow else {}
+            if self.split_bnstats:
+                extra["bnstats"] = True
             if self.split_shortcut:
                 extra["shortcut"] = True
             if self.split_narrow_wgrad:
@@ -895,7 +906,8 @@ def default_args(**overrides):
         S_resume=True, S_ckpt_path=None, D_resume=True, D_ckpt_path=None, last_step=0, start_epoch=0,
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
-        split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None)
+        split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
+        split_bnstats=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
@@ -908,5 +920,7 @@ def default_args(**overrides):
         a.split_narrow_wgrad = os.environ.get("SKD_SPLIT_NARROW_WGRAD", "0") == "1"
     if a.split_shortcut is None:       # effective only together with split_train
         a.split_shortcut = os.environ.get("SKD_SPLIT_SHORTCUT", "0") == "1"
+    if a.split_bnstats is None:        # effective only together with split_train
+        a.split_bnstats = os.environ.get("SKD_SPLIT_BNSTATS", "0") == "1"
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     return a

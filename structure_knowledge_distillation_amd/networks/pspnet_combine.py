@@ -114,6 +114,19 @@ SHORTCUT_ROUTING_EXCLUDED = frozenset({(128, 64, 1, "wgrad"), (64, 128, 2, "wgra
 # than the spread is listed here as ("1x1", K, N) or ("3x3", Cin, Cout, dilation) and keeps three pieces
 # (profiles/r25_split2_isolated.md has every shape).
 SPLIT2_ROUTING_EXCLUDED = frozenset()
+# Batch-norm statistics from the routed convolution's epilogue (route_training_convs(bnstats=True); a seventh opt-in, on top of
+# the training form): a BasicBlock's conv1 / conv2 that the training form routes -- the 11 wide convolutions of layer2-4, and
+# with ``narrow`` layer1's four -- also writes one (mean, M2) per 32-row block and channel of its output (include/skd_bnstats.h),
+# and the forward_relu behind it finishes those records and applies instead of reducing the tensor once more.  A shape whose
+# {convolution with statistics + finalize + apply} does not measure ahead of {convolution + one-launch ABN forward} by more than
+# the spread is listed here as (Cin, Cout, dilation) and keeps the pair it had (profiles/r26_conv3x3_bnstats_isolated.md has every
+# shape).
+# Measured on the MI355X at batch 8: no shape is ahead -- 128 -> 128 is within the spread, the others are 0.6 - 6 % behind (back to
+# back the one-launch ABN forward finds the convolution's output in the caches and costs what finalize + apply cost) -- so all seven
+# shapes of the step are listed, and the opt-in routes nothing until a form measures ahead.  The step with the set emptied:
+# +0.14 / +0.16 ms at the median, ranges overlapping (profiles/r26_step_ab.md).
+BNSTATS_ROUTING_EXCLUDED = frozenset({(128, 128, 1), (128, 256, 2), (256, 256, 2), (256, 512, 4), (512, 512, 4), (128, 64, 1),
+                                      (64, 64, 1)})
 _SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
                    "skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn2_pro_nhwc")
 
@@ -170,8 +183,30 @@ def _wgrad_routed(module, cin, cout, dilation):
     return bool(getattr(module, "_skd_train_wgrad", False)) and (cin, cout, dilation) not in WGRAD_ROUTING_EXCLUDED
 
 
-def _train_conv(module, conv, x):
-    """``conv(x)``: on the split core in both directions where _train_routed says so, the module's own forward otherwise."""
+def _bnstats_routed(module, conv, bn):
+    """Whether a convolution the flagged ``module`` routes is asked for the statistics records of its output as well: the
+    module carries the flag (route_training_convs(bnstats=True)), the shape is not in BNSTATS_ROUTING_EXCLUDED, the back-end has
+    the entries of include/skd_bnstats.h and ``bn``, the normalisation behind the convolution, would use them (a training-mode
+    ``activation='none'`` ABN whose call is not replicated)."""
+    return (bn is not None and bool(getattr(module, "_skd_train_bnstats", False))
+            and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in BNSTATS_ROUTING_EXCLUDED
+            and SF.conv3x3_bnstats_supported() and callable(getattr(bn, "takes_partials", None)) and bn.takes_partials())
+
+
+def _train_conv(module, conv, x, bn=None):
+    """``conv(x)``: on the split core in both directions where _train_routed says so, the module's own forward otherwise.
+    With ``bn`` (the ABN whose forward_relu follows, BasicBlock): the pair ``(conv(x), partials)`` -- ``partials`` the statistics
+    records of the routed convolution's epilogue where _bnstats_routed says so, None otherwise."""
+    if bn is not None:
+        if _bnstats_routed(module, conv, bn):
+            d, cin, cout = conv.dilation[0], conv.in_channels, conv.out_channels
+            if _train_routed(module, x, conv):
+                return SF.conv3x3_split_train(x, conv.weight, d, conv.bias, owner=conv, wgrad=_wgrad_routed(module, cin, cout, d),
+                                              stats=True)
+            if _narrow_train_routed(module, x, conv):
+                nw = getattr(module, "_skd_train_narrow_wgrad", False) and (cin, cout, d) not in NARROW_WGRAD_ROUTING_EXCLUDED
+                return SF.conv3x3_split_train(x, conv.weight, d, conv.bias, owner=conv, narrow=True, narrow_wgrad=bool(nw), stats=True)
+        return _train_conv(module, conv, x), None
     if _train_routed(module, x, conv):
         if _wgrad_routed(module, conv.in_channels, conv.out_channels, conv.dilation[0]):
             return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=True)
@@ -345,9 +380,16 @@ class BasicBlock(nn.Module):
         if self._infer_form(x):
             return self._forward_infer(x)
         if _fused(self, x):
-            out = self.bn1.forward_relu(_train_conv(self, self.conv1, x))
+            if not getattr(self, "_skd_train_bnstats", False):
+                out = self.bn1.forward_relu(_train_conv(self, self.conv1, x))
+                residual = _shortcut(self, x) if self.downsample is not None else x
+                return self.bn2.forward_relu(_train_conv(self, self.conv2, out), residual)
+            # flagged (route_training_convs(bnstats=True)): a routed convolution hands the statistics of its output on
+            y, partials = _train_conv(self, self.conv1, x, self.bn1)
+            out = self.bn1.forward_relu(y, partials=partials)
             residual = _shortcut(self, x) if self.downsample is not None else x
-            return self.bn2.forward_relu(_train_conv(self, self.conv2, out), residual)
+            y, partials = _train_conv(self, self.conv2, out, self.bn2)
+            return self.bn2.forward_relu(y, residual, partials=partials)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         residual = _shortcut(self, x) if self.downsample is not None else x
@@ -691,7 +733,7 @@ def set_teacher_pieces(model, pieces=2):
 
 
 def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False, narrow=False, narrow_wgrad=False,
-                         shortcut=False):
+                         shortcut=False, bnstats=False):
     """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
 
     A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
@@ -716,6 +758,11 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     ABN) run forward, data gradient and weight gradient on the split core as well (SF.conv1x1_split_train, include/skd_shortcut.h)
     except for the (Cin, Cout, stride, product) of SHORTCUT_ROUTING_EXCLUDED; on a back-end without the entries they stay with the
     library.  It does not depend on the other three.
+    ``bnstats=True``: a BasicBlock's routed conv1 / conv2 (the 11 wide ones of layer2-4; with ``narrow`` layer1's four) also emits
+    the batch-norm statistics of its output from the epilogue (SF.conv3x3_split_train(..., stats=True), include/skd_bnstats.h) and
+    the forward_relu behind it finishes them and applies, except for the shapes of BNSTATS_ROUTING_EXCLUDED; replicated
+    (synchronised) normalisations, dsn[0], the stem, the PSP bottleneck and the shortcuts are what they were, and so are the
+    convolution's output bits and every backward.  On a back-end without the entries nothing changes.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
     for m in model.modules():
@@ -727,6 +774,7 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
         m._skd_train_narrow_wgrad = bool(narrow_wgrad and enable)
         if isinstance(m, BasicBlock):
             m._skd_train_shortcut = bool(shortcut and enable)
+            m._skd_train_bnstats = bool(bnstats and enable)
         if enable:
             continue
         if isinstance(m, BasicBlock) and isinstance(m.downsample, nn.Sequential) and len(m.downsample):

@@ -1,0 +1,337 @@
+"""-m gpu: batch-norm statistics from the epilogue of the split-core 3x3 convolution (include/skd_bnstats.h): the STATS form of
+csrc/conv3x3.hip's kernel behind skd_conv3x3_split_stats_nhwc / skd_conv3x3_narrow_stats_nhwc, the finalize
+skd_abn_stats_from_partials_nhwc, the op (functional.conv3x3_split_train(..., stats=True) -> abn_relu_train(..., partials=...)),
+a BasicBlock with the flag on and off, and one training step with the switch.
+
+Inputs are seeded by the case name as in tests/test_conv3x3_train_gpu.py.  Every buffer of an entry-level case sits between the
+guard bands of tests/bounds_cases.py; the statistics workspace has exactly the queried size, is never initialised (payload 0xFF =
+NaN) and every entry is called twice.  ``Y`` must equal the plain entry's bit for bit.  The finalized statistics are compared with
+float64 statistics of that ``Y`` at the project's bounds for its statistics kernels (tests/test_kernels_gpu.py: mean 2e-5, var
+5e-5, running_mean 2e-6, running_var 1e-5, each relative to max |want|).
+"""
+import copy
+import ctypes
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+import bnstats_ref as R
+import bounds_cases as BC
+import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
+from structure_knowledge_distillation_amd import _lib, functional as SF
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+P = BC.P
+MOMENTUM = 0.1
+
+# (name, B, Cin, Cout, H, W, dilation)
+CASES = [
+    ("ragged-13x11-128-d1", 2, 128, 128, 13, 11, 1),      # M = 286: eight full blocks and one of 30 rows
+    ("ragged-13x11-128-d2", 2, 128, 128, 13, 11, 2),
+    ("ragged-13x11-128-d4", 2, 128, 128, 13, 11, 4),
+    ("ragged-13x11-256-d1", 2, 128, 256, 13, 11, 1),
+    ("ragged-13x11-256-d2", 2, 128, 256, 13, 11, 2),
+    ("ragged-13x11-256-d4", 2, 128, 256, 13, 11, 4),
+    ("one-row-block-3x11", 1, 128, 128, 3, 11, 1),        # M = 33: a block of one row, count 1, M2 = 0
+    ("below-a-block-3x3", 1, 128, 128, 3, 3, 1),          # M = 9 < 32
+    ("narrow-64-64", 2, 64, 64, 13, 11, 1),               # TN = 64
+    ("narrow-64-128", 2, 64, 128, 13, 11, 2),             # ... and a Cout both entries take
+    ("many-tiles-226x226", 2, 16, 128, 226, 226, 1),      # 799 row tiles: geometry 3 has 128-row rounds and a 64-row tail
+]
+CASE = {c[0]: c for c in CASES}
+
+
+@pytest.fixture(scope="module")
+def hip():
+    return _lib.load()
+
+
+def inputs(name):
+    """Seeded channels-last input (B, H, W, Cin), He-scaled weight (Cout, Cin, 3, 3), running statistics."""
+    _, b, cin, cout, h, w, _ = CASE[name]
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    x = torch.randn(b, h, w, cin, generator=g)
+    wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
+    rm, rv = torch.randn(cout, generator=g), torch.rand(cout, generator=g) + 0.5
+    return x, wt, rm, rv
+
+
+def run(hip, name, narrow=False, geometry=0, bias=None, wt=None, plain=True):
+    """One case through the statistics entry (twice) and the finalize (twice), everything between guard bands.  Returns a dict
+    of CPU tensors: y, y_plain (the plain entry's output on the same buffers), mean, var, running_mean, running_var, records."""
+    _, b, cin, cout, h, w, d = CASE[name]
+    x, wt0, rm, rv = inputs(name)
+    wt = wt0 if wt is None else wt
+    m = b * h * w
+    A = BC.Arena(DEV)
+    xd, wd, bd = A.inp("x", x), A.inp("w", wt), A.inp("conv_bias", bias)
+    nbytes = cout * cin * 54
+    pack = A.ws("pack", nbytes // 4)              # (a workspace: written once, below, and left alone by reset())
+    sn, sc, sy, sx = wd.stride()
+    if narrow:
+        assert hip.skd_conv3x3_narrow_pack_bytes(cin, cout) == nbytes
+        assert hip.skd_conv3x3_narrow_pack_pair(cin, cout, P(wd), sn, sc, sy, sx, P(pack), nbytes, None, 0, None)
+    else:
+        assert hip.skd_conv3x3_split_pack_bytes(cin, cout) == nbytes
+        assert hip.skd_conv3x3_split_pack_pair(cin, cout, P(wd), sn, sc, sy, sx, P(pack), nbytes, None, 0, None)
+    n = hip.skd_conv3x3_bnstats_floats(m, cout)
+    assert n == R.workspace_floats(m, cout)
+    stats = A.ws("stats", n)
+    y, y_plain = A.out("y", (m, cout)), A.out("y_plain", (m, cout))
+    mean, var = A.out("mean", cout), A.out("var", cout)
+    rmd, rvd = A.io("running_mean", rm), A.io("running_var", rv)
+    entry = hip.skd_conv3x3_narrow_stats_nhwc if narrow else hip.skd_conv3x3_split_stats_nhwc
+    got = []
+    for _ in range(2):
+        A.reset()
+        assert entry(b, h, w, cin, cout, d, P(xd), P(pack), P(y), P(bd), geometry, P(stats), n, None)
+        assert hip.skd_abn_stats_from_partials_nhwc(m, cout, P(stats), n, P(mean), P(var), P(rmd), P(rvd), MOMENTUM, None)
+        A.check()
+        got.append(dict(y=y.cpu(), mean=mean.cpu(), var=var.cpu(), running_mean=rmd.cpu(), running_var=rvd.cpu(),
+                        records=stats.cpu().view(-1, cout, 2)))
+    for k in got[0]:
+        assert BC.same_bits(got[0][k], got[1][k]), "%s: %s differs between two calls" % (name, k)
+    out = got[0]
+    if plain:
+        if narrow:
+            assert hip.skd_conv3x3_narrow_nhwc(b, h, w, cin, cout, d, P(xd), P(pack), P(y_plain), None, P(bd), None, None, None, None,
+                                               0.0, 0, 0.01, geometry, None)
+        else:
+            assert hip.skd_conv3x3_split_nhwc(b, h, w, cin, cout, d, P(xd), P(pack), P(y_plain), P(bd), None, None, None, None, 0.0, 0,
+                                              0.01, geometry, None)
+        A.check()
+        out["y_plain"] = y_plain.cpu()
+        assert torch.equal(out["y"], out["y_plain"]), "%s: %d outputs differ from the plain entry's" % (
+            name, int((out["y"] != out["y_plain"]).sum()))
+    assert bool(torch.isfinite(out["records"]).all()), "every record is written"
+    out["rm0"], out["rv0"], out["rows"] = rm, rv, m
+    return out
+
+
+def check_stats(name, out, keys=("mean", "var", "running_mean", "running_var")):
+    want = dict(zip(("mean", "var", "running_mean", "running_var"),
+                    R.float64_stats(out["y"].numpy(), out["rm0"].numpy(), out["rv0"].numpy(), MOMENTUM)))
+    for k in keys:
+        err = R.rel_err(out[k].numpy(), want[k])
+        print("%s %s: rel err %.3e (bound %.1e)" % (name, k, err, R.BOUNDS[k]))
+        assert err <= R.BOUNDS[k], "%s %s: %.3e > %.1e" % (name, k, err, R.BOUNDS[k])
+
+
+# ---- 1. Y bits and the statistics against float64 -------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", [c[0] for c in CASES if not c[0].startswith(("narrow", "many"))])
+def test_wide_entry_vs_float64(hip, name):
+    out = run(hip, name)
+    check_stats(name, out)
+    # the records are the numpy restatement's, up to the rounding of the one fused multiply-add it does not model exactly
+    ref = R.block_records(out["y"].numpy())
+    assert np.array_equal(out["records"].numpy()[..., 0], ref[..., 0]), "block means: the same operations in the same order"
+    np.testing.assert_allclose(out["records"].numpy()[..., 1], ref[..., 1], rtol=1e-6, atol=0)
+    if name == "one-row-block-3x11":
+        assert bool((out["records"][1, :, 1] == 0).all()) and torch.equal(out["records"][1, :, 0], out["y"][32])
+
+
+@pytest.mark.parametrize("name", ["narrow-64-64", "narrow-64-128"])
+def test_narrow_entry_vs_float64(hip, name):
+    out = run(hip, name, narrow=True)
+    check_stats(name, out)
+    for geometry in (1,):
+        again = run(hip, name, narrow=True, geometry=geometry, plain=False)
+        assert BC.same_bits(again["records"], out["records"]) and BC.same_bits(again["mean"], out["mean"])
+
+
+def test_both_column_widths_give_the_same_bits_at_cout_128(hip):
+    wide, thin = run(hip, "narrow-64-128"), run(hip, "narrow-64-128", narrow=True)
+    assert torch.equal(wide["y"], thin["y"])
+    for k in ("records", "mean", "var", "running_mean", "running_var"):
+        assert BC.same_bits(wide[k], thin[k]), k
+
+
+def test_geometries_give_the_same_bits(hip):
+    """799 row tiles: under geometry 3 the launch has whole rounds of 128-row tiles and a tail of 64-row ones, under 1 all are 128
+    rows, under 2 all 64 -- the record layout and the bits are a function of the output alone."""
+    name = "many-tiles-226x226"
+    outs = [run(hip, name, geometry=g) for g in (1, 2, 3)]
+    check_stats(name, outs[0])
+    for o in outs[1:]:
+        assert torch.equal(o["y"], outs[0]["y"])
+        for k in ("records", "mean", "var", "running_mean", "running_var"):
+            assert BC.same_bits(o[k], outs[0][k]), k
+    small = [run(hip, "ragged-13x11-256-d2", geometry=g, plain=False) for g in (1, 2, 3)]
+    for o in small[1:]:
+        for k in ("y", "records", "mean", "var"):
+            assert BC.same_bits(o[k], small[0][k]), k
+
+
+# ---- 2. exactness and a large offset ---------------------------------------------------------------------------------------------
+
+def test_constant_channel_is_exact(hip):
+    for name, narrow in (("ragged-13x11-128-d2", False), ("one-row-block-3x11", False), ("narrow-64-64", True)):
+        x, wt, _, _ = inputs(name)
+        wt = wt.clone()
+        wt[5] = 0.0
+        bias = torch.randn(wt.shape[0], generator=torch.Generator().manual_seed(3))
+        bias[5] = 7.25
+        out = run(hip, name, narrow=narrow, bias=bias, wt=wt)
+        assert bool((out["y"][:, 5] == 7.25).all())
+        assert float(out["mean"][5]) == 7.25 and float(out["var"][5]) == 0.0, (name, float(out["mean"][5]), float(out["var"][5]))
+        check_stats(name, out)
+
+
+@pytest.mark.parametrize("name,narrow", [("ragged-13x11-128-d1", False), ("narrow-64-64", True), ("one-row-block-3x11", False)])
+def test_large_offset_keeps_the_variance(hip, name, narrow):
+    base = run(hip, name, narrow=narrow, plain=False)
+    sigma = float(base["y"].double().std())
+    bias = torch.full((CASE[name][3],), 1e3 * sigma)
+    out = run(hip, name, narrow=narrow, bias=bias)
+    assert float(out["y"].double().mean()) > 900 * sigma
+    check_stats(name, out, keys=("mean", "var"))
+
+
+# ---- 3. refusals ----------------------------------------------------------------------------------------------------------------
+
+def test_refusals_launch_nothing(hip):
+    b, cin, cout, h, w, d = 2, 128, 128, 13, 11, 1
+    m = b * h * w
+    A = BC.Arena(DEV)
+    x, pack = A.inp("x", torch.zeros(b, h, w, cin)), A.inp("pack", torch.zeros(cout * cin * 54, dtype=torch.uint8))
+    n = hip.skd_conv3x3_bnstats_floats(m, cout)
+    stats, y = A.out("stats", n), A.out("y", (m, cout))
+    mean, var = A.out("mean", cout), A.out("var", cout)
+    off = lambda t, k: ctypes.c_void_p(t.data_ptr() + k)
+    ok = dict(B=b, H=h, W=w, cin=cin, cout=cout, d=d, x=P(x), pk=P(pack), y=P(y), geo=0, st=P(stats), n=n)
+    bads = [dict(st=None), dict(st=off(stats, 4)), dict(n=n - 1), dict(n=0), dict(x=None), dict(pk=None), dict(y=None),
+            dict(x=off(x, 4)), dict(pk=off(pack, 8)), dict(B=0), dict(H=0), dict(W=-1), dict(cin=24), dict(cin=0), dict(cout=0),
+            dict(d=0), dict(geo=-1)]
+    for entry, more in ((hip.skd_conv3x3_split_stats_nhwc, [dict(cout=64), dict(cout=192), dict(geo=4)]),
+                        (hip.skd_conv3x3_narrow_stats_nhwc, [dict(cout=32), dict(cout=96), dict(geo=2)])):
+        for bad in bads + more:
+            v = dict(ok, **bad)
+            assert entry(v["B"], v["H"], v["W"], v["cin"], v["cout"], v["d"], v["x"], v["pk"], v["y"], None, v["geo"], v["st"],
+                         v["n"], None) == 0, bad
+    assert hip.skd_conv3x3_bnstats_floats(0, 128) == 0 and hip.skd_conv3x3_bnstats_floats(10, 32) == 0
+    assert hip.skd_conv3x3_bnstats_floats(10, 0) == 0 and hip.skd_conv3x3_bnstats_floats(-3, 64) == 0
+    ok = dict(rows=m, C=cout, st=P(stats), n=n, mean=P(mean), var=P(var))
+    for bad in (dict(rows=0), dict(rows=-1), dict(C=8), dict(C=24), dict(C=0), dict(st=None), dict(st=off(stats, 4)), dict(n=n - 1),
+                dict(mean=None), dict(var=None), dict(rows=m + 32)):
+        v = dict(ok, **bad)
+        assert hip.skd_abn_stats_from_partials_nhwc(v["rows"], v["C"], v["st"], v["n"], v["mean"], v["var"], None, None, MOMENTUM,
+                                                    None) == 0, bad
+    A.check()
+    for t in (stats, y, mean, var):
+        assert bool((t.view(torch.uint8) == BC.FILL).all()), "a refused call wrote"
+
+
+# ---- 4. the op and a BasicBlock -------------------------------------------------------------------------------------------------
+
+def _close(got, want, tol, what):
+    got, want = got.detach().cpu().double(), want.detach().cpu().double()
+    err = float((got - want).abs().max()) / max(float(want.abs().max()), 1e-30)
+    print("%s: rel err %.3e (bound %.1e)" % (what, err, tol))
+    assert err <= tol, "%s: %.3e > %.1e" % (what, err, tol)
+
+
+@pytest.mark.parametrize("planes,narrow", [(128, False), (64, True)], ids=["128-128", "64-64-narrow"])
+def test_basic_block_with_and_without_the_flag(monkeypatch, planes, narrow):
+    """A BasicBlock at B 2, 17 x 17, training, forward + backward, with the flag on and off: the tolerances of
+    test_abn_train_forward_backward for its quantities (z 3e-5, dx 1e-4, dweight / dbias 5e-5, running_mean 2e-6, running_var
+    1e-5, each relative to max |want|); the routed convolution's output with statistics equals the one without, bit for bit."""
+    assert SF.conv3x3_bnstats_supported()
+    monkeypatch.setattr(PC, "BNSTATS_ROUTING_EXCLUDED", frozenset())      # the mechanism, whatever the measured policy lists
+    torch.manual_seed(planes)
+    block = PC.BasicBlock(planes, planes).to(DEV).to(memory_format=torch.channels_last).train()
+    with torch.no_grad():
+        for bn in (block.bn1, block.bn2):
+            bn.weight.uniform_(0.5, 1.5)
+            bn.bias.normal_(0, 0.2)
+    g = torch.Generator().manual_seed(17)
+    x = torch.relu(torch.randn(2, planes, 17, 17, generator=g)).to(DEV).contiguous(memory_format=torch.channels_last)
+    go = torch.randn(2, planes, 17, 17, generator=g).to(DEV).contiguous(memory_format=torch.channels_last)
+    real = SF.conv3x3_split_train
+    seen = []
+
+    def op(x_, weight, dilation, bias=None, owner=None, **kw):
+        out = real(x_, weight, dilation, bias, owner, **kw)
+        if kw.get("stats"):
+            y, partials = out
+            plain = real(x_, weight, dilation, bias, owner, **{k: v for k, v in kw.items() if k != "stats"})
+            assert torch.equal(y.detach(), plain.detach()), "the routed convolution's output moved"
+            assert not partials.requires_grad and partials.numel() == R.workspace_floats(2 * 17 * 17, planes)
+            seen.append(tuple(weight.shape))
+        return out
+    monkeypatch.setattr(SF, "conv3x3_split_train", op)
+    results = []
+    for flag in (False, True):
+        blk = copy.deepcopy(block)
+        PC.route_training_convs(blk, narrow=narrow, bnstats=flag)
+        xg = x.clone().requires_grad_(True)
+        out = blk(xg)
+        out.backward(go)
+        results.append(dict(out=out.detach(), dx=xg.grad, **{k: p.grad for k, p in blk.named_parameters()},
+                            **{k: v.clone() for k, v in blk.named_buffers()}))
+    assert seen == [(planes, planes, 3, 3)] * 2, "both convolutions handed their statistics on, with the flag alone"
+    off, on = results
+    assert set(off) == set(on)
+    for k in sorted(off):
+        tol = (3e-5 if k == "out" else 1e-4 if k == "dx" else 2e-6 if k.endswith("running_mean") else 1e-5 if k.endswith("running_var")
+               else 5e-5)
+        _close(on[k], off[k], tol, "%d %s" % (planes, k))
+
+
+# ---- 5. the step ----------------------------------------------------------------------------------------------------------------
+
+class Counting:
+    """The library with the calls of the include/skd_bnstats.h entries counted."""
+
+    def __init__(self, lib):
+        self._lib, self.n = lib, {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in _lib.BNSTATS_SIGNATURES or name == "skd_conv3x3_bnstats_floats":
+            return fn
+
+        def counted(*args):
+            self.n[name] = self.n.get(name, 0) + 1
+            return fn(*args)
+        return counted
+
+
+def test_step_config1_with_the_statistics_from_the_epilogue(monkeypatch):
+    """The config-1 step of tests/test_step_gpu.py with ``split_train`` and ``split_bnstats`` on, the way the shortcut opt-in's
+    step test compares: test_step_config1_vs_reference_golden's own body runs, at exactly its bounds, with the switches set where
+    its ``default_args`` reads them; and the losses are within that test's 1e-4 of the step with ``split_train`` alone.  The
+    counting library sees the 11 BasicBlock convolutions the training form routes and their 11 finalize launches -- with the
+    policy (BNSTATS_ROUTING_EXCLUDED) emptied, so that the step runs the mechanism whatever the measurements list."""
+    import test_step_gpu as TS
+    assert isinstance(PC.BNSTATS_ROUTING_EXCLUDED, frozenset) and all(len(e) == 3 for e in PC.BNSTATS_ROUTING_EXCLUDED)
+    monkeypatch.setattr(PC, "BNSTATS_ROUTING_EXCLUDED", frozenset())
+    monkeypatch.setenv("SKD_SPLIT_TRAIN", "1")
+    monkeypatch.setenv("SKD_SPLIT_BNSTATS", "0")
+    model, _, _ = TS._config1_step(pa=True)
+    assert model.split_train and not model.split_bnstats
+    base = {k: getattr(model, k) for k in ("mc_G_loss", "pi_G_loss", "pa_G_loss")}
+    del model
+    lib = Counting(_lib.load())
+    monkeypatch.setattr(_lib, "get", lambda: lib)
+    monkeypatch.setenv("SKD_SPLIT_BNSTATS", "1")
+    step, kept = TS._config1_step, []
+
+    def keeping(pa):
+        out = step(pa)
+        kept.append(out[0])
+        return out
+    monkeypatch.setattr(TS, "_config1_step", keeping)
+    TS.test_step_config1_vs_reference_golden()
+    assert kept[0].split_bnstats
+    convs = [c for blk in kept[0].student.modules() if isinstance(blk, PC.BasicBlock) for c in (blk.conv1, blk.conv2)
+             if c.stride[0] == 1 and c.in_channels % 128 == 0 and c.out_channels % 128 == 0]
+    assert len(convs) == 11
+    assert lib.n.get("skd_conv3x3_split_stats_nhwc", 0) == 11 and lib.n.get("skd_abn_stats_from_partials_nhwc", 0) == 11, lib.n
+    assert "skd_conv3x3_narrow_stats_nhwc" not in lib.n
+    for k, want in base.items():
+        print("config1 %-10s with statistics %.7g  without %.7g" % (k, getattr(kept[0], k), want))
+        assert abs(getattr(kept[0], k) - want) <= 1e-4 * abs(want), (k, getattr(kept[0], k), want)
