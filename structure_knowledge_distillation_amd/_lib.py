@@ -23,6 +23,7 @@ NARROW_WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include",
 SHORTCUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_shortcut.h"))
 SPLIT2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_split2.h"))
 BNSTATS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_bnstats.h"))
+STRIDE2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_stride2.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -261,6 +262,17 @@ BNSTATS_SIGNATURES = {
     "skd_abn_stats_from_partials_nhwc": (_I, [_L, _I, _P, _L, _P, _P, _P, _P, _F, _P]),
 }
 
+# Entry points declared in include/skd_stride2.h (csrc/conv3x3.hip with STRIDE = 2): the stride-2 frozen forward of the 128-column
+# 3x3 family -- the teacher's layer2.0 conv2 and the student's layer2.0 conv1 in its inference form -- extension entries in a table
+# of their own like the eleven above (tests/test_conv3x3_stride2_cpu.py checks header <-> table <-> exported symbols and sweeps the
+# host-only row map, tests/test_conv3x3_stride2_gpu.py holds the guard-band cases).  A back-end without them leaves those
+# convolutions on the library: nothing raises.
+STRIDE2_SIGNATURES = {
+    "skd_conv3x3_split_s2_supported": (_I, [_I, _I, _I, _I, _I, _I]),
+    "skd_conv3x3_split_s2_taps": (_I, [_I, _I, _L, _P, _P]),
+    "skd_conv3x3_split_s2_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -292,7 +304,7 @@ def load(path=None):
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
                   WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES,
-                  BNSTATS_SIGNATURES):
+                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

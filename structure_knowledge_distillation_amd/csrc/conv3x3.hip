@@ -1,4 +1,4 @@
-// conv3x3.hip -- 3x3, stride-1, "same" (padding = dilation) convolution as an IMPLICIT GEMM on the split-operand bf16-MFMA core
+// conv3x3.hip -- 3x3, stride-1 (frozen forwards: stride-2 too, STRIDE below), "same" (padding = dilation) convolution as an IMPLICIT GEMM on the split-operand bf16-MFMA core
 // of conv_split_dev.hpp (see conv1x1.hip for the core): fp32 in, fp32 out.
 //
 //     Y[m][n] = epi( sum_{tap, c} X[pixel(m) + shift(tap)][c] * W[n][c][tap] ),   M = B*H*W output pixels (channels-last),
@@ -44,6 +44,7 @@
 #include "skd_infer.h"
 #include "skd_narrow.h"
 #include "skd_split2.h"
+#include "skd_stride2.h"
 #include "skd_train.h"
 
 namespace skd {
@@ -142,6 +143,27 @@ struct Tile3 {
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES>(stage, low, acc); }
 };
 
+// STRIDE = 2 (include/skd_stride2.h; padding 1, dilation 1): THE row map of that form -- output row m = (b * Ho + oy) * Wo + ox of
+// the (B, Ho, Wo) output, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, reads the 3 x 3 window centred on input pixel (2 oy, 2 ox).
+// *pixel: the flattened index of that centre, (b * H + 2 oy) * W + 2 ox, which is always inside the image; *mask: bit 3 ty + tx
+// set iff tap (ty, tx) is, 0 <= 2 oy + ty - 1 < H and 0 <= 2 ox + tx - 1 < W.  Nothing else of the kernel knows the stride: the
+// tap shifts are those of the input's W, the rows of the output are m.  The kernel calls it per panel row, the host entry
+// skd_conv3x3_split_s2_taps per m (tests/test_conv3x3_stride2_cpu.py sweeps it).
+__host__ __device__ inline void s2_row_map(int H, int W, int64_t m, int64_t *pixel, unsigned *mask) {
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const int64_t howo = (int64_t)Ho * Wo, b = m / howo;
+  const int r = (int)(m - b * howo);
+  const int oy = r / Wo, ox = r - oy * Wo;
+  unsigned bits = 0;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const int y = 2 * oy + tap / 3 - 1, x = 2 * ox + tap % 3 - 1;
+    if (y >= 0 && y < H && x >= 0 && x < W) bits |= 1u << tap;
+  }
+  *mask = bits;
+  *pixel = (b * H + 2 * oy) * W + 2 * ox;
+}
+
 // STATS (include/skd_bnstats.h): the batch-norm statistics record of one 32 x 32 accumulator block, from the fp32 values
 // store_block has just stored (ACT = none, no BN terms: the stored value IS acc[q]).  Column `col` of the block lives in lanes l and
 // l ^ 32, sixteen rows each (store_block's row map), so a record is an in-lane sum, one exchange with the other half, the
@@ -174,8 +196,10 @@ __device__ __forceinline__ void block_stats(const f32x16 &acc, float *__restrict
 }
 
 // One output tile of TM x TN pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
-// in front of the activation (store_block): the second convolution of a BasicBlock.
-template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false>
+// in front of the activation (store_block): the second convolution of a BasicBlock.  STRIDE = 2: M counts the rows of the
+// (B, Ho, Wo) output, H and W stay the input's, and the rows' addresses and masks come from s2_row_map; STRIDE = 1 is the code
+// without it.
+template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
                                              const float *__restrict__ R, float *__restrict__ stats,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
@@ -201,6 +225,14 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
   for (int h = 0; h < kRA; ++h) {
     const int64_t m = m0 + grow + kRPP * h;
     const bool live = m < M;
+    if constexpr (STRIDE == 2) {
+      int64_t pixel = 0;
+      unsigned bits = 0;
+      if (live) s2_row_map(H, W, m, &pixel, &bits);
+      mask[h] = bits;
+      abase[h] = pixel * Cin + gkq;
+      continue;
+    }
     const int64_t mm = live ? m : 0;
     const int pix = (int)(mm % hw);
     const int py = pix / W, px = pix - py * W;
@@ -261,8 +293,9 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 // launch bound alone (profiles/r15_kernel_resources.md).
 constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kMinWG; }
 
-// PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h).
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false>
+// PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h); so does
+// STRIDE = 2 (include/skd_stride2.h), whose M is that of the smaller output.
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
@@ -273,6 +306,7 @@ void conv3x3_split_kernel(
   static_assert(TALL || TN == kTN, "64-row panels exist for the 128-column form only");
   static_assert(!STATS || (ACT == SKD_ACT_NONE && !HAS_RES && PIECES == 3), "statistics: the training forward's raw epilogue alone");
   static_assert(PIECES == 3 || (TN == kTN && !HAS_RES), "two pieces: the 128-column forward family without the residual");
+  static_assert(STRIDE == 1 || (STRIDE == 2 && TN == kTN && !HAS_RES && !STATS), "stride 2: the 128-column frozen forward alone");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -280,11 +314,11 @@ void conv3x3_split_kernel(
   if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -326,7 +360,7 @@ __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
   for (int p = 0; p < PIECES; ++p) pack[(tile * PIECES + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                    int geometry, hipStream_t st, float *stats = nullptr) {
@@ -334,7 +368,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN, PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
@@ -350,7 +384,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
       X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R, stats);
   return ok();
 }
@@ -361,7 +395,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
 // TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
-template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false>
+template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st, float *stats = nullptr) {
@@ -370,8 +404,8 @@ static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, c
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
-      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
-    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
   }
 }
 
@@ -474,6 +508,41 @@ static int run3_stats(int B, int H, int W, int Cin, int Cout, int dilation, cons
                                                     as_stream(stream), stats);
 }
 
+// include/skd_stride2.h: the predicate, the host evaluation of the row map and the frozen forward of the stride-2 form.
+static int supported3_s2(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return Cin > 0 && Cout > 0 && Cin % kBK == 0 && Cout % kTN == 0 && stride == 2 && padding == 1 && dilation == 1 && groups == 1;
+}
+
+static int taps_s2(int H, int W, int64_t m, int64_t *pixel, unsigned *mask) {
+  if (H < 1 || W < 1 || m < 0 || !pixel || !mask || (int64_t)H * W > 2147483647) return 0;
+  s2_row_map(H, W, m, pixel, mask);
+  return 1;
+}
+
+// out (B, Ho, Wo, Cout) = act(ABN_eval(conv3x3_stride2(x) + conv_bias)): run3's refusals (no residual), on the packs of either
+// piece count -- the image does not depend on the stride.  Raw and ReLU epilogues are instantiated; leaky ReLU is refused.
+template <int PIECES>
+static int run3_s2(int B, int H, int W, int Cin, int Cout, const float *x, const void *wpack, float *out, const float *conv_bias,
+                   const float *mean, const float *var, const float *weight, const float *bias, float eps, int activation,
+                   float slope, int geometry, skd_stream_t stream) {
+  if (!supported3_s2(Cin, Cout, 2, 1, 1, 1) || B < 1 || H < 1 || W < 1) return 0;
+  if (!x || !wpack || !out || (mean == nullptr) != (var == nullptr) || geometry < 0 || geometry > 3) return 0;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack)) & 15) return 0;
+  if ((int64_t)H * W > 2147483647) return 0;
+  const int64_t M = (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+  hipStream_t st = as_stream(stream);
+  const uint4 *bp = static_cast<const uint4 *>(wpack);
+  switch (activation) {
+    case SKD_ACT_NONE:
+      return launch3g<kTN, SKD_ACT_NONE, false, PIECES, false, 2>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps, slope, M,
+                                                                  H, W, Cin, Cout, 1, geometry, st);
+    case SKD_ACT_RELU:
+      return launch3g<kTN, SKD_ACT_RELU, false, PIECES, false, 2>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps, slope, M,
+                                                                  H, W, Cin, Cout, 1, geometry, st);
+    default: return 0;
+  }
+}
+
 }  // namespace
 }  // namespace skd
 
@@ -568,6 +637,23 @@ int skd_conv3x3_narrow_stats_nhwc(int B, int H, int W, int Cin, int Cout, int di
                                   float *out, const float *conv_bias, int geometry, float *stats, int64_t stats_floats,
                                   skd_stream_t stream) {
   return run3_stats<kNarrowTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, conv_bias, geometry, 1, stats, stats_floats, stream);
+}
+
+// include/skd_stride2.h: the stride-2 frozen forward of the 128-column family.
+int skd_conv3x3_split_s2_supported(int Cin, int Cout, int stride, int padding, int dilation, int groups) {
+  return supported3_s2(Cin, Cout, stride, padding, dilation, groups);
+}
+
+int skd_conv3x3_split_s2_taps(int H, int W, int64_t m, int64_t *pixel, unsigned *mask) { return taps_s2(H, W, m, pixel, mask); }
+
+int skd_conv3x3_split_s2_nhwc(int B, int H, int W, int Cin, int Cout, const float *x, const void *wpack, float *out,
+                              const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                              float eps, int activation, float slope, int pieces, int geometry, skd_stream_t stream) {
+  if (pieces == 3)
+    return run3_s2<3>(B, H, W, Cin, Cout, x, wpack, out, conv_bias, mean, var, weight, bias, eps, activation, slope, geometry, stream);
+  if (pieces == 2)
+    return run3_s2<2>(B, H, W, Cin, Cout, x, wpack, out, conv_bias, mean, var, weight, bias, eps, activation, slope, geometry, stream);
+  return 0;
 }
 
 }  // extern "C"

@@ -1022,6 +1022,52 @@ def conv3x3_narrow_eval(x, pack, cout, dilation, residual=None, conv_bias=None, 
                            _residual_cl(x, cout, residual))
 
 
+# include/skd_stride2.h: the stride-2 frozen forward of the 128-column family (csrc/conv3x3.hip with STRIDE = 2)
+_S2_ENTRY = "skd_conv3x3_split_s2_nhwc"
+_S2_ENTRIES = ("skd_conv3x3_split_s2_supported", _S2_ENTRY)
+
+
+def conv3x3_s2_supported(x, conv):
+    """True when the stride-2 form of the split-core 3x3 convolution (csrc/conv3x3.hip, include/skd_stride2.h) takes ``conv(x)``
+    of a frozen forward: no grad, a back-end that has the entries (the tests' C double does not: callers then run what they ran
+    before), an fp32 channels-last 16-byte-aligned input, a plain 3x3 / stride-2 / padding-1 / dilation-1 / ungrouped convolution
+    with Cin a multiple of 16 and Cout of 128.  Host tensors pass only under a test double, as in conv3x3_infer_supported."""
+    return _conv3x3_module_ok(x, conv, grad=False, entries=_S2_ENTRIES, query="skd_conv3x3_split_s2_supported", host_ok=True)
+
+
+def conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", pieces=3):
+    """act(bn_running(conv3x3(x, stride 2, padding 1) + conv_bias)) in one launch of csrc/conv3x3.hip's stride-2 form
+    (include/skd_stride2.h; inference only; conv3x3_s2_supported says when), returned as a plain channels-last (B, cout, Ho, Wo) allocation, Ho = (H - 1) // 2 + 1.
+    ``pack = conv3x3_pack_weights(conv, pieces=pieces)``: the image does not depend on the stride, so it is the cache of the
+    stride-1 form under the one rule of _version_key.  Only the row map differs from conv3x3_split_eval: the result is that
+    op's output at the even pixels bit for bit (tests/test_conv3x3_stride2_gpu.py), and its numerics are that op's for either
+    piece count.  ``activation``: 'none' or 'relu'.  A back-end without the entry raises; the call is never downgraded."""
+    pieces = _check_pieces(pieces)
+    if activation not in ("none", "relu"):
+        raise ValueError("conv3x3_s2_eval: activation must be 'none' or 'relu', not %r" % (activation,))
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("conv3x3_s2_eval is inference-only")
+    if not _lib.has_entry(_S2_ENTRY):
+        raise NotImplementedError("this back-end has no %s (include/skd_stride2.h)" % _S2_ENTRY)
+    lib = _lib.get()
+    b, cin, h, w = x.shape
+    if pieces == 2:
+        _need_split2_entry(_PACK2_BYTES)
+    if pack.numel() != (getattr(lib, _PACK2_BYTES) if pieces == 2 else lib.skd_conv3x3_split_pack_bytes)(cin, cout):
+        raise ValueError("%s: the pack is not the %d-piece image of a (%d, %d, 3, 3) weight" % (_S2_ENTRY, pieces, cout, cin))
+    mean = var = gamma = beta = None
+    eps, slope = 0.0, 0.01
+    if bn is not None:
+        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
+    _lib.require_device(x, pack, conv_bias, mean, var, gamma, beta)
+    out = torch.empty((b, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
+                      memory_format=torch.channels_last)
+    _lib.check(getattr(lib, _S2_ENTRY)(b, h, w, cin, cout, x.data_ptr(), pack.data_ptr(), out.data_ptr(), _lib.ptr(conv_bias),
+                                       _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, _ACT[activation], slope,
+                                       pieces, 0, _lib.stream_of(x)), _S2_ENTRY)
+    return out
+
+
 def conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups):
     """True when conv3x3_split_train(..., narrow=True) takes the convolution of a network that is being trained: everything
     conv3x3_train_supported asks, except that each direction need only fit the wide form OR the narrow one -- Cin and Cout

@@ -31,7 +31,9 @@ unchanged.
 The student's fused inference form (``networks.fuse_for_inference(model)``, or ``default_args(fused_eval=True)`` for NetModel's
 student): ``evaluate_main``, ``predict_whole``, ``predict_sliding`` and ``predict_multiscale`` take the model as it is given --
 flagged or not -- and need no argument for it; a flagged model's eval-mode forwards run its BasicBlocks on the split-core 3x3
-convolution (networks/pspnet_combine.py), everything behind the forward is the same code.
+convolution (networks/pspnet_combine.py), everything behind the forward is the same code.  With ``split_narrow`` /
+``SKD_SPLIT_NARROW=1`` the 64-channel convolutions join them, and with ``split_stride2`` / ``SKD_SPLIT_STRIDE2=1`` layer2.0's
+stride-2 ``conv1`` does (``fuse_for_inference(model, stride2=True)``, include/skd_stride2.h).
 
 Not provided: the cv2-based dataset readers; ``recurrence`` and flipping in sliding mode are accepted and ignored, as in the
 reference.  A back-end without ``skd_seg_sliding`` / ``skd_zoom_linear`` / ``skd_seg_multiscale`` (the plain-C double of

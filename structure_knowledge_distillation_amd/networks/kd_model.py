@@ -31,7 +31,8 @@ from ..utils import parallel as parallel_old
 from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
 from ..utils.utils import print_model_parm_nums, to_tuple_str  # noqa: F401
-from .pspnet_combine import BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_training_convs, set_teacher_pieces
+from .pspnet_combine import (BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_teacher_early, route_training_convs,
+                             set_teacher_pieces)
 from .sagan_models import Discriminator
 
 
@@ -181,11 +182,19 @@ class NetModel():
         if split_narrow is None:
             split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"
         self.split_narrow = bool(split_narrow)
+        # args.split_stride2 (None: SKD_SPLIT_STRIDE2, default "0"): with fused_eval, layer2.0's stride-2 conv1 (64 -> 128) runs
+        # conv1 -> bn1 -> relu as one launch of the stride-2 form of csrc/conv3x3.hip (include/skd_stride2.h); without fused_eval
+        # it routes nothing.  Off by default (profiles/r27_conv3x3_early_isolated.md).
+        split_stride2 = getattr(args, "split_stride2", None)
+        if split_stride2 is None:
+            split_stride2 = os.environ.get("SKD_SPLIT_STRIDE2", "0") == "1"
+        self.split_stride2 = bool(split_stride2)
         if getattr(args, "fused_eval", False):
+            extra = dict(stride2=True) if self.split_stride2 else {}
             if self.split_narrow:
-                fuse_for_inference(student, narrow=True)
+                fuse_for_inference(student, narrow=True, **extra)
             else:
-                fuse_for_inference(student)
+                fuse_for_inference(student, **extra)
         # args.split_train (None: SKD_SPLIT_TRAIN, default "0"): the student's stride-1 3x3 convolutions with >= 128 channels and
         # their data gradients run on the split core in training (pspnet_combine.route_training_convs); the weight gradients,
         # the eval forms and the frozen teacher are what they were.  Off by default (profiles/r18_step_ab.md has the A/B).
@@ -260,6 +269,17 @@ class NetModel():
         if self.teacher_nhwc:
             os.environ["PYTORCH_MIOPEN_SUGGEST_NHWC"] = "1"
             teacher.to(memory_format=torch.channels_last)
+        # args.teacher_early (None: SKD_TEACHER_EARLY, default "0"): the frozen teacher's nine 3x3 convolutions below 256 input
+        # channels (stem conv2 / conv3, layer1, layer2 -- layer2.0's at stride 2) on the split core instead of the library
+        # (pspnet_combine.route_teacher_early, include/skd_stride2.h).  The teacher alone; independent of the student's switches; off
+        # by default (profiles/r27_conv3x3_early_isolated.md, profiles/r27_step_ab.md).  Set here, behind set_teacher_pieces and
+        # with the weights where they stay, so the packs exist before any warm-up step or teacher-graph capture.
+        teacher_early = getattr(args, "teacher_early", None)
+        if teacher_early is None:
+            teacher_early = os.environ.get("SKD_TEACHER_EARLY", "0") == "1"
+        self.teacher_early = bool(teacher_early)
+        if self.teacher_early:
+            route_teacher_early(teacher)
 
         D_model = Discriminator(args.preprocess_GAN_mode, args.classes_num, args.batch_size,
                                 args.imsize_for_adv, args.adv_conv_dim)
@@ -907,7 +927,7 @@ def default_args(**overrides):
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
-        split_bnstats=None)
+        split_bnstats=None, teacher_early=None, split_stride2=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
@@ -922,5 +942,9 @@ def default_args(**overrides):
         a.split_shortcut = os.environ.get("SKD_SPLIT_SHORTCUT", "0") == "1"
     if a.split_bnstats is None:        # effective only together with split_train
         a.split_bnstats = os.environ.get("SKD_SPLIT_BNSTATS", "0") == "1"
+    if a.teacher_early is None:        # the frozen teacher's stem / layer1 / layer2 3x3 convolutions on the split core
+        a.teacher_early = os.environ.get("SKD_TEACHER_EARLY", "0") == "1"
+    if a.split_stride2 is None:        # effective only together with fused_eval
+        a.split_stride2 = os.environ.get("SKD_SPLIT_STRIDE2", "0") == "1"
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     return a

@@ -50,7 +50,9 @@ CONV3X3_SPLIT = True  # the frozen network's stride-1 3x3 convolutions with >= C
                       # the PSP bottleneck's feature half, the deep-supervision head) as implicit GEMMs on the bf16 MFMA with the
                       # three-piece operand split (csrc/conv3x3.hip) instead of MIOpen's fp32-MFMA kernels; profiles/r12_conv3x3_isolated.md
                       # (1.16-1.30 x per launch), profiles/r12_step_ab.md (59.38-59.71 -> 55.40-55.67 ms per step)
-CONV3X3_SPLIT_MIN_CIN = 256   # the 64- / 128-channel 3x3s (stem, layer1, layer2: narrow N, ~1.6 ms together) stay on MIOpen
+CONV3X3_SPLIT_MIN_CIN = 256   # the 64- / 128-channel 3x3s (stem, layer1, layer2: narrow N, ~1.6 ms together) stay on MIOpen unless
+                              # route_teacher_early flags the network (opt-in, below: the 64-column form, the wide kernel and,
+                              # for layer2.0's stride-2 conv2, the stride-2 forward form of include/skd_stride2.h)
 SPLIT_REDUCE = True   # the reduce / stride-1 down-sample 1x1 GEMMs on csrc/conv1x1.hip's split core instead of the library GEMM wherever
                       # profiles/r11_stage2_isolated.md shows the kernel ahead (every shape but 512 -> 128); profiles/r12_step_ab.md:
                       # 55.40-55.67 ms per step off, 54.61-55.07 on, five interleaved runs each, the sets do not overlap
@@ -127,6 +129,22 @@ SPLIT2_ROUTING_EXCLUDED = frozenset()
 # +0.14 / +0.16 ms at the median, ranges overlapping (profiles/r26_step_ab.md).
 BNSTATS_ROUTING_EXCLUDED = frozenset({(128, 128, 1), (128, 256, 2), (256, 256, 2), (256, 512, 4), (512, 512, 4), (128, 64, 1),
                                       (64, 64, 1)})
+# The frozen teacher's early 3x3 convolutions (route_teacher_early(model), below; an eighth opt-in): the nine convolutions of a
+# flagged Bottleneck network with fewer than CONV3X3_SPLIT_MIN_CIN input channels -- the stem's conv2 (64 -> 64, bn2 + ReLU in the
+# epilogue) and layer1's three conv2 on the 64-column form, the stem's conv3 (64 -> 128) and layer2's three stride-1 conv2 on the
+# wide kernel, layer2.0's stride-2 conv2 on the stride-2 form (include/skd_stride2.h) -- all but the stem's conv2 raw, in front of
+# the fused tail's bn2 + ReLU prologue.  A shape that does not measure ahead of the library by more than the spread is listed here
+# as (Cin, Cout, stride, dilation) and keeps the library (profiles/r27_conv3x3_early_isolated.md has every shape).
+# Measured on the MI355X at batch 8: all nine are 1.28 - 1.37 x ahead of the library (the five wide ones 2.09 - 2.14 x on two
+# pieces) at a spread of at most 2.8 %, so the set is empty.  The step: -0.53 ms at the median, sets apart (profiles/r27_step_ab.md).
+TEACHER_EARLY_ROUTING_EXCLUDED = frozenset()
+# The student's stride-2 3x3 convolution in its inference form (fuse_for_inference(stride2=True); a further opt-in on top of the
+# fused inference form): a flagged BasicBlock whose conv1 has stride 2 and a Cout that is a multiple of 128 -- layer2.0 (64 ->
+# 128) -- runs conv1 -> bn1 -> relu as one launch of the stride-2 form.  A shape that measures behind is listed here as
+# (Cin, Cout) and keeps conv -> forward_relu: none does (64 -> 128 at 257 x 513, batch 1: 3.06 x ahead of convolution + ABN pass).
+STRIDE2_ROUTING_EXCLUDED = frozenset()
+_TEACHER_EARLY_ENTRIES = ("skd_conv3x3_split_s2_supported", "skd_conv3x3_split_s2_nhwc", "skd_conv3x3_split_supported",
+                          "skd_conv3x3_split_nhwc", "skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_nhwc")
 _SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
                    "skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn2_pro_nhwc")
 
@@ -154,6 +172,30 @@ def _narrow_infer_routed(module, x, conv, residual=False):
     if conv.out_channels % 128 == 0:
         return "wide" if SF.conv3x3_infer_supported(x, conv, residual) else False
     return "narrow" if SF.conv3x3_narrow_supported(x, conv, residual) else False
+
+
+def _early_form(x, conv):
+    """The split-core form route_teacher_early gives ``conv(x)`` of a frozen forward: "narrow" (the 64-column entry), "wide" (the
+    128-column one), "s2" (the stride-2 one, include/skd_stride2.h), or False -- a convolution with a bias or with
+    CONV3X3_SPLIT_MIN_CIN input channels or more (those are _conv3x3_split's), a shape TEACHER_EARLY_ROUTING_EXCLUDED lists, a
+    back-end without the entries, a call the op's predicate refuses (grad enabled, an input that is not an fp32 channels-last map)."""
+    geometry = SF.conv2d_square_geometry(conv)
+    if (geometry is None or conv.bias is not None or conv.in_channels >= CONV3X3_SPLIT_MIN_CIN
+            or (conv.in_channels, conv.out_channels, geometry[0], geometry[2]) in TEACHER_EARLY_ROUTING_EXCLUDED
+            or not all(_lib.has_entry(n) for n in _TEACHER_EARLY_ENTRIES)):
+        return False
+    if geometry[0] == 2:
+        return "s2" if SF.conv3x3_s2_supported(x, conv) else False
+    if conv.out_channels % 128 == 0:
+        return "wide" if SF.conv3x3_infer_supported(x, conv) else False
+    return "narrow" if SF.conv3x3_narrow_supported(x, conv) else False
+
+
+def _early_routed(module, x, conv):
+    """_early_form for a ``module`` route_teacher_early flagged, in eval mode, under no grad; False otherwise."""
+    if not getattr(module, "_skd_teacher_early", False) or module.training or torch.is_grad_enabled():
+        return False
+    return _early_form(x, conv)
 
 
 def _narrow_train_routed(module, x, conv):
@@ -261,12 +303,17 @@ def _conv3x3_split(x, conv):
             and SF.conv3x3_split_supported(x, conv))
 
 
-def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False, owner=None):
+def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False, owner=None, stride2=False):
     """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, for a call one of the
     SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names).  ``narrow``: the
     64-column form (the same file, include/skd_narrow.h) on its own pack, for a call SF.conv3x3_narrow_supported accepted.
     ``owner``: the calling module of a frozen teacher; where set_teacher_pieces marked it, the wide form without residual runs on
-    two pieces (its own pack)."""
+    two pieces (its own pack).  ``stride2``: the stride-2 form (include/skd_stride2.h) on the wide form's pack of either piece
+    count, for a call SF.conv3x3_s2_supported accepted."""
+    if stride2:
+        pieces = _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0])
+        extra = dict(pieces=2) if pieces == 2 else {}
+        return SF.conv3x3_s2_eval(x, SF.conv3x3_pack_weights(conv, **extra), conv.out_channels, conv.bias, bn, activation, **extra)
     if (not narrow and residual is None
             and _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]) == 2):
         return SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv, pieces=2), conv.out_channels, conv.dilation[0], conv.bias, bn,
@@ -355,13 +402,19 @@ class BasicBlock(nn.Module):
                 and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in INFER_ROUTING_EXCLUDED
                 and SF.conv3x3_infer_supported(x, conv, residual)):
             return True
+        if (not residual and getattr(self, "_skd_infer_stride2", False) and conv.bias is None and tuple(conv.stride) == (2, 2)
+                and (conv.in_channels, conv.out_channels) not in STRIDE2_ROUTING_EXCLUDED and SF.conv3x3_s2_supported(x, conv)):
+            return "s2"      # fuse_for_inference(stride2=True): chosen by its stride, not by ``min_cin``
         return _narrow_infer_routed(self, x, conv, residual) == "narrow" and "narrow"
 
     def _forward_infer(self, x):
         """relu(bn1(conv1(x))) and relu(bn2(conv2(.)) + residual) as one launch of csrc/conv3x3.hip each (BN + ReLU, and BN +
         residual + ReLU, in the epilogue) where _routed says so."""
         r1 = self._routed(x, self.conv1, False)
-        out = _split_conv(x, self.conv1, self.bn1, "relu", narrow=r1 == "narrow") if r1 else self.bn1.forward_relu(self.conv1(x))
+        if r1 == "s2":
+            out = _split_conv(x, self.conv1, self.bn1, "relu", stride2=True)
+        else:
+            out = _split_conv(x, self.conv1, self.bn1, "relu", narrow=r1 == "narrow") if r1 else self.bn1.forward_relu(self.conv1(x))
         r2 = self._routed(out, self.conv2, True)
         if self.downsample is None:
             residual = x
@@ -422,7 +475,12 @@ class Bottleneck(nn.Module):
             else:
                 out = self.bn1.forward_relu(self.conv1(x))
             # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
-            c2 = _split_conv(out, self.conv2, owner=self) if _conv3x3_split(out, self.conv2) else self.conv2(out)
+            if _conv3x3_split(out, self.conv2):
+                c2 = _split_conv(out, self.conv2, owner=self)
+            else:
+                early = _early_routed(self, out, self.conv2)      # route_teacher_early: layer1 / layer2 of a flagged teacher
+                c2 = (_split_conv(out, self.conv2, owner=self, narrow=early == "narrow", stride2=early == "s2") if early
+                      else self.conv2(out))
             tail = (not self.training and _fused_tail(x) and SF.conv1x1_abn_supported(c2, self.conv3) and self.conv3.in_channels <= 512
                     and getattr(self.bn2, "activation", None) == "none" and getattr(self.bn3, "activation", None) == "none")
             if not tail:
@@ -585,6 +643,12 @@ class ResNet(nn.Module):
                 and x.is_contiguous(memory_format=torch.channels_last) and getattr(self.bn2, "activation", None) == "none"
                 and getattr(self.bn2, "running_mean", None) is not None and getattr(self.bn2, "running_var", None) is not None)
 
+    def _stem_early(self, x):
+        """_stem_narrow for a network route_teacher_early flagged (a frozen Bottleneck network: the teacher)."""
+        return (getattr(self, "_skd_teacher_early", False) and not torch.is_grad_enabled() and x.dim() == 4
+                and x.is_contiguous(memory_format=torch.channels_last) and getattr(self.bn2, "activation", None) == "none"
+                and getattr(self.bn2, "running_mean", None) is not None and getattr(self.bn2, "running_var", None) is not None)
+
     def forward(self, x):
         if _fused(self, x) and not self.training and getattr(self.bn3, "activation", None) == "none":
             # Frozen network: eval-mode BN + ReLU is a non-decreasing map per channel (its scale (|gamma| + eps) / sqrt(var + eps) is
@@ -597,6 +661,11 @@ class ResNet(nn.Module):
                 r2 = _narrow_infer_routed(self, x, self.conv2)
                 x = _split_conv(x, self.conv2, self.bn2, "relu", narrow=True) if r2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
                 c3 = _split_conv(x, self.conv3) if _narrow_infer_routed(self, x, self.conv3) == "wide" else self.conv3(x)
+            elif self._stem_early(x):
+                # route_teacher_early: the same path for the frozen teacher; conv3 on two pieces where set_teacher_pieces marked it
+                r2 = _early_routed(self, x, self.conv2)
+                x = _split_conv(x, self.conv2, self.bn2, "relu", narrow=True) if r2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
+                c3 = _split_conv(x, self.conv3, owner=self) if _early_routed(self, x, self.conv3) == "wide" else self.conv3(x)
             else:
                 x = self.bn2.forward_relu(self.conv2(x))
                 c3 = self.conv3(x)
@@ -648,7 +717,7 @@ def Res_pspnet(block=Bottleneck, layers=[3, 4, 23, 3], num_classes=21):
     return ResNet(block, layers, num_classes)
 
 
-def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False):
+def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False, stride2=False):
     """Flag every BasicBlock of ``model`` (the student) for the fused inference form and return ``model``.
 
     A flagged block in eval mode, with grad disabled, on an fp32 channels-last input runs ``conv1 -> bn1 -> relu`` and
@@ -664,6 +733,10 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
     64-column form of the kernel (include/skd_narrow.h; BN + ReLU, and BN + residual + ReLU, in the epilogue), the stem's
     conv2 on it with bn2 + ReLU in the epilogue, the stem's conv3 (64 -> 128) raw on the existing kernel in front of
     max_pool_stem and bn3 -- except the shapes of NARROW_ROUTING_EXCLUDED.  The stem is flagged on the ResNet itself.
+    ``stride2=True`` (a further opt-in): a flagged block whose ``conv1`` has stride 2 and a Cout that is a multiple of 128 -- in the
+    student layer2.0 (64 -> 128) -- runs ``conv1 -> bn1 -> relu`` as one launch of the stride-2 form of the kernel
+    (include/skd_stride2.h) on the wide form's pack -- except the shapes of STRIDE2_ROUTING_EXCLUDED; the default leaves every
+    existing call as it is.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
     is set and changes nothing."""
     for m in model.modules():
@@ -672,6 +745,8 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
         stem = isinstance(m, ResNet)
         convs = ((m.conv2, False), (m.conv3, False)) if stem else ((m.conv1, False), (m.conv2, True))
         m._skd_infer_narrow = bool(narrow and enable)
+        if not stem:
+            m._skd_infer_stride2 = bool(stride2 and enable)
         if not enable:
             if not stem:
                 m._skd_infer_min_cin = None
@@ -689,8 +764,50 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
                 how = _narrow_infer_routed(m, probe, conv, res) if stem else m._routed(probe, conv, res)
                 if how == "narrow":
                     SF.conv3x3_narrow_pack_weights(conv)
-                elif how:
+                elif how:                   # True, or "s2": the stride-2 form runs on the wide form's pack
                     SF.conv3x3_pack_weights(conv)
+    return model
+
+
+def route_teacher_early(model, enable=True):
+    """Flag ``model`` (a frozen Bottleneck network: the teacher) for its early 3x3 convolutions on the split core and return it.
+
+    A flagged network in eval mode, under no grad, on an fp32 channels-last device input runs the nine 3x3 convolutions below
+    CONV3X3_SPLIT_MIN_CIN input channels on csrc/conv3x3.hip instead of the library: the stem through the path _stem_narrow
+    implements for the student (``conv2`` + bn2 + ReLU as one launch of the 64-column form, ``conv3`` raw on the wide kernel),
+    layer1's three ``conv2`` raw on the 64-column form, layer2's three stride-1 ``conv2`` raw on the wide kernel and layer2.0's
+    stride-2 ``conv2`` raw on the stride-2 form (include/skd_stride2.h) -- except the shapes of TEACHER_EARLY_ROUTING_EXCLUDED.  The
+    raw outputs feed the fused tail's bn2 + ReLU prologue as in layer3 / layer4; everything else is what it was.  Under
+    ``set_teacher_pieces(model, 2)`` the five wide calls (the stem's ``conv3``, layer2's four) take two pieces unless
+    SPLIT2_ROUTING_EXCLUDED lists them as ("3x3", Cin, Cout, dilation); the four 64-column calls keep three.  Call it behind
+    set_teacher_pieces and with the weights where they will stay (device, memory format): the packs of the routed weights are made
+    here, so a graph captured later allocates nothing for them.  A BasicBlock network (the student) is left untouched.
+    ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
+    set and changes nothing."""
+    if not any(isinstance(m, Bottleneck) for m in model.modules()):
+        return model
+    for m in model.modules():
+        if not isinstance(m, (Bottleneck, ResNet)):
+            continue
+        convs = [c for c in ((m.conv2, m.conv3) if isinstance(m, ResNet) else (m.conv2,))
+                 if tuple(c.kernel_size) == (3, 3) and c.in_channels < CONV3X3_SPLIT_MIN_CIN]
+        if not enable:
+            vars(m).pop("_skd_teacher_early", None)
+            for conv in convs:
+                SF.drop_conv3x3_packs(conv)
+            continue
+        m._skd_teacher_early = True
+        with torch.no_grad():
+            for conv in convs:
+                w = conv.weight
+                if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
+                    continue
+                how = _early_form(w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2), conv)
+                if how == "narrow":
+                    SF.conv3x3_narrow_pack_weights(conv)
+                elif how:
+                    two = _pieces(m, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]) == 2
+                    SF.conv3x3_pack_weights(conv, **(dict(pieces=2) if two else {}))
     return model
 
 
