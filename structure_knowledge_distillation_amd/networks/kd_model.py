@@ -173,79 +173,17 @@ class NetModel():
         if self.student_nhwc:
             os.environ["PYTORCH_MIOPEN_SUGGEST_NHWC"] = "1"
             student.to(memory_format=torch.channels_last)
+        # The opt-in switches of the split core (SWITCHES, below), each ``args.<name>`` or, where that is None, its environment
+        # variable; one that is "effective only together with" others is off without them.
+        for name, env, needs in SWITCHES:
+            setattr(self, name, _switch(args, name, env) and all(getattr(self, n) for n in needs))
         # args.fused_eval: the student's eval-mode / no-grad forwards (validation between epochs, evaluate_main) take the fused
         # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
-        # args.split_narrow (None: SKD_SPLIT_NARROW, default "0"): the 64-channel 3x3 convolutions of the stem and layer1 on the
-        # split core too (the 64-column form of csrc/conv3x3.hip) -- in the fused inference form together with fused_eval, in
-        # training together with split_train; alone it routes nothing.  Off by default (profiles/r21_conv3x3_narrow_isolated.md, profiles/r21_step_ab.md).
-        split_narrow = getattr(args, "split_narrow", None)
-        if split_narrow is None:
-            split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"
-        self.split_narrow = bool(split_narrow)
-        # args.split_stride2 (None: SKD_SPLIT_STRIDE2, default "0"): with fused_eval, layer2.0's stride-2 conv1 (64 -> 128) runs
-        # conv1 -> bn1 -> relu as one launch of the stride-2 form of csrc/conv3x3.hip (include/skd_stride2.h); without fused_eval
-        # it routes nothing.  Off by default (profiles/r27_conv3x3_early_isolated.md).
-        split_stride2 = getattr(args, "split_stride2", None)
-        if split_stride2 is None:
-            split_stride2 = os.environ.get("SKD_SPLIT_STRIDE2", "0") == "1"
-        self.split_stride2 = bool(split_stride2)
         if getattr(args, "fused_eval", False):
-            extra = dict(stride2=True) if self.split_stride2 else {}
-            if self.split_narrow:
-                fuse_for_inference(student, narrow=True, **extra)
-            else:
-                fuse_for_inference(student, **extra)
-        # args.split_train (None: SKD_SPLIT_TRAIN, default "0"): the student's stride-1 3x3 convolutions with >= 128 channels and
-        # their data gradients run on the split core in training (pspnet_combine.route_training_convs); the weight gradients,
-        # the eval forms and the frozen teacher are what they were.  Off by default (profiles/r18_step_ab.md has the A/B).
-        split_train = getattr(args, "split_train", None)
-        if split_train is None:
-            split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
-        self.split_train = bool(split_train)
-        # args.split_wgrad (None: SKD_SPLIT_WGRAD, default "0"): with split_train, the weight gradients of those convolutions run
-        # on the split core as well (csrc/conv3x3_wgrad.hip); without split_train it routes nothing.  Off by default
-        # (isolated: profiles/r20_conv3x3_wgrad_isolated.md; the step A/B is in profiles/r23_step_ab.md: -1.55 ms per step).
-        split_wgrad = getattr(args, "split_wgrad", None)
-        if split_wgrad is None:
-            split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
-        self.split_wgrad = bool(split_wgrad) and self.split_train
-        # args.split_narrow_wgrad (None: SKD_SPLIT_NARROW_WGRAD, default "0"): with split_train and split_narrow, the weight
-        # gradients of the six 64-channel convolutions run on the split core too (the 128 x 64 form of csrc/conv3x3_wgrad.hip);
-        # without either it routes nothing, and it does not depend on split_wgrad.  Off by default
-        # (profiles/r23_conv3x3_narrow_wgrad_isolated.md, profiles/r23_step_ab.md).
-        split_narrow_wgrad = getattr(args, "split_narrow_wgrad", None)
-        if split_narrow_wgrad is None:
-            split_narrow_wgrad = os.environ.get("SKD_SPLIT_NARROW_WGRAD", "0") == "1"
-        self.split_narrow_wgrad = bool(split_narrow_wgrad) and self.split_train and self.split_narrow
-        # args.split_shortcut (None: SKD_SPLIT_SHORTCUT, default "0"): with split_train, the four 1x1 down-sample convolutions of the
-        # student's BasicBlocks run forward, data gradient and weight gradient on the split core (csrc/conv1x1_train.hip and the
-        # one-tap form of csrc/conv3x3_wgrad.hip); without split_train it routes nothing, and it depends on no other switch.  Off
-        # by default (profiles/r24_conv1x1_train_isolated.md, profiles/r24_step_ab.md).
-        split_shortcut = getattr(args, "split_shortcut", None)
-        if split_shortcut is None:
-            split_shortcut = os.environ.get("SKD_SPLIT_SHORTCUT", "0") == "1"
-        self.split_shortcut = bool(split_shortcut) and self.split_train
-        # args.split_bnstats (None: SKD_SPLIT_BNSTATS, default "0"): with split_train, the routed 3x3 convolutions of the student's
-        # BasicBlocks emit the batch-norm statistics of their output from the epilogue and the ABN forward behind them finishes
-        # those and applies (csrc/conv3x3.hip's STATS form, include/skd_bnstats.h); without split_train it routes nothing.  Single
-        # replica only: a synchronised normalisation ignores it.  Off by default
-        # (profiles/r26_conv3x3_bnstats_isolated.md, profiles/r26_step_ab.md).
-        split_bnstats = getattr(args, "split_bnstats", None)
-        if split_bnstats is None:
-            split_bnstats = os.environ.get("SKD_SPLIT_BNSTATS", "0") == "1"
-        self.split_bnstats = bool(split_bnstats) and self.split_train
+            fuse_for_inference(student, narrow=self.split_narrow, stride2=self.split_stride2)
         if self.split_train:
-            extra = dict(narrow=True) if self.split_narrow else {}
-            if self.split_bnstats:
-                extra["bnstats"] = True
-            if self.split_shortcut:
-                extra["shortcut"] = True
-            if self.split_narrow_wgrad:
-                extra["narrow_wgrad"] = True
-            if self.split_wgrad:
-                route_training_convs(student, wgrad=True, **extra)
-            else:
-                route_training_convs(student, **extra)
+            route_training_convs(student, wgrad=self.split_wgrad, narrow=self.split_narrow, narrow_wgrad=self.split_narrow_wgrad,
+                                 shortcut=self.split_shortcut, bnstats=self.split_bnstats)
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -269,15 +207,8 @@ class NetModel():
         if self.teacher_nhwc:
             os.environ["PYTORCH_MIOPEN_SUGGEST_NHWC"] = "1"
             teacher.to(memory_format=torch.channels_last)
-        # args.teacher_early (None: SKD_TEACHER_EARLY, default "0"): the frozen teacher's nine 3x3 convolutions below 256 input
-        # channels (stem conv2 / conv3, layer1, layer2 -- layer2.0's at stride 2) on the split core instead of the library
-        # (pspnet_combine.route_teacher_early, include/skd_stride2.h).  The teacher alone; independent of the student's switches; off
-        # by default (profiles/r27_conv3x3_early_isolated.md, profiles/r27_step_ab.md).  Set here, behind set_teacher_pieces and
-        # with the weights where they stay, so the packs exist before any warm-up step or teacher-graph capture.
-        teacher_early = getattr(args, "teacher_early", None)
-        if teacher_early is None:
-            teacher_early = os.environ.get("SKD_TEACHER_EARLY", "0") == "1"
-        self.teacher_early = bool(teacher_early)
+        # args.teacher_early (SWITCHES): set here, behind set_teacher_pieces and with the weights where they stay, so the packs exist
+        # before any warm-up step or teacher-graph capture.
         if self.teacher_early:
             route_teacher_early(teacher)
 
@@ -904,6 +835,48 @@ def advance_versions_after_step(optimizer, args=None, kwargs=None):
         torch.autograd.graph.increment_version(written)      # one host call for all of them
 
 
+# The eight boolean opt-in switches of the split core: (attribute of ``args`` and of NetModel, environment variable read where the
+# attribute is None -- the way to A/B the step without another flag -- default "0", the switches it is effective only together
+# with).  All off by default.
+SWITCHES = (
+    # the 64-channel 3x3 convolutions of the stem and layer1 on the split core too (the 64-column form of csrc/conv3x3.hip) -- in
+    # the fused inference form together with fused_eval, in training together with split_train; alone it routes nothing
+    # (profiles/r21_conv3x3_narrow_isolated.md, profiles/r21_step_ab.md)
+    ("split_narrow", "SKD_SPLIT_NARROW", ()),
+    # with fused_eval, layer2.0's stride-2 conv1 (64 -> 128) runs conv1 -> bn1 -> relu as one launch of the stride-2 form of
+    # csrc/conv3x3.hip (include/skd_stride2.h); without fused_eval it routes nothing (profiles/r27_conv3x3_early_isolated.md)
+    ("split_stride2", "SKD_SPLIT_STRIDE2", ()),
+    # the student's stride-1 3x3 convolutions with >= 128 channels and their data gradients run on the split core in training
+    # (pspnet_combine.route_training_convs); the weight gradients, the eval forms and the frozen teacher are what they were
+    # (profiles/r18_step_ab.md has the A/B)
+    ("split_train", "SKD_SPLIT_TRAIN", ()),
+    # the weight gradients of those convolutions run on the split core as well (csrc/conv3x3_wgrad.hip) (isolated:
+    # profiles/r20_conv3x3_wgrad_isolated.md; the step A/B is in profiles/r23_step_ab.md: -1.55 ms per step)
+    ("split_wgrad", "SKD_SPLIT_WGRAD", ("split_train",)),
+    # the weight gradients of the six 64-channel convolutions run on the split core too (the 128 x 64 form of
+    # csrc/conv3x3_wgrad.hip); it does not depend on split_wgrad (profiles/r23_conv3x3_narrow_wgrad_isolated.md, profiles/r23_step_ab.md)
+    ("split_narrow_wgrad", "SKD_SPLIT_NARROW_WGRAD", ("split_train", "split_narrow")),
+    # the four 1x1 down-sample convolutions of the student's BasicBlocks run forward, data gradient and weight gradient on the split
+    # core (csrc/conv1x1_train.hip and the one-tap form of csrc/conv3x3_wgrad.hip); it depends on no other switch
+    # (profiles/r24_conv1x1_train_isolated.md, profiles/r24_step_ab.md)
+    ("split_shortcut", "SKD_SPLIT_SHORTCUT", ("split_train",)),
+    # the routed 3x3 convolutions of the student's BasicBlocks emit the batch-norm statistics of their output from the epilogue and
+    # the ABN forward behind them finishes those and applies (csrc/conv3x3.hip's STATS form, include/skd_bnstats.h).  Single
+    # replica only: a synchronised normalisation ignores it (profiles/r26_conv3x3_bnstats_isolated.md, profiles/r26_step_ab.md)
+    ("split_bnstats", "SKD_SPLIT_BNSTATS", ("split_train",)),
+    # the frozen teacher's nine 3x3 convolutions below 256 input channels (stem conv2 / conv3, layer1, layer2 -- layer2.0's at
+    # stride 2) on the split core instead of the library (pspnet_combine.route_teacher_early, include/skd_stride2.h).  The teacher
+    # alone; independent of the student's switches (profiles/r27_conv3x3_early_isolated.md, profiles/r27_step_ab.md)
+    ("teacher_early", "SKD_TEACHER_EARLY", ()),
+)
+
+
+def _switch(args, name, env):
+    """``args.<name>`` as a bool; None or absent: whether the environment's ``env`` is "1" (default "0")."""
+    value = getattr(args, name, None)
+    return os.environ.get(env, "0") == "1" if value is None else bool(value)
+
+
 def _teacher_pieces(value):
     """``value`` (None: the environment's SKD_TEACHER_PIECES, default "3") as 2 or 3; anything else is a ValueError."""
     if value is None:
@@ -930,21 +903,8 @@ def default_args(**overrides):
         split_bnstats=None, teacher_early=None, split_stride2=None)
     for k, v in overrides.items():
         setattr(a, k, v)
-    if a.split_train is None:          # the environment switch: the way to A/B the step without another flag
-        a.split_train = os.environ.get("SKD_SPLIT_TRAIN", "0") == "1"
-    if a.split_wgrad is None:          # effective only together with split_train
-        a.split_wgrad = os.environ.get("SKD_SPLIT_WGRAD", "0") == "1"
-    if a.split_narrow is None:         # effective only together with fused_eval (inference) or split_train (training)
-        a.split_narrow = os.environ.get("SKD_SPLIT_NARROW", "0") == "1"
-    if a.split_narrow_wgrad is None:   # effective only together with split_train and split_narrow
-        a.split_narrow_wgrad = os.environ.get("SKD_SPLIT_NARROW_WGRAD", "0") == "1"
-    if a.split_shortcut is None:       # effective only together with split_train
-        a.split_shortcut = os.environ.get("SKD_SPLIT_SHORTCUT", "0") == "1"
-    if a.split_bnstats is None:        # effective only together with split_train
-        a.split_bnstats = os.environ.get("SKD_SPLIT_BNSTATS", "0") == "1"
-    if a.teacher_early is None:        # the frozen teacher's stem / layer1 / layer2 3x3 convolutions on the split core
-        a.teacher_early = os.environ.get("SKD_TEACHER_EARLY", "0") == "1"
-    if a.split_stride2 is None:        # effective only together with fused_eval
-        a.split_stride2 = os.environ.get("SKD_SPLIT_STRIDE2", "0") == "1"
+    for name, env, _ in SWITCHES:      # None: the environment switch
+        if getattr(a, name) is None:
+            setattr(a, name, _switch(a, name, env))
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     return a

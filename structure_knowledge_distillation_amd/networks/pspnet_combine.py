@@ -9,6 +9,7 @@ the training student's stride-1 3x3 convolutions and their data gradients (route
 MIOpen unless its ``wgrad`` is set: csrc/conv3x3_wgrad.hip; the 64-channel convolutions of the stem and layer1 only with ``narrow``:
 the 64-column form of csrc/conv3x3.hip), which run on the bf16 MFMA through a three-piece operand split; every normalisation is the hand-written InPlace-ABN of
 csrc/abn*.hip (``libs``), applied in place on the conv output.
+Which of these a convolution gets is decided in two places: _frozen_form (a frozen forward) and _train_form (a training one).
 """
 import functools
 
@@ -162,62 +163,62 @@ def _narrow_shape(conv):
     return cin % 64 == 0 and cout % 64 == 0 and (cin % 128 != 0 or cout % 128 != 0)
 
 
-def _narrow_infer_routed(module, x, conv, residual=False):
-    """Whether the ``narrow``-flagged ``module`` (fuse_for_inference) hands ``conv(x)`` of a frozen forward to the split core:
-    "narrow" for the 64-column entry (Cout = 64), "wide" for the existing one (the stem's conv3, 64 -> 128), False otherwise."""
-    if not getattr(module, "_skd_infer_narrow", False) or conv.bias is not None or not _narrow_shape(conv):
-        return False
-    if (conv.in_channels, conv.out_channels, conv.dilation[0], "infer") in NARROW_ROUTING_EXCLUDED:
-        return False
-    if conv.out_channels % 128 == 0:
-        return "wide" if SF.conv3x3_infer_supported(x, conv, residual) else False
-    return "narrow" if SF.conv3x3_narrow_supported(x, conv, residual) else False
+def _frozen_form(module, x, conv, residual=False, packing=False):
+    """The split-core form ``conv(x)`` of a frozen forward takes: "wide" (the 128-column kernel), "narrow" (the 64-column entry),
+    "s2" (the stride-2 one, include/skd_stride2.h) or None (the library).  ``module`` says whose convolution it is, and with it
+    which policies are asked, in this order:
 
+    a BasicBlock, behind its gate BasicBlock._infer_form (fuse_for_inference) -- each convolution is asked on its own: one the
+    kernel does not take (stride 2 without ``stride2``; Cout = 64 without ``narrow``) or the policy leaves out keeps
+    conv -> forward_relu while the other is fused.  "wide" for at least ``_skd_infer_min_cin`` input channels outside
+    INFER_ROUTING_EXCLUDED (Cin, Cout, dilation), and from this rule alone; "s2" with ``_skd_infer_stride2`` (chosen by its stride,
+    not by ``min_cin``) outside STRIDE2_ROUTING_EXCLUDED (Cin, Cout), never with a residual; "narrow" with ``_skd_infer_narrow``.
+    the ResNet, for its stem's conv2 / conv3 behind its gate ResNet._stem_routed -- with ``_skd_infer_narrow`` that opt-in's
+    answer and no other; otherwise route_teacher_early's.
+    a Bottleneck, or None for a convolution no opt-in is about (dsn[0]) -- "wide" under CONV3X3_SPLIT for an eval-mode convolution
+    with CONV3X3_SPLIT_MIN_CIN input channels or more that SF.conv3x3_split_supported takes; otherwise route_teacher_early's.
 
-def _early_form(x, conv):
-    """The split-core form route_teacher_early gives ``conv(x)`` of a frozen forward: "narrow" (the 64-column entry), "wide" (the
-    128-column one), "s2" (the stride-2 one, include/skd_stride2.h), or False -- a convolution with a bias or with
-    CONV3X3_SPLIT_MIN_CIN input channels or more (those are _conv3x3_split's), a shape TEACHER_EARLY_ROUTING_EXCLUDED lists, a
-    back-end without the entries, a call the op's predicate refuses (grad enabled, an input that is not an fp32 channels-last map)."""
+    ``_skd_infer_narrow`` (fuse_for_inference(narrow=True)): a convolution without bias, 64 channels on one side at least
+    (_narrow_shape), outside NARROW_ROUTING_EXCLUDED (Cin, Cout, dilation, "infer") -- "narrow" for the 64-column entry (Cout =
+    64), "wide" for the existing one (the stem's conv3, 64 -> 128).
+    ``_skd_teacher_early`` (route_teacher_early), in eval mode under no grad: a convolution without bias and with fewer than
+    CONV3X3_SPLIT_MIN_CIN input channels (the others are CONV3X3_SPLIT's), outside TEACHER_EARLY_ROUTING_EXCLUDED (Cin, Cout,
+    stride, dilation), on a back-end that has the entries -- "s2" at stride 2, "wide" for a Cout that is a multiple of 128,
+    "narrow" otherwise.  ``packing``: asked by _prepack, of a module that may be in training mode now and frozen later.
+
+    Every answer but None is one the op's predicate gave (through ``SF.`` at call time: tests patch those names): grad enabled
+    and an input that is not an fp32 channels-last map are refused there."""
+    cin, cout = conv.in_channels, conv.out_channels
+    block, stem = isinstance(module, BasicBlock), isinstance(module, ResNet)
+    if block:
+        min_cin = getattr(module, "_skd_infer_min_cin", None)
+        if (conv.bias is None and min_cin is not None and cin >= min_cin
+                and (cin, cout, conv.dilation[0]) not in INFER_ROUTING_EXCLUDED and SF.conv3x3_infer_supported(x, conv, residual)):
+            return "wide"
+        if (not residual and getattr(module, "_skd_infer_stride2", False) and conv.bias is None and tuple(conv.stride) == (2, 2)
+                and (cin, cout) not in STRIDE2_ROUTING_EXCLUDED and SF.conv3x3_s2_supported(x, conv)):
+            return "s2"
+    elif not stem and CONV3X3_SPLIT and cin >= CONV3X3_SPLIT_MIN_CIN and not conv.training and SF.conv3x3_split_supported(x, conv):
+        return "wide"
+    if block or (stem and getattr(module, "_skd_infer_narrow", False)):
+        if (not getattr(module, "_skd_infer_narrow", False) or conv.bias is not None or not _narrow_shape(conv)
+                or (cin, cout, conv.dilation[0], "infer") in NARROW_ROUTING_EXCLUDED):
+            return None
+        if cout % 128 == 0:      # in a BasicBlock "wide" comes from the min_cin rule alone
+            return "wide" if stem and SF.conv3x3_infer_supported(x, conv, residual) else None
+        return "narrow" if SF.conv3x3_narrow_supported(x, conv, residual) else None
+    if not getattr(module, "_skd_teacher_early", False) or (module.training and not packing) or torch.is_grad_enabled():
+        return None
     geometry = SF.conv2d_square_geometry(conv)
-    if (geometry is None or conv.bias is not None or conv.in_channels >= CONV3X3_SPLIT_MIN_CIN
-            or (conv.in_channels, conv.out_channels, geometry[0], geometry[2]) in TEACHER_EARLY_ROUTING_EXCLUDED
+    if (geometry is None or conv.bias is not None or cin >= CONV3X3_SPLIT_MIN_CIN
+            or (cin, cout, geometry[0], geometry[2]) in TEACHER_EARLY_ROUTING_EXCLUDED
             or not all(_lib.has_entry(n) for n in _TEACHER_EARLY_ENTRIES)):
-        return False
+        return None
     if geometry[0] == 2:
-        return "s2" if SF.conv3x3_s2_supported(x, conv) else False
-    if conv.out_channels % 128 == 0:
-        return "wide" if SF.conv3x3_infer_supported(x, conv) else False
-    return "narrow" if SF.conv3x3_narrow_supported(x, conv) else False
-
-
-def _early_routed(module, x, conv):
-    """_early_form for a ``module`` route_teacher_early flagged, in eval mode, under no grad; False otherwise."""
-    if not getattr(module, "_skd_teacher_early", False) or module.training or torch.is_grad_enabled():
-        return False
-    return _early_form(x, conv)
-
-
-def _narrow_train_routed(module, x, conv):
-    """Whether the ``narrow``-flagged ``module`` (route_training_convs) in training mode hands ``conv(x)`` to
-    SF.conv3x3_split_train(..., narrow=True)."""
-    if not getattr(module, "_skd_train_narrow", False) or not module.training or not _narrow_shape(conv):
-        return False
-    geometry = SF.conv2d_square_geometry(conv)
-    if geometry is None or (conv.in_channels, conv.out_channels, geometry[2], "train") in NARROW_ROUTING_EXCLUDED:
-        return False
-    return SF.conv3x3_narrow_train_supported(x, conv.weight, *geometry, conv.groups)
-
-
-def _train_routed(module, x, conv):
-    """Whether the flagged ``module`` (route_training_convs) in training mode hands ``conv(x)`` to SF.conv3x3_split_train."""
-    min_cin = getattr(module, "_skd_train_min_cin", None)
-    if min_cin is None or not module.training or conv.in_channels < min_cin:
-        return False
-    geometry = SF.conv2d_square_geometry(conv)
-    if geometry is None or (conv.in_channels, conv.out_channels, geometry[2]) in TRAIN_ROUTING_EXCLUDED:
-        return False
-    return SF.conv3x3_train_supported(x, conv.weight, *geometry, conv.groups)
+        return "s2" if SF.conv3x3_s2_supported(x, conv) else None
+    if cout % 128 == 0:
+        return "wide" if SF.conv3x3_infer_supported(x, conv) else None
+    return "narrow" if SF.conv3x3_narrow_supported(x, conv) else None
 
 
 def _wgrad_routed(module, cin, cout, dilation):
@@ -225,40 +226,47 @@ def _wgrad_routed(module, cin, cout, dilation):
     return bool(getattr(module, "_skd_train_wgrad", False)) and (cin, cout, dilation) not in WGRAD_ROUTING_EXCLUDED
 
 
-def _bnstats_routed(module, conv, bn):
-    """Whether a convolution the flagged ``module`` routes is asked for the statistics records of its output as well: the
-    module carries the flag (route_training_convs(bnstats=True)), the shape is not in BNSTATS_ROUTING_EXCLUDED, the back-end has
-    the entries of include/skd_bnstats.h and ``bn``, the normalisation behind the convolution, would use them (a training-mode
+def _train_form(module, x, conv, bn=None):
+    """``(form, wgrad, stats)``: how the flagged ``module`` (route_training_convs) in training mode runs ``conv(x)``.
+    ``form``: "wide" -- SF.conv3x3_split_train: at least ``_skd_train_min_cin`` input channels, outside TRAIN_ROUTING_EXCLUDED
+    (Cin, Cout, dilation), a call SF.conv3x3_train_supported takes; "narrow" -- the same op with ``narrow=True``: with
+    ``_skd_train_narrow``, a _narrow_shape outside NARROW_ROUTING_EXCLUDED (Cin, Cout, dilation, "train") that
+    SF.conv3x3_narrow_train_supported takes; None -- the module's own forward, and the two bits False.
+    ``wgrad``: the weight gradient on the split core as well -- _wgrad_routed for "wide"; ``_skd_train_narrow_wgrad`` outside
+    NARROW_WGRAD_ROUTING_EXCLUDED (Cin, Cout, dilation) for "narrow".
+    ``stats``: the convolution is asked for the statistics records of its output as well: the module carries the flag
+    (route_training_convs(bnstats=True)), the shape is not in BNSTATS_ROUTING_EXCLUDED (Cin, Cout, dilation), the back-end has the
+    entries of include/skd_bnstats.h and ``bn``, the normalisation behind the convolution, would use them (a training-mode
     ``activation='none'`` ABN whose call is not replicated)."""
-    return (bn is not None and bool(getattr(module, "_skd_train_bnstats", False))
-            and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in BNSTATS_ROUTING_EXCLUDED
-            and SF.conv3x3_bnstats_supported() and callable(getattr(bn, "takes_partials", None)) and bn.takes_partials())
+    min_cin, narrow = getattr(module, "_skd_train_min_cin", None), getattr(module, "_skd_train_narrow", False)
+    geometry = SF.conv2d_square_geometry(conv) if module.training and (min_cin is not None or narrow) else None
+    if geometry is None:      # an unflagged module, above all: nothing but the two flags is looked at
+        return None, False, False
+    shape = (conv.in_channels, conv.out_channels, geometry[2])
+    if (min_cin is not None and conv.in_channels >= min_cin and shape not in TRAIN_ROUTING_EXCLUDED
+            and SF.conv3x3_train_supported(x, conv.weight, *geometry, conv.groups)):
+        form, wgrad = "wide", _wgrad_routed(module, *shape)
+    elif (narrow and _narrow_shape(conv) and shape + ("train",) not in NARROW_ROUTING_EXCLUDED
+          and SF.conv3x3_narrow_train_supported(x, conv.weight, *geometry, conv.groups)):
+        form, wgrad = "narrow", bool(getattr(module, "_skd_train_narrow_wgrad", False)) and shape not in NARROW_WGRAD_ROUTING_EXCLUDED
+    else:
+        return None, False, False
+    stats = (bn is not None and bool(getattr(module, "_skd_train_bnstats", False)) and shape not in BNSTATS_ROUTING_EXCLUDED
+             and SF.conv3x3_bnstats_supported() and callable(getattr(bn, "takes_partials", None)) and bn.takes_partials())
+    return form, wgrad, stats
 
 
 def _train_conv(module, conv, x, bn=None):
-    """``conv(x)``: on the split core in both directions where _train_routed says so, the module's own forward otherwise.
-    With ``bn`` (the ABN whose forward_relu follows, BasicBlock): the pair ``(conv(x), partials)`` -- ``partials`` the statistics
-    records of the routed convolution's epilogue where _bnstats_routed says so, None otherwise."""
-    if bn is not None:
-        if _bnstats_routed(module, conv, bn):
-            d, cin, cout = conv.dilation[0], conv.in_channels, conv.out_channels
-            if _train_routed(module, x, conv):
-                return SF.conv3x3_split_train(x, conv.weight, d, conv.bias, owner=conv, wgrad=_wgrad_routed(module, cin, cout, d),
-                                              stats=True)
-            if _narrow_train_routed(module, x, conv):
-                nw = getattr(module, "_skd_train_narrow_wgrad", False) and (cin, cout, d) not in NARROW_WGRAD_ROUTING_EXCLUDED
-                return SF.conv3x3_split_train(x, conv.weight, d, conv.bias, owner=conv, narrow=True, narrow_wgrad=bool(nw), stats=True)
-        return _train_conv(module, conv, x), None
-    if _train_routed(module, x, conv):
-        if _wgrad_routed(module, conv.in_channels, conv.out_channels, conv.dilation[0]):
-            return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=True)
-        return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv)
-    if _narrow_train_routed(module, x, conv):
-        if (getattr(module, "_skd_train_narrow_wgrad", False)
-                and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in NARROW_WGRAD_ROUTING_EXCLUDED):
-            return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, narrow=True, narrow_wgrad=True)
-        return SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, narrow=True)
-    return conv(x)
+    """``(conv(x), partials)``: the convolution on the split core in both directions where _train_form says so, the module's own
+    forward otherwise; ``partials`` the statistics records of the routed convolution's epilogue where it says so for ``bn`` (the
+    ABN whose forward_relu follows, BasicBlock), None otherwise."""
+    form, wgrad, stats = _train_form(module, x, conv, bn)
+    if form is None:
+        return conv(x), None
+    narrow = form == "narrow"
+    out = SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=wgrad and not narrow, narrow=narrow,
+                                 narrow_wgrad=wgrad and narrow, stats=stats)
+    return out if stats else (out, None)
 
 
 def _shortcut(block, x):
@@ -292,39 +300,28 @@ def _conv1x1_bn_eval(x, conv, bn, relu, owner=None):
     library GEMM with the folded BN otherwise."""
     if (SPLIT_REDUCE and not (conv.in_channels == 512 and conv.out_channels == 128)      # the library wins 512 -> 128 (r11)
             and getattr(bn, "activation", None) == "none" and SF.conv1x1_abn_supported(x, conv)):
-        extra = dict(pieces=2) if _pieces(owner, "1x1", conv.in_channels, conv.out_channels) == 2 else {}
         return SF.conv1x1_abn_eval(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps,
-                                   "relu" if relu else "none", **extra)
+                                   "relu" if relu else "none", pieces=_pieces(owner, "1x1", conv.in_channels, conv.out_channels))
     return SF.conv1x1_bn_blas(x, conv, bn, relu=relu)
 
 
-def _conv3x3_split(x, conv):
-    return (CONV3X3_SPLIT and conv.in_channels >= CONV3X3_SPLIT_MIN_CIN and not conv.training
-            and SF.conv3x3_split_supported(x, conv))
-
-
-def _split_conv(x, conv, bn=None, activation="none", residual=None, narrow=False, owner=None, stride2=False):
-    """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, for a call one of the
-    SF.conv3x3_*_supported predicates accepted (through ``SF.`` at call time: tests patch those names).  ``narrow``: the
-    64-column form (the same file, include/skd_narrow.h) on its own pack, for a call SF.conv3x3_narrow_supported accepted.
-    ``owner``: the calling module of a frozen teacher; where set_teacher_pieces marked it, the wide form without residual runs on
-    two pieces (its own pack).  ``stride2``: the stride-2 form (include/skd_stride2.h) on the wide form's pack of either piece
-    count, for a call SF.conv3x3_s2_supported accepted."""
-    if stride2:
-        pieces = _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0])
-        extra = dict(pieces=2) if pieces == 2 else {}
-        return SF.conv3x3_s2_eval(x, SF.conv3x3_pack_weights(conv, **extra), conv.out_channels, conv.bias, bn, activation, **extra)
-    if (not narrow and residual is None
-            and _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]) == 2):
-        return SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv, pieces=2), conv.out_channels, conv.dilation[0], conv.bias, bn,
-                                     activation, pieces=2)
-    if narrow:
+def _split_conv(x, conv, form, bn=None, activation="none", residual=None, owner=None):
+    """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, in the ``form`` _frozen_form
+    gave: "wide"; "narrow", the 64-column form (the same file, include/skd_narrow.h) on its own pack; "s2", the stride-2 form
+    (include/skd_stride2.h) on the wide form's pack.  ``owner``: the calling module of a frozen teacher; where set_teacher_pieces
+    marked it, "wide" without residual and "s2" run on two pieces (their own pack); the other two keep three."""
+    pieces = _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0])
+    if form == "narrow":
         return SF.conv3x3_narrow_eval(x, SF.conv3x3_narrow_pack_weights(conv), conv.out_channels, conv.dilation[0], residual, conv.bias,
                                       bn, activation)
-    pack = SF.conv3x3_pack_weights(conv)
+    if form == "s2":
+        return SF.conv3x3_s2_eval(x, SF.conv3x3_pack_weights(conv, pieces=pieces), conv.out_channels, conv.bias, bn, activation,
+                                  pieces=pieces)
     if residual is not None:
-        return SF.conv3x3_split_res_eval(x, pack, conv.out_channels, conv.dilation[0], residual, bn, activation, conv.bias)
-    return SF.conv3x3_split_eval(x, pack, conv.out_channels, conv.dilation[0], conv.bias, bn, activation)
+        return SF.conv3x3_split_res_eval(x, SF.conv3x3_pack_weights(conv, pieces=3), conv.out_channels, conv.dilation[0], residual, bn,
+                                         activation, conv.bias)
+    return SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv, pieces=pieces), conv.out_channels, conv.dilation[0], conv.bias, bn,
+                                 activation, pieces=pieces)
 
 
 class _ClassifierConvFn(torch.autograd.Function):
@@ -394,50 +391,31 @@ class BasicBlock(nn.Module):
                 and all(getattr(bn, "activation", None) == "none" and getattr(bn, "running_mean", None) is not None
                         and getattr(bn, "running_var", None) is not None for bn in (self.bn1, self.bn2)))
 
-    def _routed(self, x, conv, residual):
-        """Whether the flagged block hands ``conv(x)`` to the split core.  Each convolution is asked on its own: one the kernel
-        does not take (stride 2; Cout = 64 without ``narrow``) or the policy leaves out keeps conv -> forward_relu while the other
-        is fused.  "narrow": the 64-column form takes it (_narrow_infer_routed)."""
-        if (conv.bias is None and conv.in_channels >= self._skd_infer_min_cin
-                and (conv.in_channels, conv.out_channels, conv.dilation[0]) not in INFER_ROUTING_EXCLUDED
-                and SF.conv3x3_infer_supported(x, conv, residual)):
-            return True
-        if (not residual and getattr(self, "_skd_infer_stride2", False) and conv.bias is None and tuple(conv.stride) == (2, 2)
-                and (conv.in_channels, conv.out_channels) not in STRIDE2_ROUTING_EXCLUDED and SF.conv3x3_s2_supported(x, conv)):
-            return "s2"      # fuse_for_inference(stride2=True): chosen by its stride, not by ``min_cin``
-        return _narrow_infer_routed(self, x, conv, residual) == "narrow" and "narrow"
-
     def _forward_infer(self, x):
         """relu(bn1(conv1(x))) and relu(bn2(conv2(.)) + residual) as one launch of csrc/conv3x3.hip each (BN + ReLU, and BN +
-        residual + ReLU, in the epilogue) where _routed says so."""
-        r1 = self._routed(x, self.conv1, False)
-        if r1 == "s2":
-            out = _split_conv(x, self.conv1, self.bn1, "relu", stride2=True)
-        else:
-            out = _split_conv(x, self.conv1, self.bn1, "relu", narrow=r1 == "narrow") if r1 else self.bn1.forward_relu(self.conv1(x))
-        r2 = self._routed(out, self.conv2, True)
+        residual + ReLU, in the epilogue) where _frozen_form says so."""
+        f1 = _frozen_form(self, x, self.conv1)
+        out = _split_conv(x, self.conv1, f1, self.bn1, "relu") if f1 else self.bn1.forward_relu(self.conv1(x))
+        f2 = _frozen_form(self, out, self.conv2, True)
         if self.downsample is None:
             residual = x
-        elif not (r1 or r2):                 # nothing of this block is routed: the sequence it ran before, op for op
+        elif not (f1 or f2):                 # nothing of this block is routed: the sequence it ran before, op for op
             residual = self.downsample(x)
         elif (_blas_tail(self, x) and len(self.downsample) == 2 and SF.blas_1x1_bn_supported(x, self.downsample[0])
               and getattr(self.downsample[1], "activation", None) == "none"):
             residual = _conv1x1_bn_eval(x, self.downsample[0], self.downsample[1], relu=False)
         else:
             residual = self.downsample(x)
-        if r2:
-            return _split_conv(out, self.conv2, self.bn2, "relu", residual, narrow=r2 == "narrow")
+        if f2:
+            return _split_conv(out, self.conv2, f2, self.bn2, "relu", residual)
         return self.bn2.forward_relu(self.conv2(out), residual)
 
     def forward(self, x):
         if self._infer_form(x):
             return self._forward_infer(x)
         if _fused(self, x):
-            if not getattr(self, "_skd_train_bnstats", False):
-                out = self.bn1.forward_relu(_train_conv(self, self.conv1, x))
-                residual = _shortcut(self, x) if self.downsample is not None else x
-                return self.bn2.forward_relu(_train_conv(self, self.conv2, out), residual)
-            # flagged (route_training_convs(bnstats=True)): a routed convolution hands the statistics of its output on
+            # ``partials``: where route_training_convs(bnstats=True) flagged the block, a routed convolution hands the statistics of
+            # its output on; None otherwise, which is forward_relu without them
             y, partials = _train_conv(self, self.conv1, x, self.bn1)
             out = self.bn1.forward_relu(y, partials=partials)
             residual = _shortcut(self, x) if self.downsample is not None else x
@@ -475,12 +453,8 @@ class Bottleneck(nn.Module):
             else:
                 out = self.bn1.forward_relu(self.conv1(x))
             # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
-            if _conv3x3_split(out, self.conv2):
-                c2 = _split_conv(out, self.conv2, owner=self)
-            else:
-                early = _early_routed(self, out, self.conv2)      # route_teacher_early: layer1 / layer2 of a flagged teacher
-                c2 = (_split_conv(out, self.conv2, owner=self, narrow=early == "narrow", stride2=early == "s2") if early
-                      else self.conv2(out))
+            form = _frozen_form(self, out, self.conv2)      # layer3 / layer4; layer1 / layer2 of a teacher route_teacher_early flagged
+            c2 = _split_conv(out, self.conv2, form, owner=self) if form else self.conv2(out)
             tail = (not self.training and _fused_tail(x) and SF.conv1x1_abn_supported(c2, self.conv3) and self.conv3.in_channels <= 512
                     and getattr(self.bn2, "activation", None) == "none" and getattr(self.bn3, "activation", None) == "none")
             if not tail:
@@ -493,10 +467,10 @@ class Bottleneck(nn.Module):
             else:
                 residual = self.downsample(x)
             if tail:
-                extra = dict(pieces=2) if _pieces(self, "1x1", self.conv3.in_channels, self.conv3.out_channels) == 2 else {}
                 return SF.conv1x1_abn_eval(c2, self.conv3.weight, self.bn3.running_mean, self.bn3.running_var, self.bn3.weight,
                                            self.bn3.bias, self.bn3.eps, "relu", residual=residual,
-                                           pro=SF.abn_pack_eval_params(self.bn2), **extra)
+                                           pro=SF.abn_pack_eval_params(self.bn2),
+                                           pieces=_pieces(self, "1x1", self.conv3.in_channels, self.conv3.out_channels))
             return self.bn3.forward_relu(self.conv3(out), residual)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -561,14 +535,13 @@ class PSPModule(nn.Module):
                 if not hasattr(self, "_fold_cache"):
                     self._fold_cache = {}
                 min_cin = getattr(self, "_skd_train_min_cin", None)
-                extra = dict(split_wgrad=True) if _wgrad_routed(self, feats.shape[1], conv.out_channels, 1) else {}
-                if not self.training and _pieces(self, "3x3", feats.shape[1], conv.out_channels, 1) == 2:
-                    extra["pieces"] = 2        # the frozen feature half on two pieces (set_teacher_pieces)
                 out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache,
                                              split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
                                              split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
                                                           and (feats.shape[1], conv.out_channels, 1) not in TRAIN_ROUTING_EXCLUDED),
-                                             **extra)
+                                             split_wgrad=_wgrad_routed(self, feats.shape[1], conv.out_channels, 1),
+                                             # the frozen feature half on two pieces (set_teacher_pieces)
+                                             pieces=3 if self.training else _pieces(self, "3x3", feats.shape[1], conv.out_channels, 1))
                 return self.bottleneck[2](self.bottleneck[1](out))
             return self.bottleneck(SF.ppm_concat(priors, feats))
         h, w = feats.size(2), feats.size(3)
@@ -629,23 +602,18 @@ class ResNet(nn.Module):
         csrc/conv3x3.hip (the Dropout2d between them and the classifier is the identity in eval mode)."""
         conv, bn = self.dsn[0], self.dsn[1]
         if (not self.training and not torch.is_grad_enabled() and getattr(bn, "activation", None) in ("none", "relu", "leaky_relu")
-                and hasattr(bn, "running_mean") and _conv3x3_split(x3, conv)):
-            return self.dsn[3](_split_conv(x3, conv, bn, bn.activation, owner=self))
-        if _train_routed(self, x3, conv):      # the training form: the same sequence with dsn[0] (bias in the epilogue) on the split core
-            return self.dsn[3](self.dsn[2](bn(_train_conv(self, conv, x3))))
+                and hasattr(bn, "running_mean") and _frozen_form(None, x3, conv)):      # no opt-in is about dsn[0]
+            return self.dsn[3](_split_conv(x3, conv, "wide", bn, bn.activation, owner=self))
+        if _train_form(self, x3, conv)[0] == "wide":      # the same sequence with dsn[0] (bias in the epilogue) on the split core
+            return self.dsn[3](self.dsn[2](bn(_train_conv(self, conv, x3)[0])))
         return self.dsn(x3)
 
-    def _stem_narrow(self, x):
-        """Whether the frozen forward asks _narrow_infer_routed about the stem's conv2 / conv3: this network is flagged
-        (fuse_for_inference(narrow=True): an unflagged teacher never is), no grad, ``x`` an fp32 channels-last map and bn2 a plain
-        eval-mode BatchNorm."""
-        return (getattr(self, "_skd_infer_narrow", False) and not torch.is_grad_enabled() and x.dim() == 4
-                and x.is_contiguous(memory_format=torch.channels_last) and getattr(self.bn2, "activation", None) == "none"
-                and getattr(self.bn2, "running_mean", None) is not None and getattr(self.bn2, "running_var", None) is not None)
-
-    def _stem_early(self, x):
-        """_stem_narrow for a network route_teacher_early flagged (a frozen Bottleneck network: the teacher)."""
-        return (getattr(self, "_skd_teacher_early", False) and not torch.is_grad_enabled() and x.dim() == 4
+    def _stem_routed(self, x):
+        """Whether the frozen forward asks _frozen_form about the stem's conv2 / conv3: this network is flagged
+        (fuse_for_inference(narrow=True), or route_teacher_early for a frozen Bottleneck network: an unflagged teacher never is), no
+        grad, ``x`` an fp32 channels-last map and bn2 a plain eval-mode BatchNorm."""
+        return ((getattr(self, "_skd_infer_narrow", False) or getattr(self, "_skd_teacher_early", False))
+                and not torch.is_grad_enabled() and x.dim() == 4
                 and x.is_contiguous(memory_format=torch.channels_last) and getattr(self.bn2, "activation", None) == "none"
                 and getattr(self.bn2, "running_mean", None) is not None and getattr(self.bn2, "running_var", None) is not None)
 
@@ -656,16 +624,13 @@ class ResNet(nn.Module):
             # the max-pool bit for bit: relu(bn(max(window))) == max(relu(bn(.)) over the window).  The pass over the 268 MB
             # conv3 output becomes a pass over the 68 MB pooled map (pspnet_combine.py:131-135; VERDICT r04 missing 5).
             x = self.bn1.forward_relu(self.conv1(x))
-            if self._stem_narrow(x):
-                # fuse_for_inference(narrow=True): conv2 + bn2 + ReLU as one launch of the 64-column form, conv3 raw on the wide kernel
-                r2 = _narrow_infer_routed(self, x, self.conv2)
-                x = _split_conv(x, self.conv2, self.bn2, "relu", narrow=True) if r2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
-                c3 = _split_conv(x, self.conv3) if _narrow_infer_routed(self, x, self.conv3) == "wide" else self.conv3(x)
-            elif self._stem_early(x):
-                # route_teacher_early: the same path for the frozen teacher; conv3 on two pieces where set_teacher_pieces marked it
-                r2 = _early_routed(self, x, self.conv2)
-                x = _split_conv(x, self.conv2, self.bn2, "relu", narrow=True) if r2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
-                c3 = _split_conv(x, self.conv3, owner=self) if _early_routed(self, x, self.conv3) == "wide" else self.conv3(x)
+            if self._stem_routed(x):
+                # conv2 + bn2 + ReLU as one launch of the 64-column form, conv3 raw on the wide kernel.  ``owner=self``: conv3 on
+                # two pieces where set_teacher_pieces marked this network; it marks the modules of Bottleneck networks alone, so
+                # a student's never carry ``_skd_teacher_pieces`` and its conv3 keeps three
+                f2 = _frozen_form(self, x, self.conv2)
+                x = _split_conv(x, self.conv2, f2, self.bn2, "relu") if f2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
+                c3 = _split_conv(x, self.conv3, "wide", owner=self) if _frozen_form(self, x, self.conv3) == "wide" else self.conv3(x)
             else:
                 x = self.bn2.forward_relu(self.conv2(x))
                 c3 = self.conv3(x)
@@ -673,11 +638,11 @@ class ResNet(nn.Module):
         else:
             if _fused(self, x):
                 x = self.bn1.forward_relu(self.conv1(x))
-                x = self.bn2.forward_relu(_train_conv(self, self.conv2, x))
+                x = self.bn2.forward_relu(_train_conv(self, self.conv2, x)[0])
                 # training: bn3 -> relu3 -> maxpool in two fused passes per direction (csrc/abn_stem.hip, round 6): the
                 # 268 MB normalised conv3 output is never written, its gradient never un-pooled into memory; STEM_FUSED = False or an
                 # input the fused kernels do not take: forward_relu, then csrc/maxpool.hip (channels-last) / the stock pool
-                c3 = _train_conv(self, self.conv3, x)       # the library's, unless route_training_convs(narrow=True) flagged the stem
+                c3 = _train_conv(self, self.conv3, x)[0]    # the library's, unless route_training_convs(narrow=True) flagged the stem
                 x = (self.bn3.forward_relu_maxpool(c3, self.maxpool) if STEM_FUSED
                      else SF.max_pool_stem(self.bn3.forward_relu(c3), self.maxpool))
             else:
@@ -715,6 +680,22 @@ class ResNet(nn.Module):
 def Res_pspnet(block=Bottleneck, layers=[3, 4, 23, 3], num_classes=21):
     """ResNet(Bottleneck, [3, 4, 23, 3], C) = teacher; ResNet(BasicBlock, [2, 2, 2, 2], C) = student."""
     return ResNet(block, layers, num_classes)
+
+
+def _prepack(module, convs):
+    """Make the weight pack of every ``(conv, residual?)`` of the freshly flagged ``module`` that _frozen_form routes and whose
+    fp32 weight is on the device already: the form is asked with a one-pixel channels-last map of the right width, and "wide" and
+    "s2" (which runs on the wide form's pack) take the piece count _split_conv will ask for with ``module`` as the owner."""
+    with torch.no_grad():
+        for conv, residual in convs:
+            w = conv.weight
+            if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
+                continue
+            form = _frozen_form(module, w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2), conv, residual, packing=True)
+            if form == "narrow":
+                SF.conv3x3_narrow_pack_weights(conv)
+            elif form:
+                SF.conv3x3_pack_weights(conv, pieces=_pieces(module, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]))
 
 
 def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False, stride2=False):
@@ -755,17 +736,7 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
             continue
         if not stem:
             m._skd_infer_min_cin = int(min_cin)
-        with torch.no_grad():
-            for conv, res in convs:
-                w = conv.weight
-                if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
-                    continue
-                probe = w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2)      # a channels-last map of the right width
-                how = _narrow_infer_routed(m, probe, conv, res) if stem else m._routed(probe, conv, res)
-                if how == "narrow":
-                    SF.conv3x3_narrow_pack_weights(conv)
-                elif how:                   # True, or "s2": the stride-2 form runs on the wide form's pack
-                    SF.conv3x3_pack_weights(conv)
+        _prepack(m, convs)
     return model
 
 
@@ -773,8 +744,8 @@ def route_teacher_early(model, enable=True):
     """Flag ``model`` (a frozen Bottleneck network: the teacher) for its early 3x3 convolutions on the split core and return it.
 
     A flagged network in eval mode, under no grad, on an fp32 channels-last device input runs the nine 3x3 convolutions below
-    CONV3X3_SPLIT_MIN_CIN input channels on csrc/conv3x3.hip instead of the library: the stem through the path _stem_narrow
-    implements for the student (``conv2`` + bn2 + ReLU as one launch of the 64-column form, ``conv3`` raw on the wide kernel),
+    CONV3X3_SPLIT_MIN_CIN input channels on csrc/conv3x3.hip instead of the library: the stem through the path the student's takes
+    under fuse_for_inference(narrow=True) (``conv2`` + bn2 + ReLU as one launch of the 64-column form, ``conv3`` raw on the wide kernel),
     layer1's three ``conv2`` raw on the 64-column form, layer2's three stride-1 ``conv2`` raw on the wide kernel and layer2.0's
     stride-2 ``conv2`` raw on the stride-2 form (include/skd_stride2.h) -- except the shapes of TEACHER_EARLY_ROUTING_EXCLUDED.  The
     raw outputs feed the fused tail's bn2 + ReLU prologue as in layer3 / layer4; everything else is what it was.  Under
@@ -797,17 +768,7 @@ def route_teacher_early(model, enable=True):
                 SF.drop_conv3x3_packs(conv)
             continue
         m._skd_teacher_early = True
-        with torch.no_grad():
-            for conv in convs:
-                w = conv.weight
-                if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
-                    continue
-                how = _early_form(w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2), conv)
-                if how == "narrow":
-                    SF.conv3x3_narrow_pack_weights(conv)
-                elif how:
-                    two = _pieces(m, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]) == 2
-                    SF.conv3x3_pack_weights(conv, **(dict(pieces=2) if two else {}))
+        _prepack(m, [(conv, False) for conv in convs])
     return model
 
 
@@ -865,7 +826,7 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     ``wgrad=True``: the weight gradients of the routed convolutions run on the split core as well (SF.conv3x3_split_wgrad,
     csrc/conv3x3_wgrad.hip) except for the shapes of WGRAD_ROUTING_EXCLUDED; on a back-end without the entries of
     include/skd_wgrad.h they stay with the library.
-    ``narrow=True``: the stem's conv2 / conv3 and layer1's four convolutions too (SF.conv3x3_split_train(..., narrow=True): each
+    ``narrow=True``: the stem's conv2 / conv3 and layer1's four convolutions too (SF.conv3x3_split_train with ``narrow=True``: each
     direction on the 128-column form of the kernel where its N is a multiple of 128, on the 64-column one otherwise; their weight gradients
     stay with the library) except for the shapes of NARROW_ROUTING_EXCLUDED.
     ``narrow_wgrad=True``: the weight gradients of the convolutions ``narrow`` routes run on the split core as well
@@ -876,7 +837,7 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     except for the (Cin, Cout, stride, product) of SHORTCUT_ROUTING_EXCLUDED; on a back-end without the entries they stay with the
     library.  It does not depend on the other three.
     ``bnstats=True``: a BasicBlock's routed conv1 / conv2 (the 11 wide ones of layer2-4; with ``narrow`` layer1's four) also emits
-    the batch-norm statistics of its output from the epilogue (SF.conv3x3_split_train(..., stats=True), include/skd_bnstats.h) and
+    the batch-norm statistics of its output from the epilogue (SF.conv3x3_split_train with ``stats=True``, include/skd_bnstats.h) and
     the forward_relu behind it finishes them and applies, except for the shapes of BNSTATS_ROUTING_EXCLUDED; replicated
     (synchronised) normalisations, dsn[0], the stem, the PSP bottleneck and the shortcuts are what they were, and so are the
     convolution's output bits and every backward.  On a back-end without the entries nothing changes.

@@ -204,7 +204,7 @@ def test_routing_of_a_flagged_student(recording):
     xn = torch.randn(2, 256, 5, 6)
     net.layer3[1](xn)                   # each convolution is asked on its own: conv1 reads the NCHW map and keeps the library
     assert all(c["x"] != xn.data_ptr() for c in recording.calls) and len(recording.calls) <= 1
-    assert not PC._train_routed(net.layer3[1], xn, net.layer3[1].conv1)
+    assert not PC._train_form(net.layer3[1], xn, net.layer3[1].conv1)[0]
     recording.calls.clear()
     net.layer3[1](torch.randn(2, 256, 5, 6).contiguous(memory_format=torch.channels_last))
     assert len(recording.calls) == 2

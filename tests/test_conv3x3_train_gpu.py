@@ -364,9 +364,9 @@ def test_step_config1_with_the_training_form(monkeypatch):
     real_op, real_launch = SF.conv3x3_split_train, SF._conv3x3_split_launch
     seen = {"forward": 0, "bwd_packs": set(), "fwd_packs": set(), "launch_fwd": 0, "launch_bwd": 0}
 
-    def op(x, weight, dilation, bias=None, owner=None):
+    def op(x, weight, dilation, bias=None, owner=None, **kw):
         seen["forward"] += 1
-        out = real_op(x, weight, dilation, bias, owner)
+        out = real_op(x, weight, dilation, bias, owner, **kw)
         pf, pb = SF.conv3x3_train_packs(weight, owner)             # the cached pair this forward used
         seen["fwd_packs"].add(pf.data_ptr())
         seen["bwd_packs"].add(pb.data_ptr())
