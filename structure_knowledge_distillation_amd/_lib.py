@@ -24,6 +24,7 @@ SHORTCUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "sk
 SPLIT2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_split2.h"))
 BNSTATS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_bnstats.h"))
 STRIDE2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_stride2.h"))
+PAIRWISE_SPLIT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_pairwise_split.h"))
 
 _c = ctypes
 _P = _c.c_void_p
@@ -273,6 +274,18 @@ STRIDE2_SIGNATURES = {
     "skd_conv3x3_split_s2_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _P]),
 }
 
+# Entry points declared in include/skd_pairwise_split.h (csrc/pairwise_split.hip): the Gram + loss and the backward product of the
+# pair-wise similarity loss on the split core, twins of skd_pairwise_gram_loss / skd_pairwise_backward with the same argument
+# lists, extension entries in a table of their own like the twelve above (tests/test_pairwise_split_cpu.py checks header <-> table
+# <-> exported symbols, tests/test_pairwise_split_gpu.py holds the guard-band cases).  A back-end without them leaves the loss on
+# the fp32 kernels (kd_model warns when the switch asks for them): nothing raises.
+PAIRWISE_SPLIT_SIGNATURES = {
+    "skd_pairwise_split_workspace_floats": (_L, [_I, _I, _I, _I]),
+    "skd_pairwise_split_gram_loss": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "skd_pairwise_split_backward_workspace_floats": (_L, [_I, _I, _I]),
+    "skd_pairwise_split_backward": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -304,7 +317,7 @@ def load(path=None):
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
                   WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES,
-                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES):
+                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES, PAIRWISE_SPLIT_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

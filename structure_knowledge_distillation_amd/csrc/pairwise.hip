@@ -15,7 +15,9 @@
 //             (B, ldm, ldc) is still offered by the entry; the backward GEMM no longer needs it.)
 //   gram      G = Fh_T^T Fh_T - Fh_S^T Fh_S accumulated in ONE set of fp32 MFMA accumulators
 //             (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate -- there is no
-//             TF32/xf32 on gfx950 and bf16 would break the 1e-4 loss tolerance).  128x128 output
+//             TF32/xf32 on gfx950 and PLAIN bf16 operands would break the 1e-4 loss tolerance; the
+//             three-piece bf16 split does not: pairwise_split.hip is this product and the backward's
+//             on the split core, opt-in, include/skd_pairwise_split.h).  128x128 output
 //             tile per 256-thread workgroup, 4 waves x (2x2) 32x32 MFMA tiles, K streamed through
 //             a double-buffered LDS ring of k-major panels; both operands are rows of the same
 //             channel-major matrix, so LDS reads are conflict-free ds_read_b32 with no transposes.

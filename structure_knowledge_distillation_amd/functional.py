@@ -1727,7 +1727,7 @@ class _PairWise(Function):
     layout its feature had."""
 
     @staticmethod
-    def forward(ctx, feat_s, feat_t, kh, kw):
+    def forward(ctx, feat_s, feat_t, kh, kw, split=False):
         _lib.require_device(feat_s, feat_t)
         for t in (feat_s, feat_t):
             if t.dtype != torch.float32:
@@ -1757,6 +1757,8 @@ class _PairWise(Function):
             ctx.save_for_backward(dp, index)
             return loss
         ctx.small = False
+        # the two matrix products on the split core (include/skd_pairwise_split.h)?  Decided once, here: the backward follows
+        ctx.split = bool(split) and pairwise_split_supported() and (cs, ct, m) not in PAIRWISE_SPLIT_ROUTING_EXCLUDED
         ldm = lib.skd_pairwise_ldm(m)
         p_s = feat_s.new_empty((b, cs, m))
         p_t = feat_s.new_empty((b, ct, m))
@@ -1773,10 +1775,16 @@ class _PairWise(Function):
                                                 None, 0, None, st), "skd_channel_l2_normalise")
         g = feat_s.new_empty((b, ldm, ldm)) if need else None
         loss = feat_s.new_empty(())
-        ws = feat_s.new_empty((max(1, lib.skd_pairwise_workspace_floats(b, m)),))
-        _lib.check(lib.skd_pairwise_gram_loss(b, cs, ct, m, ldm, fh_s.data_ptr(), fh_t.data_ptr(),
-                                              _lib.ptr(g), loss.data_ptr(), ws.data_ptr(), st),
-                   "skd_pairwise_gram_loss")
+        if ctx.split:
+            ws = feat_s.new_empty((max(1, lib.skd_pairwise_split_workspace_floats(b, cs, ct, m)),))
+            _lib.check(lib.skd_pairwise_split_gram_loss(b, cs, ct, m, ldm, fh_s.data_ptr(), fh_t.data_ptr(),
+                                                        _lib.ptr(g), loss.data_ptr(), ws.data_ptr(), st),
+                       "skd_pairwise_split_gram_loss")
+        else:
+            ws = feat_s.new_empty((max(1, lib.skd_pairwise_workspace_floats(b, m)),))
+            _lib.check(lib.skd_pairwise_gram_loss(b, cs, ct, m, ldm, fh_s.data_ptr(), fh_t.data_ptr(),
+                                                  _lib.ptr(g), loss.data_ptr(), ws.data_ptr(), st),
+                       "skd_pairwise_gram_loss")
         ctx.geom = (b, cs, h, w, kh, kw, m, ldm, 0)
         ctx.save_for_backward(fh_s if need else None, g, norm_s, index)
         return loss
@@ -1787,28 +1795,51 @@ class _PairWise(Function):
         if ctx.small:
             dp, index = ctx.saved_tensors
             if dp is None:
-                return None, None, None, None
+                return None, None, None, None, None
             b, cs, h, w, kh, kw, m, _, _ = ctx.geom
             lib, st = _lib.get(), _lib.stream_of(dp)
             dpg = dp * gl.to(torch.float32)
-            return _unpool_feature(lib, ctx.nhwc, (b, cs, h, w, kh, kw), dpg, m, index, st), None, None, None
+            return _unpool_feature(lib, ctx.nhwc, (b, cs, h, w, kh, kw), dpg, m, index, st), None, None, None, None
         fh_s, g, norm_s, index = ctx.saved_tensors
         if g is None:
-            return None, None, None, None
+            return None, None, None, None, None
         b, cs, h, w, kh, kw, m, ldm, _ = ctx.geom
         lib, st = _lib.get(), _lib.stream_of(g)
         gl = gl.to(torch.float32).contiguous()
         dp = g.new_empty((b, cs, ldm))
-        ws = g.new_empty((max(1, lib.skd_pairwise_backward_workspace_floats(b, cs, m)),))
-        _lib.check(lib.skd_pairwise_backward(b, cs, m, ldm, fh_s.data_ptr(), g.data_ptr(),
-                                             norm_s.data_ptr(), gl.data_ptr(), dp.data_ptr(), ws.data_ptr(), st),
-                   "skd_pairwise_backward")
-        return _unpool_feature(lib, ctx.nhwc, (b, cs, h, w, kh, kw), dp, ldm, index, st), None, None, None
+        if ctx.split:
+            ws = g.new_empty((max(1, lib.skd_pairwise_split_backward_workspace_floats(b, cs, m)),))
+            _lib.check(lib.skd_pairwise_split_backward(b, cs, m, ldm, fh_s.data_ptr(), g.data_ptr(),
+                                                       norm_s.data_ptr(), gl.data_ptr(), dp.data_ptr(), ws.data_ptr(), st),
+                       "skd_pairwise_split_backward")
+        else:
+            ws = g.new_empty((max(1, lib.skd_pairwise_backward_workspace_floats(b, cs, m)),))
+            _lib.check(lib.skd_pairwise_backward(b, cs, m, ldm, fh_s.data_ptr(), g.data_ptr(),
+                                                 norm_s.data_ptr(), gl.data_ptr(), dp.data_ptr(), ws.data_ptr(), st),
+                       "skd_pairwise_backward")
+        return _unpool_feature(lib, ctx.nhwc, (b, cs, h, w, kh, kw), dp, ldm, index, st), None, None, None, None
 
 
-def pair_wise_loss(feat_s, feat_t, kh, kw):
-    """CriterionPairWiseforWholeFeatAfterPool.forward on raw (B,C,H,W) features, criterion.py:236-245."""
-    return _PairWise.apply(feat_s, feat_t.detach(), int(kh), int(kw))
+# (Cs, Ct, M) of the pair-wise loss that stay on the fp32 kernels whatever `split` says: the measured shapes whose split forward +
+# backward are not ahead of the fp32 pair (profiles/r29_pairwise_split_isolated.md has the table and the rule).
+PAIRWISE_SPLIT_ROUTING_EXCLUDED = frozenset()
+
+_PAIRWISE_SPLIT_ENTRIES = ("skd_pairwise_split_workspace_floats", "skd_pairwise_split_gram_loss",
+                           "skd_pairwise_split_backward_workspace_floats", "skd_pairwise_split_backward")
+
+
+def pairwise_split_supported():
+    """Whether the active back-end has the entries of include/skd_pairwise_split.h (the plain-C double has not: not an error)."""
+    return all(_lib.has_entry(n) for n in _PAIRWISE_SPLIT_ENTRIES)
+
+
+def pair_wise_loss(feat_s, feat_t, kh, kw, split=False):
+    """CriterionPairWiseforWholeFeatAfterPool.forward on raw (B,C,H,W) features, criterion.py:236-245.
+
+    ``split=True``: for graphs of more than 64 nodes the Gram + loss and the backward product run on the split bf16-MFMA core
+    (include/skd_pairwise_split.h) where the back-end has the entries and (Cs, Ct, M) is not in PAIRWISE_SPLIT_ROUTING_EXCLUDED;
+    everything else -- pooling, normalising, the small-graph kernel, the unpool -- is what it is without it."""
+    return _PairWise.apply(feat_s, feat_t.detach(), int(kh), int(kw), bool(split))
 
 
 class _SpectralNormalize(Function):

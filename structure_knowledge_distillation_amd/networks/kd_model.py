@@ -27,6 +27,7 @@ import torch.nn as nn  # noqa: F401
 import torch.optim as optim
 
 from .. import _lib
+from ..functional import pairwise_split_supported
 from ..utils import parallel as parallel_old
 from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
@@ -247,8 +248,15 @@ class NetModel():
         else:
             self.criterion = self.DataParallelCriterionProcess(CriterionDSN())
         self.criterion_pixel_wise = self.DataParallelCriterionProcess(CriterionPixelWise())
+        # args.split_pairwise (SWITCHES): the pair-wise loss's two matrix products on the split core.  A back-end without the entries
+        # keeps the fp32 kernels and says so once, here, as set_teacher_pieces does
+        if self.split_pairwise and not pairwise_split_supported():
+            import warnings
+            warnings.warn("split_pairwise: this back-end lacks the split pair-wise entries (include/skd_pairwise_split.h); the "
+                          "pair-wise loss stays on the fp32 kernels", RuntimeWarning, stacklevel=2)
+            self.split_pairwise = False
         self.criterion_pair_wise_for_interfeat = self.DataParallelCriterionProcess(
-            CriterionPairWiseforWholeFeatAfterPool(scale=args.pool_scale, feat_ind=-5))
+            CriterionPairWiseforWholeFeatAfterPool(scale=args.pool_scale, feat_ind=-5, split=self.split_pairwise))
         self.criterion_adv = self.DataParallelCriterionProcess(CriterionAdv(args.adv_loss_type))
         if args.adv_loss_type == "wgan-gp":
             self.criterion_AdditionalGP = self.DataParallelCriterionProcess(
@@ -835,7 +843,7 @@ def advance_versions_after_step(optimizer, args=None, kwargs=None):
         torch.autograd.graph.increment_version(written)      # one host call for all of them
 
 
-# The eight boolean opt-in switches of the split core: (attribute of ``args`` and of NetModel, environment variable read where the
+# The nine boolean opt-in switches of the split core: (attribute of ``args`` and of NetModel, environment variable read where the
 # attribute is None -- the way to A/B the step without another flag -- default "0", the switches it is effective only together
 # with).  All off by default.
 SWITCHES = (
@@ -868,6 +876,10 @@ SWITCHES = (
     # stride 2) on the split core instead of the library (pspnet_combine.route_teacher_early, include/skd_stride2.h).  The teacher
     # alone; independent of the student's switches (profiles/r27_conv3x3_early_isolated.md, profiles/r27_step_ab.md)
     ("teacher_early", "SKD_TEACHER_EARLY", ()),
+    # the Gram + loss and the backward product of the pair-wise loss on the split core instead of the fp32 MFMA, for pooled graphs
+    # of more than 64 nodes (csrc/pairwise_split.hip, include/skd_pairwise_split.h); the default pool_scale pools to 9 nodes and
+    # routes nothing.  Independent of the other switches (profiles/r29_pairwise_split_isolated.md, profiles/r29_step_ab.md)
+    ("split_pairwise", "SKD_SPLIT_PAIRWISE", ()),
 )
 
 
@@ -900,7 +912,7 @@ def default_args(**overrides):
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
-        split_bnstats=None, teacher_early=None, split_stride2=None)
+        split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     for name, env, _ in SWITCHES:      # None: the environment switch

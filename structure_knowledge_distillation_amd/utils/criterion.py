@@ -115,19 +115,23 @@ class CriterionPixelWise(nn.Module):
 
 
 class CriterionPairWiseforWholeFeatAfterPool(nn.Module):
-    def __init__(self, scale, feat_ind):
-        """inter pair-wise loss from inter feature maps"""
+    def __init__(self, scale, feat_ind, split=False):
+        """inter pair-wise loss from inter feature maps
+
+        ``split`` (keyword, not in the reference's signature): the two matrix products of graphs with more than 64 nodes on the
+        split bf16-MFMA core (functional.pair_wise_loss)."""
         super().__init__()
         self.criterion = sim_dis_compute
         self.feat_ind = feat_ind
         self.scale = scale
+        self.split = bool(split)
 
     def forward(self, preds_S, preds_T):
         feat_S = preds_S[self.feat_ind]
         feat_T = preds_T[self.feat_ind]
         total_w, total_h = feat_T.shape[2], feat_T.shape[3]
         patch_w, patch_h = int(total_w * self.scale), int(total_h * self.scale)
-        return SF.pair_wise_loss(feat_S.float(), feat_T.float(), patch_w, patch_h)
+        return SF.pair_wise_loss(feat_S.float(), feat_T.float(), patch_w, patch_h, split=self.split)
 
 
 def _check_adv_type(adv_type):
