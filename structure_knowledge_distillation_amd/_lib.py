@@ -286,6 +286,23 @@ PAIRWISE_SPLIT_SIGNATURES = {
     "skd_pairwise_split_backward": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# Entry points declared in include_ext/skd_planes.h (csrc/planes.hip, csrc/conv1x1.hip and csrc/conv3x3.hip with PLANES): piece
+# planes -- an activation map handed from the frozen teacher's split reduce GEMM to its 3x3 convolution as the three bf16 pieces
+# the consumer reads -- extension entries in a table of their own like the thirteen above; their header lives in include_ext/
+# because include/ is closed (tests/test_conv_planes_cpu.py checks header <-> table <-> exported symbols and sweeps the host-only
+# offset map, tests/test_conv_planes_gpu.py holds the guard-band cases).  A back-end without them leaves the teacher's link on
+# fp32 (kd_model warns when the switch asks for them): nothing raises.
+PLANES_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include_ext", "skd_planes.h"))
+PLANES_SIGNATURES = {
+    "skd_planes_supported": (_I, [_I]),
+    "skd_planes_bytes": (_I, [_L, _I, _P]),
+    "skd_planes_offset": (_I, [_L, _I, _L, _I, _I, _P]),
+    "skd_planes_split_nhwc": (_I, [_L, _I, _P, _P, _P]),
+    "skd_planes_join_nhwc": (_I, [_L, _I, _P, _P, _P]),
+    "skd_conv1x1_abn_planes_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _P]),
+    "skd_conv3x3_split_planes_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -317,7 +334,7 @@ def load(path=None):
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
                   WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES,
-                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES, PAIRWISE_SPLIT_SIGNATURES):
+                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES, PAIRWISE_SPLIT_SIGNATURES, PLANES_SIGNATURES):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -13,6 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
+INCLUDE_EXT = os.path.normpath(os.path.join(HERE, "..", "include_ext"))      # headers added since include/ was closed (skd_planes.h)
 LIB_PATH = os.path.join(HERE, "libskd_hip.so")
 STAMP = LIB_PATH + ".stamp"
 ARCH = "gfx950"
@@ -28,6 +29,7 @@ def _digest():
     h = hashlib.sha256()
     files = sources() + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
     files += sorted(os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h"))
+    files += sorted(os.path.join(INCLUDE_EXT, f) for f in os.listdir(INCLUDE_EXT) if f.endswith(".h"))
     for f in files:
         h.update(f.encode())
         with open(f, "rb") as fh:
@@ -49,7 +51,7 @@ def build(force=False, verbose=False):
         with open(STAMP) as fh:
             if fh.read().strip() == digest:
                 return LIB_PATH
-    cmd = [hipcc_path()] + FLAGS + ["-I", INCLUDE, "-I", CSRC] + sources() + ["-o", LIB_PATH]
+    cmd = [hipcc_path()] + FLAGS + ["-I", INCLUDE, "-I", INCLUDE_EXT, "-I", CSRC] + sources() + ["-o", LIB_PATH]
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -46,6 +46,7 @@
 #include <stdlib.h>
 
 #include "conv_split_dev.hpp"
+#include "skd_planes.h"
 #include "skd_split2.h"
 
 namespace skd {
@@ -127,8 +128,46 @@ struct Tile1 {
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, PIECES>(stage, acc); }
 };
 
-// One output tile of TM x 128: K loop through the double-buffered LDS ring, then the epilogue.
-template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3>
+// PLANES (include_ext/skd_planes.h): the epilogue of one 32 x 32 accumulator block that writes the three bf16 pieces of
+// act(bn(acc)) -- store_block's fp32 value, the same expression -- into the piece planes of an (M, N) map (planes_offset,
+// conv_split_dev.hpp) and no fp32 output.  A lane holds one column of sixteen rows, and neighbouring columns' pieces are
+// neighbouring bf16, so lanes l and l ^ 1 trade every other row first: the even lane keeps rows q = 0, 2, ... of both columns, the
+// odd lane rows q = 1, 3, ...; a lane then splits eight column pairs (pack_bf16 on the pair, as split4 does on its quads) and
+// issues 24 dword stores instead of 48 two-byte ones.  The pieces of a value do not depend on its neighbour, so every element is
+// split4's bit for bit.  The exchange runs on every lane; only the stores look at M.
+template <int ACT, bool FULL>
+__device__ __forceinline__ void store_block_planes(const f32x16 &acc, unsigned char *__restrict__ P, int64_t row0, int col,
+                                                   int64_t M, int N, float mu, float is, float ga, float be, float slope) {
+  const int lane = threadIdx.x & (kWave - 1), odd = lane & 1;
+  float z[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    z[q] = ((acc[q] - mu) * is) * ga + be;                    // bn.cu:158-159, as store_block
+    if (ACT == SKD_ACT_RELU) z[q] = z[q] < 0.f ? 0.f : z[q];
+    if (ACT == SKD_ACT_LEAKY_RELU) z[q] = z[q] < 0.f ? z[q] * slope : z[q];
+  }
+#pragma unroll
+  for (int q = 0; q < 16; q += 2) {
+    const float got = __shfl_xor(odd ? z[q] : z[q + 1], 1, kWave);
+    float lo = odd ? got : z[q], hi = odd ? z[q + 1] : got;   // columns col & ~1 and col | 1 of row q (even lane) / q + 1 (odd lane)
+    const int qq = q + odd;
+    const int64_t row = row0 + (qq & 3) + 8 * (qq >> 2) + 4 * (lane >> 5);
+    const uint32_t p0 = pack_bf16(lo, hi);
+    lo -= bf16_lo(p0); hi -= bf16_hi(p0);
+    const uint32_t p1 = pack_bf16(lo, hi);
+    lo -= bf16_lo(p1); hi -= bf16_hi(p1);
+    const uint32_t p2 = pack_bf16(lo, hi);
+    if (FULL || row < M) {
+      *reinterpret_cast<uint32_t *>(P + planes_offset(M, N, row, col & ~1, 0)) = p0;
+      *reinterpret_cast<uint32_t *>(P + planes_offset(M, N, row, col & ~1, 1)) = p1;
+      *reinterpret_cast<uint32_t *>(P + planes_offset(M, N, row, col & ~1, 2)) = p2;
+    }
+  }
+}
+
+// One output tile of TM x 128: K loop through the double-buffered LDS ring, then the epilogue.  PLANES: Y is the piece-plane
+// allocation of the (M, N) output and the epilogue is store_block_planes (no residual, no prologue, three pieces).
+template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false>
 __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R,
                                              float *__restrict__ Y, const float *__restrict__ mean, const float *__restrict__ var,
                                              const float *__restrict__ weight, const float *__restrict__ bias,
@@ -174,7 +213,11 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
 #pragma unroll
     for (int bi = 0; bi < WM; ++bi) {
       const int64_t row0 = m0 + wi + bi * 32;
-      if (full)
+      if constexpr (PLANES) {
+        unsigned char *P = reinterpret_cast<unsigned char *>(Y);
+        if (full) store_block_planes<ACT, true>(acc[bi][bj], P, row0, col, M, N, mu, is, ga, be, slope);
+        else store_block_planes<ACT, false>(acc[bi][bj], P, row0, col, M, N, mu, is, ga, be, slope);
+      } else if (full)
         store_block<ACT, HAS_RES, true, NT>(acc[bi][bj], R, Y, row0, col, M, N, mu, is, ga, be, slope);
       else
         store_block<ACT, HAS_RES, false, NT>(acc[bi][bj], R, Y, row0, col, M, N, mu, is, ga, be, slope);
@@ -246,12 +289,14 @@ __host__ __device__ __forceinline__ TileOf conv1x1_tile_of(unsigned block, int64
 
 // PIECES = 2 (include/skd_split2.h): two pieces per operand, the three products a0 b1, a1 b0, a0 b0 into the one accumulator; the
 // grid, the tile order and the half-height round are those of the three-piece launch (32 KB of LDS + the prologue's table).
-template <int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3>
+// PLANES (include_ext/skd_planes.h): Y is the piece planes of the output (conv1x1_tile); grid and tile order as the fp32 launch.
+template <int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false>
 __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
     const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R, float *__restrict__ Y,
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
     const float *__restrict__ bias, const float *__restrict__ ppack, float eps, float slope, int64_t M, int K, int N,
     int tiles_n, int pm, int ct, int p_full) {
+  static_assert(!PLANES || (!HAS_RES && !PRO && !NT && PIECES == 3), "planes out: the plain three-piece GEMM, plain stores");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   // XCD-aware tile order.  Workgroup b runs on XCD b % 8 (observed placement, MI355X_MICROARCH.md; used for traffic only, any
   // placement is correct) and every XCD has its own L2: the tiles_n workgroups that share one 128 x K activation panel are
@@ -275,9 +320,9 @@ __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
   // workgroups of half the duration fill the last round's slots (p_full is a multiple of 8: whole XCD rows).
   const TileOf t = conv1x1_tile_of(blockIdx.x, M, tiles_n, pm, ct, p_full);
   if (t.rows == kTM)
-    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT, PIECES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT, PIECES, PLANES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
   else if (t.rows == kTM / 2)
-    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT, PIECES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT, PIECES, PLANES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
 }
 
 __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, const float *__restrict__ var,
@@ -291,7 +336,9 @@ __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, c
   pack[3 * (int64_t)K + k] = bias != nullptr ? bias[k] : 0.f;
 }
 
-template <int ACT, bool HAS_RES, bool PRO, int PIECES = 3, bool NT = false>
+// PLANES: Y is the piece planes; the tile order is the geometry's (the super-tile order of a wide output included) but the stores
+// are plain, never non-temporal -- the planes are read by the next launch -- so the one instantiation NT = false serves.
+template <int ACT, bool HAS_RES, bool PRO, int PIECES = 3, bool NT = false, bool PLANES = false>
 static int launch(const float *X, const float *Wt, const float *R, float *Y, const float *mean, const float *var,
                   const float *weight, const float *bias, const float *ppack, float eps, float slope, int64_t M, int K, int N,
                   hipStream_t st) {
@@ -299,15 +346,15 @@ static int launch(const float *X, const float *Wt, const float *R, float *Y, con
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES, PLANES>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(conv_lds(PIECES) + sizeof(float) * 4 * kProMaxK)) != hipSuccess) return 0;
     *rdy = true;
   }
   const size_t lds_bytes = conv_lds(PIECES) + (PRO ? sizeof(float) * 4 * (size_t)K : 0);
   Geometry g;
   if (!conv1x1_geometry(M, K, N, cu_count(st), g)) return 0;
-  if (g.nt && !NT) return launch<ACT, HAS_RES, PRO, PIECES, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
-  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
+  if (g.nt && !NT && !PLANES) return launch<ACT, HAS_RES, PRO, PIECES, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
+  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES, PLANES><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
       X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, g.tiles_n, g.pm, g.ct, (int)g.p_full);
   return ok();
 }
@@ -403,6 +450,25 @@ int skd_conv1x1_abn2_nhwc(int64_t M, int K, int N, const float *x, const float *
                           const float *mean, const float *var, const float *weight, const float *bias, float eps,
                           int activation, float slope, skd_stream_t stream) {
   return conv1x1_dispatch<2>(M, K, N, x, w, residual, out, mean, var, weight, bias, nullptr, eps, activation, slope, stream);
+}
+
+// include_ext/skd_planes.h: the plain three-piece GEMM with the pieces of its epilogue's value written to piece planes.
+int skd_conv1x1_abn_planes_nhwc(int64_t M, int K, int N, const float *x, const float *w, void *planes_out, const float *mean,
+                                const float *var, const float *weight, const float *bias, float eps, int activation, float slope,
+                                skd_stream_t stream) {
+  if (!skd_conv1x1_abn_supported(M, K, N) || !x || !w || !planes_out || !mean || !var) return 0;
+  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(planes_out)) & 15) return 0;
+  hipStream_t st = as_stream(stream);
+  float *y = static_cast<float *>(planes_out);
+#define SKD_C11P(A) \
+  case A: return launch<A, false, false, 3, false, true>(x, w, nullptr, y, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st)
+  switch (activation) {
+    SKD_C11P(SKD_ACT_NONE);
+    SKD_C11P(SKD_ACT_RELU);
+    SKD_C11P(SKD_ACT_LEAKY_RELU);
+    default: return 0;
+  }
+#undef SKD_C11P
 }
 
 int skd_conv1x1_abn2_pro_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,

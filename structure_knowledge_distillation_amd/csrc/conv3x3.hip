@@ -43,6 +43,7 @@
 #include "skd_bnstats.h"
 #include "skd_infer.h"
 #include "skd_narrow.h"
+#include "skd_planes.h"
 #include "skd_split2.h"
 #include "skd_stride2.h"
 #include "skd_train.h"
@@ -68,10 +69,22 @@ constexpr size_t conv3x3_lds(int TN, int PIECES = 3) {
 static_assert(conv3x3_lds(kTN) == kConvLds, "the 128-column form fills both stages");
 static_assert(conv3x3_lds(kTN, 2) == conv_lds(2) && tile_chunks(kTN, 2) == 2 * kThreads, "... of two pieces too: 32 KB, two copies");
 
-template <int TM, int TN, int PIECES = 3>
+// One panel row's four k of a K-tile in the staging registers: the fp32 quad that stage_store3 splits, or -- PLANES
+// (include_ext/skd_planes.h): the activation is the piece planes of the map -- its three 8-byte piece quads, ready to store: two
+// registers more per panel row and staging set, four per 64 rows of the tile over k_loop's two sets.
+// (Native vector types, one array per piece: with HIP's uint2 / uint4 structs in this set the copies of the first weight chunk
+// stayed memcpys and the set in scratch, 56 bytes per lane.)
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+template <int TM, int TN, int PIECES = 3, bool PLANES = false>
 struct Staging3 {
   float4 a[TM / kRPP];
   uint4 b[b_copies(TN, PIECES)];
+};
+template <int TM, int TN, int PIECES>
+struct Staging3<TM, TN, PIECES, true> {
+  u32x2 a0[TM / kRPP], a1[TM / kRPP], a2[TM / kRPP];
+  u32x4 b[b_copies(TN, PIECES)];
 };
 
 struct TapCursor {      // the K-tile being staged: tap 0..8, first channel c0, and the tap's address shift in floats
@@ -85,42 +98,80 @@ __device__ __forceinline__ int64_t tap_shift(int tap, int W, int dil, int Cin) {
 }
 
 // The packed weights: every lane loads its chunks (a copy that does not exist stages zeros, which nothing stores).
-template <int TM, int TN, int PIECES>
-__device__ __forceinline__ void stage_load3_b(Staging3<TM, TN, PIECES> &s, const uint4 *__restrict__ bsrc) {
+template <int TM, int TN, int PIECES, bool PLANES>
+__device__ __forceinline__ void stage_load3_b(Staging3<TM, TN, PIECES, PLANES> &s, const uint4 *__restrict__ bsrc) {
 #pragma unroll
   for (int i = 0; i < b_copies(TN, PIECES); ++i) {
-    s.b[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (b_copy_live<TN, PIECES>(i)) s.b[i] = bsrc[i * kThreads];
+    if constexpr (PLANES) {
+      s.b[i] = u32x4{0u, 0u, 0u, 0u};
+      if (b_copy_live<TN, PIECES>(i)) s.b[i] = reinterpret_cast<const u32x4 *>(bsrc)[i * kThreads];
+    } else {
+      s.b[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (b_copy_live<TN, PIECES>(i)) s.b[i] = bsrc[i * kThreads];
+    }
   }
 }
 // The activations: a lane whose tap is outside the image issues no load and stages an exact zero.
 template <int TM, int TN, int PIECES>
-__device__ __forceinline__ void stage_load3_a(Staging3<TM, TN, PIECES> &s, const float *__restrict__ X, const TapCursor &cur,
-                                              const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP]) {
+__device__ __forceinline__ void stage_load3_a(Staging3<TM, TN, PIECES, false> &s, const float *__restrict__ X, const TapCursor &cur,
+                                              const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP], int) {
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) {
     s.a[h] = make_float4(0.f, 0.f, 0.f, 0.f);
     if ((mask[h] >> cur.tap) & 1u) s.a[h] = *reinterpret_cast<const float4 *>(X + abase[h] + cur.shift + cur.c0);
   }
 }
-
+// PLANES: X is the piece planes, abase[h] the BYTE offset of (the row's pixel, the thread's k quad, piece 0) and the cursor's
+// shift + c0 -- a multiple of 16 channels, negative for the upper taps -- goes through planes_offset as the channel: the map is
+// affine in it (conv_split_dev.hpp).  Three 8-byte loads in the source, adjacent in the committed layout (the compiler issues a
+// 16-byte and an 8-byte one); a masked tap stages zeros in all three pieces, which is what split4 makes of the fp32 zero the other
+// form stages.
 template <int TM, int TN, int PIECES>
-__device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES> &s, uint4 *stage, int srow) {
+__device__ __forceinline__ void stage_load3_a(Staging3<TM, TN, PIECES, true> &s, const float *__restrict__ X, const TapCursor &cur,
+                                              const int64_t (&abase)[TM / kRPP], const unsigned (&mask)[TM / kRPP], int Cin) {
+  static_assert(PIECES == 3, "piece planes hold three pieces");
+  const unsigned char *P = reinterpret_cast<const unsigned char *>(X);
+#pragma unroll
+  for (int h = 0; h < TM / kRPP; ++h) {
+    s.a0[h] = s.a1[h] = s.a2[h] = u32x2{0u, 0u};
+    if ((mask[h] >> cur.tap) & 1u) {
+      const unsigned char *src = P + abase[h];
+      s.a0[h] = *reinterpret_cast<const u32x2 *>(src + planes_offset(0, Cin, 0, cur.shift + cur.c0, 0));
+      s.a1[h] = *reinterpret_cast<const u32x2 *>(src + planes_offset(0, Cin, 0, cur.shift + cur.c0, 1));
+      s.a2[h] = *reinterpret_cast<const u32x2 *>(src + planes_offset(0, Cin, 0, cur.shift + cur.c0, 2));
+    }
+  }
+}
+
+template <int TM, int TN, int PIECES, bool PLANES>
+__device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLANES> &s, uint4 *stage, int srow) {
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
 #pragma unroll
-  for (int h = 0; h < TM / kRPP; ++h) split_store<PIECES>(s.a[h], sa + 2 * kRPP * h);
+  for (int h = 0; h < TM / kRPP; ++h) {
+    if constexpr (PLANES) {          // the three piece quads into split_store's slots, no split4
+      u32x2 *dst = reinterpret_cast<u32x2 *>(sa + 2 * kRPP * h);
+      dst[0] = s.a0[h];
+      dst[2 * kPlaneChunks] = s.a1[h];
+      dst[4 * kPlaneChunks] = s.a2[h];
+    } else {
+      split_store<PIECES>(s.a[h], sa + 2 * kRPP * h);
+    }
+  }
   uint4 *sb = stage + operand_chunks(PIECES) + threadIdx.x;
 #pragma unroll
   for (int i = 0; i < b_copies(TN, PIECES); ++i)
-    if (b_copy_live<TN, PIECES>(i)) sb[i * kThreads] = s.b[i];
+    if (b_copy_live<TN, PIECES>(i)) {
+      if constexpr (PLANES) reinterpret_cast<u32x4 *>(sb)[i * kThreads] = s.b[i];
+      else sb[i * kThreads] = s.b[i];
+    }
 }
 
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.  k_loop calls load for kt = 0, 1, 2, ... in order, so the
 // cursor is simply stepped behind every one: it runs as far ahead of the MFMAs as the loads do and crosses a tap boundary
 // wherever that falls.  (Behind the last tile it stands at tap 9, which nothing reads.)
-template <int TM, int TN, int PIECES = 3>
+template <int TM, int TN, int PIECES = 3, bool PLANES = false>
 struct Tile3 {
-  typedef Staging3<TM, TN, PIECES> Stg;
+  typedef Staging3<TM, TN, PIECES, PLANES> Stg;
   static constexpr int WM = wave_blocks_m(TM, TN);
   const float *__restrict__ X;
   const uint4 *__restrict__ bsrc;
@@ -130,8 +181,8 @@ struct Tile3 {
   unsigned mask[TM / kRPP];
   f32x16 (&low)[WM][2], (&acc)[WM][2];
   __device__ __forceinline__ void load(Stg &s, int kt) {
-    stage_load3_a<TM, TN, PIECES>(s, X, cur, abase, mask);
-    stage_load3_b<TM, TN, PIECES>(s, bsrc + (int64_t)kt * tile_chunks(TN, PIECES));
+    stage_load3_a<TM, TN, PIECES>(s, X, cur, abase, mask, Cin);
+    stage_load3_b<TM, TN, PIECES, PLANES>(s, bsrc + (int64_t)kt * tile_chunks(TN, PIECES));
     cur.c0 += kBK;
     if (cur.c0 == Cin) {
       cur.c0 = 0;
@@ -139,7 +190,7 @@ struct Tile3 {
       cur.shift = tap_shift(cur.tap, W, dil, Cin);
     }
   }
-  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES>(s, stage, srow); }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES, PLANES>(s, stage, srow); }
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES>(stage, low, acc); }
 };
 
@@ -198,8 +249,10 @@ __device__ __forceinline__ void block_stats(const f32x16 &acc, float *__restrict
 // One output tile of TM x TN pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
 // in front of the activation (store_block): the second convolution of a BasicBlock.  STRIDE = 2: M counts the rows of the
 // (B, Ho, Wo) output, H and W stay the input's, and the rows' addresses and masks come from s2_row_map; STRIDE = 1 is the code
-// without it.
-template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
+// without it.  PLANES (include_ext/skd_planes.h): X is the piece planes of the (M, Cin) input map; the rows' addresses are byte
+// offsets of that layout and the staging set holds piece quads (stage_load3_a, stage_store3); masks, tap cursor, K loop, product order
+// and epilogue are the code without it.
+template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
                                              const float *__restrict__ R, float *__restrict__ stats,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
@@ -243,10 +296,10 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
       if (live && y >= 0 && y < H && x >= 0 && x < W) bits |= 1u << tap;
     }
     mask[h] = bits;
-    abase[h] = mm * Cin + gkq;
+    abase[h] = PLANES ? planes_offset(M, Cin, mm, gkq, 0) : mm * Cin + gkq;
   }
   const uint4 *bsrc = Bp + (int64_t)tn * nk * tile_chunks(TN, PIECES) + gt;
-  Tile3<TM, TN, PIECES> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
+  Tile3<TM, TN, PIECES, PLANES> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
     tile.abase[h] = abase[h];
@@ -295,7 +348,7 @@ constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kM
 
 // PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h); so does
 // STRIDE = 2 (include/skd_stride2.h), whose M is that of the smaller output.
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
@@ -307,6 +360,7 @@ void conv3x3_split_kernel(
   static_assert(!STATS || (ACT == SKD_ACT_NONE && !HAS_RES && PIECES == 3), "statistics: the training forward's raw epilogue alone");
   static_assert(PIECES == 3 || (TN == kTN && !HAS_RES), "two pieces: the 128-column forward family without the residual");
   static_assert(STRIDE == 1 || (STRIDE == 2 && TN == kTN && !HAS_RES && !STATS), "stride 2: the 128-column frozen forward alone");
+  static_assert(!PLANES || (TN == kTN && PIECES == 3 && !HAS_RES && !STATS && STRIDE == 1), "piece planes in: the wide stride-1 frozen forward alone");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -314,11 +368,11 @@ void conv3x3_split_kernel(
   if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -360,7 +414,7 @@ __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
   for (int p = 0; p < PIECES; ++p) pack[(tile * PIECES + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                    int geometry, hipStream_t st, float *stats = nullptr) {
@@ -368,7 +422,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN, PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
@@ -384,7 +438,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
       X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R, stats);
   return ok();
 }
@@ -395,7 +449,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
 // TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
-template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1>
+template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st, float *stats = nullptr) {
@@ -404,8 +458,8 @@ static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, c
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
-      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
-    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
   }
 }
 
@@ -482,6 +536,32 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
     default: return 0;
   }
 #undef SKD_CONV3X3_CASE
+}
+
+// include_ext/skd_planes.h: run3<kTN> without residual whose activation operand is the piece planes of the (B, H, W, Cin) map --
+// run3's refusals, the planes pointer in x's place (16-byte aligned, as x).
+static int run3_planes(int B, int H, int W, int Cin, int Cout, int dilation, const void *planes, const void *wpack, float *out,
+                       const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                       float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+  if (!supported3<kTN>(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
+  if (!planes || !wpack || !out || (mean == nullptr) != (var == nullptr) || geometry < 0 || geometry > 3) return 0;
+  if ((reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(wpack)) & 15) return 0;
+  if ((int64_t)H * W > 2147483647 || dilation > (1 << 24)) return 0;
+  const int64_t M = (int64_t)B * H * W;
+  hipStream_t st = as_stream(stream);
+  const float *x = static_cast<const float *>(planes);
+  const uint4 *bp = static_cast<const uint4 *>(wpack);
+#define SKD_CONV3X3_PLANES_CASE(ACT)                                                                                          \
+  case ACT:                                                                                                                   \
+    return launch3g<kTN, ACT, false, 3, false, 1, true>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, \
+                                                        Cin, Cout, dilation, geometry, st)
+  switch (activation) {
+    SKD_CONV3X3_PLANES_CASE(SKD_ACT_NONE);
+    SKD_CONV3X3_PLANES_CASE(SKD_ACT_RELU);
+    SKD_CONV3X3_PLANES_CASE(SKD_ACT_LEAKY_RELU);
+    default: return 0;
+  }
+#undef SKD_CONV3X3_PLANES_CASE
 }
 
 // include/skd_bnstats.h: floats of the statistics workspace of an (M, Cout) output -- one (mean, M2) per 32-row block and
@@ -637,6 +717,15 @@ int skd_conv3x3_narrow_stats_nhwc(int B, int H, int W, int Cin, int Cout, int di
                                   float *out, const float *conv_bias, int geometry, float *stats, int64_t stats_floats,
                                   skd_stream_t stream) {
   return run3_stats<kNarrowTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, conv_bias, geometry, 1, stats, stats_floats, stream);
+}
+
+// include_ext/skd_planes.h: the wide stride-1 frozen forward on the piece planes of its input.
+int skd_conv3x3_split_planes_nhwc(int B, int H, int W, int Cin, int Cout, const void *planes_in, const void *wpack, float *out,
+                                  const float *conv_bias, const float *mean, const float *var, const float *weight,
+                                  const float *bias, float eps, int activation, float slope, int dilation, int geometry,
+                                  skd_stream_t stream) {
+  return run3_planes(B, H, W, Cin, Cout, dilation, planes_in, wpack, out, conv_bias, mean, var, weight, bias, eps, activation, slope,
+                     geometry, stream);
 }
 
 // include/skd_stride2.h: the stride-2 frozen forward of the 128-column family.

@@ -84,6 +84,22 @@ __device__ __forceinline__ void split_store(float4 v, uint2 *dst, int plane) {
   dst[2 * plane] = p2;
 }
 
+// PIECE PLANES (include_ext/skd_planes.h): an (M, C) fp32 activation map stored as its three bf16 pieces, C % 16 == 0, so that a
+// consumer stages a K-tile without split4.  THE layout, the one function every kernel and the host entry skd_planes_offset use:
+// byte offset of piece `piece` of element (row, channel c).  Interleaved per QUAD of four channels: a row's four consecutive k
+// are 24 contiguous bytes (piece 0 | piece 1 | piece 2, 8 bytes each), a row's quads follow each other, rows follow each other:
+// 6 C bytes per row, 6 M C in all, no padding (so M does not enter the map).  A thread of the K loop owns exactly one quad of a
+// row: its three pieces are one 16-byte and one 8-byte load at 8-byte alignment, and the four threads of a row read the K-tile's
+// 96 bytes.  (Interleaved per K-tile -- 32 bytes of each piece, three separate loads per thread -- measured no better:
+// profiles/r31_planes_isolated.md.)
+// The map is affine in row * C + (c rounded down to 4), so it is also defined for a `c` outside 0 .. C - 1 that is a multiple of
+// 4 (channel c + C of a row is channel c of the next row); conv3x3.hip steps its tap cursor that way.
+__host__ __device__ inline int64_t planes_offset(int64_t M, int C, int64_t row, int64_t c, int piece) {
+  (void)M;
+  return (row * C + (c & ~(int64_t)3)) * 6 + piece * 8 + (c & 3) * 2;
+}
+constexpr int64_t planes_bytes(int64_t M, int C) { return M * C * 6; }
+
 // 8-byte slot, in uint2 units, of (row `row` < 64 + what the caller adds, k quad `gkq` = 0, 4, 8, 12) inside a plane; rows 64
 // apart are 128 slots apart.
 __device__ __forceinline__ int plane_slot(int row, int gkq) {

@@ -698,6 +698,103 @@ def _need_split2_entry(name):
         raise NotImplementedError("the active back-end does not provide %s (include/skd_split2.h)" % name)
 
 
+# include_ext/skd_planes.h: piece planes -- an activation map as the three bf16 pieces the split core's consumer reads
+_PLANES_PRODUCER, _PLANES_CONSUMER = "skd_conv1x1_abn_planes_nhwc", "skd_conv3x3_split_planes_nhwc"
+_PLANES_ENTRIES = ("skd_planes_supported", "skd_planes_bytes", "skd_planes_offset", "skd_planes_split_nhwc", "skd_planes_join_nhwc",
+                   _PLANES_PRODUCER, _PLANES_CONSUMER)
+
+
+def planes_supported():
+    """True when the active back-end has the seven entries of include_ext/skd_planes.h (the tests' plain-C double has none)."""
+    return all(_lib.has_entry(n) for n in _PLANES_ENTRIES)
+
+
+def _need_planes():
+    if not planes_supported():
+        raise NotImplementedError("the active back-end does not provide the entries of include_ext/skd_planes.h")
+
+
+class Planes:
+    """The piece planes of a (B, C, H, W) fp32 channels-last map (include_ext/skd_planes.h): ``data``, the byte tensor of
+    skd_planes_bytes(M, C) bytes in the layout of skd_planes_offset; ``M`` = B * H * W rows, ``C`` channels, ``shape`` =
+    (B, H, W, C).  Made by ``conv1x1_abn_planes_eval`` or ``planes_split``, read by ``conv3x3_split_eval`` in place
+    of ``x`` and by ``planes_join``.  Holds exactly the bf16 pieces the consumer would cut from the fp32 map itself."""
+
+    __slots__ = ("data", "M", "C", "shape")
+
+    def __init__(self, data, M, C, shape):
+        self.data, self.M, self.C, self.shape = data, int(M), int(C), tuple(int(v) for v in shape)
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def requires_grad(self):
+        return False
+
+
+def planes_bytes(m, c):
+    """skd_planes_bytes(m, c): the allocation size of the planes of an (m, c) map; ValueError for sizes the kernels refuse."""
+    _need_planes()
+    n = ctypes.c_int64(0)
+    if not _lib.get().skd_planes_bytes(int(m), int(c), ctypes.cast(ctypes.byref(n), ctypes.c_void_p)):
+        raise ValueError("piece planes: unsupported map of %d rows x %d channels (channels: a multiple of 16)" % (m, c))
+    return int(n.value)
+
+
+def _new_planes(ref, b, h, w, c):
+    """An uninitialised Planes for a (b, c, h, w) map on ``ref``'s device, allocated through torch (so it lives on the current
+    stream and inside a graph capture's pool like every other temporary)."""
+    m = b * h * w
+    return Planes(torch.empty((planes_bytes(m, c),), dtype=torch.uint8, device=ref.device), m, c, (b, h, w, c))
+
+
+def planes_split(x):
+    """The piece planes of the fp32 channels-last map ``x`` (B, C, H, W), by the stand-alone kernel skd_planes_split_nhwc: for a
+    map no producer wrote."""
+    _need_planes()
+    _lib.require_device(x)
+    if not _fp32_cl_map(x):
+        raise ValueError("planes_split: an fp32 channels-last map is required")
+    b, c, h, w = x.shape
+    out = _new_planes(x, b, h, w, c)
+    _lib.check(_lib.get().skd_planes_split_nhwc(out.M, c, x.data_ptr(), out.data.data_ptr(), _lib.stream_of(x)), "skd_planes_split_nhwc")
+    return out
+
+
+def planes_join(planes):
+    """The fp32 channels-last map (B, C, H, W) whose pieces ``planes`` holds, (p0 + p1) + p2: a debugging and test aid."""
+    _need_planes()
+    b, h, w, c = planes.shape
+    out = _new_cl(planes.data, b, c, h, w)
+    _lib.check(_lib.get().skd_planes_join_nhwc(planes.M, c, planes.data.data_ptr(), out.data_ptr(), _lib.stream_of(planes.data)),
+               "skd_planes_join_nhwc")
+    return out
+
+
+def conv1x1_abn_planes_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01):
+    """``conv1x1_abn_eval(...)`` -- three pieces, no residual, no ``pro`` -- with the result returned as a ``Planes``
+    (include_ext/skd_planes.h): the three bf16 pieces of the very fp32 values that call would return, written by the GEMM's epilogue
+    (skd_conv1x1_abn_planes_nhwc) for ``conv3x3_split_eval`` to read in place of ``x``; no fp32 tensor is written.  (An op of its
+    own and not a keyword of conv1x1_abn_eval: that op's bound arguments are what tests/golden/routing_census.json records call by
+    call.)  Inference only; a back-end without the entries raises."""
+    if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
+        raise RuntimeError("conv1x1_abn_planes_eval is inference-only")
+    _need_planes()
+    _lib.require_device(x, conv_weight, running_mean, running_var, weight, bias)
+    b, k, h, w = x.shape
+    n = conv_weight.shape[0]
+    wt = conv_weight.reshape(n, k)      # (N, K, 1, 1): the same memory in NCHW and channels-last
+    if not wt.is_contiguous():
+        wt = wt.contiguous()
+    out = _new_planes(x, b, h, w, n)
+    _lib.check(getattr(_lib.get(), _PLANES_PRODUCER)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), out.data.data_ptr(),
+                                                     running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
+                                                     float(eps), _ACT[activation], float(slope), _lib.stream_of(x)), _PLANES_PRODUCER)
+    return out
+
+
 def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
                      residual=None, pro=None, pieces=3):
     """act(bn_running(conv1x1(x)) [+ residual]) as ONE GEMM with the normalisation in its epilogue (inference only;
@@ -712,7 +809,8 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
     ``pieces`` = 2: the reduced-precision form of include/skd_split2.h -- two bf16 pieces per operand and the three products
     a0 b1, a1 b0, a0 b0: about 4e-6 of the output's largest magnitude per product instead of 3e-7 (tests/split2_ref.py is its model,
     tests/test_split2_gpu.py the comparison; profiles/r25_split2_accuracy.md); a back-end without the entries raises, the call is
-    never downgraded."""
+    never downgraded.  ``conv1x1_abn_planes_eval`` is the same GEMM with its result written as bf16 piece planes
+    (include_ext/skd_planes.h)."""
     pieces = _check_pieces(pieces)
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
         raise RuntimeError("conv1x1_abn_eval is inference-only")
@@ -905,6 +1003,28 @@ def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, act
     return out
 
 
+def _conv3x3_planes_launch(planes, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0):
+    """_conv3x3_launch for skd_conv3x3_split_planes_nhwc (include_ext/skd_planes.h): the input is a ``Planes``; the entry takes
+    dilation and geometry behind the epilogue arguments."""
+    lib = _lib.get()
+    b, h, w, cin = planes.shape
+    if pack.numel() != lib.skd_conv3x3_split_pack_bytes(cin, cout):
+        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (_PLANES_CONSUMER, cout, cin))
+    if planes.data.numel() != planes_bytes(planes.M, cin) or planes.M != b * h * w:
+        raise ValueError("%s: the planes are not those of a %s map" % (_PLANES_CONSUMER, (planes.shape,)))
+    mean = var = gamma = beta = None
+    eps, slope = 0.0, 0.01
+    if bn is not None:
+        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
+    _lib.require_device(planes.data, pack, conv_bias, mean, var, gamma, beta)
+    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=planes.device, memory_format=torch.channels_last)
+    _lib.check(getattr(lib, _PLANES_CONSUMER)(b, h, w, cin, cout, planes.data.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                              _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                              _ACT[activation], slope, int(dilation), int(geometry), _lib.stream_of(planes.data)),
+               _PLANES_CONSUMER)
+    return out
+
+
 def _residual_cl(x, cout, residual):
     """The residual of a split-core 3x3 launch on ``x`` with ``cout`` output channels: None, or a (B, cout, H, W) fp32 tensor,
     returned in channels-last memory (copied when it is not)."""
@@ -925,8 +1045,15 @@ def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activ
     ``pieces`` = 2: the reduced-precision form of include/skd_split2.h with ``pack = conv3x3_pack_weights(..., pieces=2)`` -- two
     pieces per operand, the products a0 b1, a1 b0, a0 b0: within 2e-5 of its float64 model (tests/split2_ref.py), which itself is
     about 4e-6 of the output's largest magnitude from the exact product (profiles/r25_split2_accuracy.md).  A back-end without the
-    entry raises; the call is never downgraded."""
+    entry raises; the call is never downgraded.
+    ``x`` may be a ``Planes`` (include_ext/skd_planes.h; three pieces only): the kernel loads the pieces instead of cutting the
+    fp32 map (skd_conv3x3_split_planes_nhwc), and the result is bit for bit that of the call on the fp32 map."""
     pieces = _check_pieces(pieces)
+    if isinstance(x, Planes):
+        if pieces != 3:
+            raise ValueError("conv3x3_split_eval: piece planes hold three pieces")
+        _need_planes()
+        return _conv3x3_planes_launch(x, pack, cout, dilation, conv_bias, bn, activation, geometry)
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_split_eval is inference-only")
     if pieces == 2:

@@ -32,8 +32,8 @@ from ..utils import parallel as parallel_old
 from ..utils.criterion import (CriterionAdditionalGP, CriterionAdv, CriterionAdvForG, CriterionDSN, CriterionOhemDSN,
                                CriterionPairWiseforWholeFeatAfterPool, CriterionPixelWise)
 from ..utils.utils import print_model_parm_nums, to_tuple_str  # noqa: F401
-from .pspnet_combine import (BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_teacher_early, route_training_convs,
-                             set_teacher_pieces)
+from .pspnet_combine import (BasicBlock, Bottleneck, Res_pspnet, fuse_for_inference, route_teacher_early, route_teacher_planes,
+                             route_training_convs, set_teacher_pieces)
 from .sagan_models import Discriminator
 
 
@@ -212,6 +212,15 @@ class NetModel():
         # before any warm-up step or teacher-graph capture.
         if self.teacher_early:
             route_teacher_early(teacher)
+        # args.teacher_planes (None: SKD_TEACHER_PLANES, default "0"; handled like teacher_pieces, outside SWITCHES): the teacher's
+        # Bottlenecks hand conv1 -> bn1 -> relu to their 3x3 convolution as bf16 piece planes instead of fp32
+        # (pspnet_combine.route_teacher_planes, include_ext/skd_planes.h) -- bit-identical outputs, a speed feature.  Independent of
+        # every other switch; inert under teacher_pieces = 2 (the planes hold three pieces).  route_teacher_planes warns once on a
+        # back-end without the entries and the teacher keeps its present path.
+        self.teacher_planes = _teacher_planes(getattr(args, "teacher_planes", None))
+        if self.teacher_planes:
+            route_teacher_planes(teacher)
+            self.teacher_planes = any(getattr(m, "_skd_teacher_planes", False) for m in teacher.modules())
 
         D_model = Discriminator(args.preprocess_GAN_mode, args.classes_num, args.batch_size,
                                 args.imsize_for_adv, args.adv_conv_dim)
@@ -898,6 +907,11 @@ def _teacher_pieces(value):
     return int(str(value).strip())
 
 
+def _teacher_planes(value):
+    """``value`` as a bool; None: whether the environment's SKD_TEACHER_PLANES is "1" (default "0")."""
+    return os.environ.get("SKD_TEACHER_PLANES", "0") == "1" if value is None else bool(value)
+
+
 def default_args(**overrides):
     """The flag defaults of utils/train_options.py:18-63 that shape the step, as a namespace
     (``run_train_val.sh`` overrides: weight_decay 5e-4, lambda_pa 0.5)."""
@@ -912,11 +926,12 @@ def default_args(**overrides):
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
-        split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None)
+        split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None, teacher_planes=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     for name, env, _ in SWITCHES:      # None: the environment switch
         if getattr(a, name) is None:
             setattr(a, name, _switch(a, name, env))
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
+    a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include_ext/skd_planes.h)
     return a

@@ -144,6 +144,18 @@ TEACHER_EARLY_ROUTING_EXCLUDED = frozenset()
 # 128) -- runs conv1 -> bn1 -> relu as one launch of the stride-2 form.  A shape that measures behind is listed here as
 # (Cin, Cout) and keeps conv -> forward_relu: none does (64 -> 128 at 257 x 513, batch 1: 3.06 x ahead of convolution + ABN pass).
 STRIDE2_ROUTING_EXCLUDED = frozenset()
+# The frozen teacher's conv1 -> bn1 -> relu -> conv2 link as bf16 PIECE PLANES (route_teacher_planes(model), below; a further
+# opt-in, include_ext/skd_planes.h): a flagged Bottleneck whose conv1 runs on the split reduce GEMM and whose conv2 runs on the
+# wide 3x3 kernel anyway, both on three pieces, has the GEMM's epilogue write the three bf16 pieces of its result and the 3x3
+# load them instead of cutting the fp32 map nine times per output tile -- layer3's 23 blocks and layer4's 3.  The outputs are bit
+# for bit what they were (tests/test_conv_planes_gpu.py).  A pair whose {planes-out reduce + planes-in 3x3} does not measure
+# ahead of {fp32-out reduce + fp32-in 3x3} by more than the larger side's spread is listed here as (conv1 Cin, planes, dilation)
+# and keeps the fp32 link (profiles/r31_planes_isolated.md has every pair).
+# Measured on the MI355X at batch 8, 65 x 65: no pair is ahead.  The 3x3 on planes takes 1.6 - 5.3 % LONGER than the 3x3 that
+# splits its fp32 input itself (the split's VALU work was hidden behind the MFMAs; the planes are 6 bytes per element to load
+# instead of 4), the reduce GEMM with the planes epilogue 2.5 - 9.7 % longer than its fp32 twin, the pairs 1.9 - 6.2 % longer at
+# spreads of at most 1.2 % -- so all four pairs of the teacher are listed, and the opt-in routes nothing until a form measures ahead.
+PLANES_ROUTING_EXCLUDED = frozenset({(512, 256, 2), (1024, 256, 2), (1024, 512, 4), (2048, 512, 4)})
 _TEACHER_EARLY_ENTRIES = ("skd_conv3x3_split_s2_supported", "skd_conv3x3_split_s2_nhwc", "skd_conv3x3_split_supported",
                           "skd_conv3x3_split_nhwc", "skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_nhwc")
 _SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
@@ -294,15 +306,43 @@ def _blas_tail(module, x):
     return BLAS_TAILS and not module.training and not torch.is_grad_enabled()
 
 
+def _reduce_on_split(x, conv, bn):
+    """THE rule of _conv1x1_bn_eval: whether a 1x1 convolution + BN of the frozen network that blas_1x1_bn_supported accepted runs on
+    the split-core GEMM of csrc/conv1x1.hip (SPLIT_REDUCE) and not on the library GEMM."""
+    return (SPLIT_REDUCE and not (conv.in_channels == 512 and conv.out_channels == 128)      # the library wins 512 -> 128 (r11)
+            and getattr(bn, "activation", None) == "none" and SF.conv1x1_abn_supported(x, conv))
+
+
 def _conv1x1_bn_eval(x, conv, bn, relu, owner=None):
     """relu?(bn(conv1x1(x))) of the frozen network for a call blas_1x1_bn_supported accepted: the split-core GEMM of csrc/conv1x1.hip
     where SPLIT_REDUCE routes it there -- on two pieces where ``owner`` (the calling block) is marked by set_teacher_pieces -- the
     library GEMM with the folded BN otherwise."""
-    if (SPLIT_REDUCE and not (conv.in_channels == 512 and conv.out_channels == 128)      # the library wins 512 -> 128 (r11)
-            and getattr(bn, "activation", None) == "none" and SF.conv1x1_abn_supported(x, conv)):
+    if _reduce_on_split(x, conv, bn):
         return SF.conv1x1_abn_eval(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps,
                                    "relu" if relu else "none", pieces=_pieces(owner, "1x1", conv.in_channels, conv.out_channels))
     return SF.conv1x1_bn_blas(x, conv, bn, relu=relu)
+
+
+_UNASKED = object()      # _planes_link: conv2's form has not been asked for yet
+
+
+def _planes_link(block, x):
+    """``(link, form)``: whether the flagged Bottleneck ``block`` (route_teacher_planes) hands conv1 -> bn1 -> relu to conv2 as bf16
+    piece planes (include_ext/skd_planes.h) for the input ``x``, decided ONCE, before conv1 runs, from the modules and ``x`` alone:
+    the block is flagged, in eval mode, under no grad; the back-end has the entries; (conv1 Cin, planes, dilation) is not in
+    PLANES_ROUTING_EXCLUDED; both convolutions run on three pieces (a block set_teacher_pieces marked keeps its present path);
+    conv1 would go to the split reduce GEMM anyway (_reduce_on_split, so not 512 -> 128); conv2 would take the "wide" form anyway
+    (_frozen_form, asked on a stand-in with the shape and memory format conv1's output will have).  ``form``: conv2's form where
+    that last question was asked -- the caller does not ask again: one routing decision per convolution -- _UNASKED otherwise."""
+    c1, c2 = block.conv1, block.conv2
+    if (not getattr(block, "_skd_teacher_planes", False) or block.training or torch.is_grad_enabled()
+            or (c1.in_channels, c1.out_channels, c2.dilation[0]) in PLANES_ROUTING_EXCLUDED or not SF.planes_supported()
+            or _pieces(block, "1x1", c1.in_channels, c1.out_channels) != 3
+            or _pieces(block, "3x3", c2.in_channels, c2.out_channels, c2.dilation[0]) != 3
+            or not (_blas_tail(block, x) and SF.blas_1x1_bn_supported(x, c1) and _reduce_on_split(x, c1, block.bn1))):
+        return False, _UNASKED
+    form = _frozen_form(block, x.new_empty((1, 1, 1, c1.out_channels)).permute(0, 3, 1, 2), c2)
+    return form == "wide", form
 
 
 def _split_conv(x, conv, form, bn=None, activation="none", residual=None, owner=None):
@@ -448,12 +488,18 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         if _fused(self, x):
             blas = _blas_tail(self, x)
-            if blas and SF.blas_1x1_bn_supported(x, self.conv1):
+            # route_teacher_planes: relu(bn1(conv1(x))) reaches conv2 as bf16 piece planes (SF.Planes), not as an fp32 map
+            link, form = _planes_link(self, x)
+            if link:
+                out = SF.conv1x1_abn_planes_eval(x, self.conv1.weight, self.bn1.running_mean, self.bn1.running_var, self.bn1.weight,
+                                                 self.bn1.bias, self.bn1.eps, "relu")
+            elif blas and SF.blas_1x1_bn_supported(x, self.conv1):
                 out = _conv1x1_bn_eval(x, self.conv1, self.bn1, relu=True, owner=self)
             else:
                 out = self.bn1.forward_relu(self.conv1(x))
             # raw output: bn2 + ReLU stay in the tail GEMM's prologue (or the pass below)
-            form = _frozen_form(self, out, self.conv2)      # layer3 / layer4; layer1 / layer2 of a teacher route_teacher_early flagged
+            if form is _UNASKED:
+                form = _frozen_form(self, out, self.conv2)      # layer3 / layer4; layer1 / layer2 of a teacher route_teacher_early flagged
             c2 = _split_conv(out, self.conv2, form, owner=self) if form else self.conv2(out)
             tail = (not self.training and _fused_tail(x) and SF.conv1x1_abn_supported(c2, self.conv3) and self.conv3.in_channels <= 512
                     and getattr(self.bn2, "activation", None) == "none" and getattr(self.bn3, "activation", None) == "none")
@@ -769,6 +815,33 @@ def route_teacher_early(model, enable=True):
             continue
         m._skd_teacher_early = True
         _prepack(m, [(conv, False) for conv in convs])
+    return model
+
+
+def route_teacher_planes(model, enable=True):
+    """Flag the Bottlenecks of ``model`` (a frozen Bottleneck network: the teacher) for the piece-plane link and return it.
+
+    A flagged Bottleneck in eval mode, under no grad, whose ``conv1`` runs on the split reduce GEMM and whose ``conv2`` runs on the
+    wide split-core 3x3 kernel anyway, both on three pieces, has the GEMM's epilogue write relu(bn1(conv1(x))) as its three bf16
+    pieces (include_ext/skd_planes.h, ``SF.conv1x1_abn_planes_eval``) and the 3x3 load those pieces instead of
+    splitting the fp32 map itself (_planes_link has the whole rule) -- except the pairs of PLANES_ROUTING_EXCLUDED.  With today's
+    rules that is layer3's 23 blocks and layer4's 3; layer1 (64 columns), layer2 (library 512 -> 128, or the early forms) and a
+    block marked by ``set_teacher_pieces(model, 2)`` keep their present path.  The outputs are bit for bit what they were: the
+    split is a pure function of the fp32 value.  Everything behind ``conv2`` is unchanged.  It composes with route_teacher_early,
+    which routes other blocks, and works inside a graph capture: the planes are a torch allocation like the fp32 map they replace.
+    ``enable=False`` clears the flags.  A BasicBlock network (the student) is left untouched.  On a back-end without the entries
+    it warns once (RuntimeWarning, naming skd_planes.h) and flags nothing."""
+    blocks = [m for m in model.modules() if isinstance(m, Bottleneck)]
+    if enable and blocks and not SF.planes_supported():
+        import warnings
+        warnings.warn("route_teacher_planes: this back-end lacks the piece-plane entries (include_ext/skd_planes.h); the teacher "
+                      "keeps its fp32 link between conv1 and conv2", RuntimeWarning, stacklevel=2)
+        enable = False
+    for m in blocks:
+        if enable:
+            m._skd_teacher_planes = True
+        else:
+            vars(m).pop("_skd_teacher_planes", None)
     return model
 
 
