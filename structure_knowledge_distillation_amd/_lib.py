@@ -303,6 +303,22 @@ PLANES_SIGNATURES = {
     "skd_conv3x3_split_planes_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _P]),
 }
 
+# Entry points declared in include_ext2/skd_split2h.h (csrc/conv3x3.hip, csrc/conv1x1.hip with two FP16 pieces per operand and a
+# scaled residual): the frozen teacher's two-piece mode at the three-piece accuracy, twins of SPLIT2_SIGNATURES with the same
+# argument lists, extension entries in a table of their own like the fourteen above (tests/test_split2h_cpu.py checks header <->
+# table <-> exported symbols, tests/test_split2h_gpu.py holds the guard-band cases).  include/ is closed at 14 headers and
+# include_ext/ at skd_planes.h (tests/test_conv_planes_cpu.py pins both listings and the count of *_SIGNATURES tables here), so
+# the header lives in include_ext2/ and the table is named SPLIT2H_TABLE.  A back-end without them leaves the teacher on
+# three pieces (pspnet_combine.set_teacher_pieces warns): nothing raises.
+SPLIT2H_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include_ext2", "skd_split2h.h"))
+SPLIT2H_TABLE = {
+    "skd_conv3x3_split2h_pack_bytes": (_L, [_I, _I]),
+    "skd_conv3x3_split2h_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
+    "skd_conv3x3_split2h_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+    "skd_conv1x1_abn2h_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _P]),
+    "skd_conv1x1_abn2h_pro_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _F, _P]),
+}
+
 _lib = None
 _test_backend = None  # see install_test_backend()
 
@@ -334,7 +350,8 @@ def load(path=None):
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
     for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
                   WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES,
-                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES, PAIRWISE_SPLIT_SIGNATURES, PLANES_SIGNATURES):
+                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES, PAIRWISE_SPLIT_SIGNATURES, PLANES_SIGNATURES,
+                  SPLIT2H_TABLE):
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

@@ -48,6 +48,7 @@
 #include "conv_split_dev.hpp"
 #include "skd_planes.h"
 #include "skd_split2.h"
+#include "skd_split2h.h"
 
 namespace skd {
 namespace {
@@ -85,7 +86,7 @@ __device__ __forceinline__ float pro_one(float x, float m, float is, float g, fl
 }
 
 // `srow`: this thread's 8-byte slot inside a plane, in uint2 units (see conv1x1_tile); rows 64 apart are 128 slots apart.
-template <bool PRO, int TM, int PIECES>
+template <bool PRO, int TM, int PIECES, int FMT = kBf16>
 __device__ __forceinline__ void stage_store(const Staging<TM> &s, uint4 *stage, int srow, const float *ptab, int K, int kq) {
   constexpr int kRA = TM / kRPP;
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow, *sb = reinterpret_cast<uint2 *>(stage + operand_chunks(PIECES)) + srow;
@@ -102,30 +103,44 @@ __device__ __forceinline__ void stage_store(const Staging<TM> &s, uint4 *stage, 
       v.y = pro_one(v.y, pp.pm.y, pp.pi.y, pp.pg.y, pp.pb.y);
       v.z = pro_one(v.z, pp.pm.z, pp.pi.z, pp.pg.z, pp.pb.z);
       v.w = pro_one(v.w, pp.pm.w, pp.pi.w, pp.pg.w, pp.pb.w);
-      split_store<PIECES>(v, sa + 2 * kRPP * h);
+      split_store<PIECES, FMT>(v, sa + 2 * kRPP * h);
     }
   } else {
 #pragma unroll
-    for (int h = 0; h < kRA; ++h) split_store<PIECES>(s.a[h], sa + 2 * kRPP * h);
+    for (int h = 0; h < kRA; ++h) split_store<PIECES, FMT>(s.a[h], sa + 2 * kRPP * h);
   }
 #pragma unroll
-  for (int h = 0; h < kRB; ++h) split_store<PIECES>(s.b[h], sb + 2 * kRPP * h);
+  for (int h = 0; h < kRB; ++h) split_store<PIECES, FMT>(s.b[h], sb + 2 * kRPP * h);
 }
 
+// The accumulator set of the products below a0 b0.  bf16 pieces: the one set `acc` itself (lo and hi are the same array, see
+// tile_mma).  fp16 pieces (include_ext2/skd_split2h.h): a set of its own -- those products carry the factor 2^11 -- of 32 WM registers.
+template <int WM, int FMT>
+struct LowSet {
+  typedef f32x16 Set[WM][2];
+  __device__ __forceinline__ Set &of(Set &acc) { return acc; }
+};
+template <int WM>
+struct LowSet<WM, kFp16> {
+  typedef f32x16 Set[WM][2];
+  Set v;
+  __device__ __forceinline__ Set &of(Set &) { return v; }
+};
+
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.
-template <bool PRO, int TM, int PIECES = 3>
+template <bool PRO, int TM, int PIECES = 3, int FMT = kBf16>
 struct Tile1 {
   typedef Staging<TM> Stg;
   const float *__restrict__ X, *__restrict__ Wt;
   const float *ptab;
   int K, gkq, srow;
   int64_t wrow0, arow[TM / kRPP];
-  f32x16 (&acc)[TM / 64][2];
+  f32x16 (&low)[TM / 64][2], (&acc)[TM / 64][2];
   __device__ __forceinline__ void load(Stg &s, int kt) const { stage_load<PRO, TM>(s, X, Wt, kt * kBK, gkq, arow, wrow0, K); }
   __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int kt) const {
-    stage_store<PRO, TM, PIECES>(s, stage, srow, ptab, K, kt * kBK + gkq);
+    stage_store<PRO, TM, PIECES, FMT>(s, stage, srow, ptab, K, kt * kBK + gkq);
   }
-  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, PIECES>(stage, acc); }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, kTN, false, PIECES, FMT>(stage, low, acc); }
 };
 
 // PLANES (include_ext/skd_planes.h): the epilogue of one 32 x 32 accumulator block that writes the three bf16 pieces of
@@ -167,7 +182,7 @@ __device__ __forceinline__ void store_block_planes(const f32x16 &acc, unsigned c
 
 // One output tile of TM x 128: K loop through the double-buffered LDS ring, then the epilogue.  PLANES: Y is the piece-plane
 // allocation of the (M, N) output and the epilogue is store_block_planes (no residual, no prologue, three pieces).
-template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false>
+template <int TM, int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false, int FMT = kBf16>
 __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R,
                                              float *__restrict__ Y, const float *__restrict__ mean, const float *__restrict__ var,
                                              const float *__restrict__ weight, const float *__restrict__ bias,
@@ -181,6 +196,16 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+  LowSet<WM, FMT> lowset;
+  f32x16 (&low)[WM][2] = lowset.of(acc);
+  if constexpr (FMT == kFp16) {
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) low[i][j][q] = 0.f;
+  }
   const int nk = K / kBK;
   const int gt = threadIdx.x, grow = gt / kQK, gkq = (gt % kQK) * 4;
   const int srow = plane_slot(grow, gkq);           // 8-byte slot of (row grow, k quad) inside a plane
@@ -196,10 +221,10 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
     for (int i = gt * 4; i < 4 * K; i += kThreads * 4) *reinterpret_cast<float4 *>(ptab + i) = *reinterpret_cast<const float4 *>(ppack + i);
     __syncthreads();
   }
-  Tile1<PRO, TM, PIECES> tile = {X, Wt, ptab, K, gkq, srow, wrow0, {}, acc};
+  Tile1<PRO, TM, PIECES, FMT> tile = {X, Wt, ptab, K, gkq, srow, wrow0, {}, low, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) tile.arow[h] = arow[h];
-  k_loop<kDepth1x1, PIECES, PIECES == 2 && !PRO>(tile, nk, lds);
+  k_loop<kDepth1x1, PIECES, PIECES == 2 && !PRO && FMT == kBf16>(tile, nk, lds);
   // ---- epilogue: the eval-mode InPlace-ABN formula on the accumulator (+ residual) + activation ----
   const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   const int wi = (wid >> 1) * (TM / 2), wj = (wid & 1) * 64;
@@ -213,6 +238,7 @@ __device__ __forceinline__ void conv1x1_tile(const float *__restrict__ X, const 
 #pragma unroll
     for (int bi = 0; bi < WM; ++bi) {
       const int64_t row0 = m0 + wi + bi * 32;
+      if constexpr (FMT == kFp16) join_sets<FMT>(acc[bi][bj], low[bi][bj]);      // hi + 2^-11 lo
       if constexpr (PLANES) {
         unsigned char *P = reinterpret_cast<unsigned char *>(Y);
         if (full) store_block_planes<ACT, true>(acc[bi][bj], P, row0, col, M, N, mu, is, ga, be, slope);
@@ -290,13 +316,17 @@ __host__ __device__ __forceinline__ TileOf conv1x1_tile_of(unsigned block, int64
 // PIECES = 2 (include/skd_split2.h): two pieces per operand, the three products a0 b1, a1 b0, a0 b0 into the one accumulator; the
 // grid, the tile order and the half-height round are those of the three-piece launch (32 KB of LDS + the prologue's table).
 // PLANES (include_ext/skd_planes.h): Y is the piece planes of the output (conv1x1_tile); grid and tile order as the fp32 launch.
-template <int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false>
-__global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
+// FMT = kFp16 (include_ext2/skd_split2h.h): two fp16 pieces, the three products into TWO accumulator sets (128 registers at 128 rows),
+// so the kernel is compiled for two workgroups per CU; grid, tile order and half-height round stay the three-piece launch's.
+constexpr int conv1x1_wgs(int FMT) { return FMT == kFp16 ? 2 : kMinWG; }
+template <int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false, int FMT = kBf16>
+__global__ __launch_bounds__(kThreads, conv1x1_wgs(FMT)) void conv1x1_abn_kernel(
     const float *__restrict__ X, const float *__restrict__ Wt, const float *__restrict__ R, float *__restrict__ Y,
     const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ weight,
     const float *__restrict__ bias, const float *__restrict__ ppack, float eps, float slope, int64_t M, int K, int N,
     int tiles_n, int pm, int ct, int p_full) {
   static_assert(!PLANES || (!HAS_RES && !PRO && !NT && PIECES == 3), "planes out: the plain three-piece GEMM, plain stores");
+  static_assert(FMT == kBf16 || PIECES == 2, "fp16 pieces: two of them");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   // XCD-aware tile order.  Workgroup b runs on XCD b % 8 (observed placement, MI355X_MICROARCH.md; used for traffic only, any
   // placement is correct) and every XCD has its own L2: the tiles_n workgroups that share one 128 x K activation panel are
@@ -320,9 +350,9 @@ __global__ __launch_bounds__(kThreads, kMinWG) void conv1x1_abn_kernel(
   // workgroups of half the duration fill the last round's slots (p_full is a multiple of 8: whole XCD rows).
   const TileOf t = conv1x1_tile_of(blockIdx.x, M, tiles_n, pm, ct, p_full);
   if (t.rows == kTM)
-    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT, PIECES, PLANES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+    conv1x1_tile<kTM, ACT, HAS_RES, PRO, NT, PIECES, PLANES, FMT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
   else if (t.rows == kTM / 2)
-    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT, PIECES, PLANES>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
+    conv1x1_tile<kTM / 2, ACT, HAS_RES, PRO, NT, PIECES, PLANES, FMT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, t.m0, t.n0, lds);
 }
 
 __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, const float *__restrict__ var,
@@ -338,7 +368,7 @@ __global__ void pack_eval_params_kernel(int K, const float *__restrict__ mean, c
 
 // PLANES: Y is the piece planes; the tile order is the geometry's (the super-tile order of a wide output included) but the stores
 // are plain, never non-temporal -- the planes are read by the next launch -- so the one instantiation NT = false serves.
-template <int ACT, bool HAS_RES, bool PRO, int PIECES = 3, bool NT = false, bool PLANES = false>
+template <int ACT, bool HAS_RES, bool PRO, int PIECES = 3, bool NT = false, bool PLANES = false, int FMT = kBf16>
 static int launch(const float *X, const float *Wt, const float *R, float *Y, const float *mean, const float *var,
                   const float *weight, const float *bias, const float *ppack, float eps, float slope, int64_t M, int K, int N,
                   hipStream_t st) {
@@ -346,15 +376,15 @@ static int launch(const float *X, const float *Wt, const float *R, float *Y, con
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES, PLANES>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES, PLANES, FMT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(conv_lds(PIECES) + sizeof(float) * 4 * kProMaxK)) != hipSuccess) return 0;
     *rdy = true;
   }
   const size_t lds_bytes = conv_lds(PIECES) + (PRO ? sizeof(float) * 4 * (size_t)K : 0);
   Geometry g;
   if (!conv1x1_geometry(M, K, N, cu_count(st), g)) return 0;
-  if (g.nt && !NT && !PLANES) return launch<ACT, HAS_RES, PRO, PIECES, true>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
-  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES, PLANES><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
+  if (g.nt && !NT && !PLANES) return launch<ACT, HAS_RES, PRO, PIECES, true, false, FMT>(X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, st);
+  conv1x1_abn_kernel<ACT, HAS_RES, PRO, NT, PIECES, PLANES, FMT><<<dim3((unsigned)g.grid), dim3(kThreads), lds_bytes, st>>>(
       X, Wt, R, Y, mean, var, weight, bias, ppack, eps, slope, M, K, N, g.tiles_n, g.pm, g.ct, (int)g.p_full);
   return ok();
 }
@@ -395,7 +425,7 @@ int skd_conv1x1_abn_tile_of(int64_t M, int K, int N, int cus, int64_t block, int
 }  // extern "C"
 
 // The host body of the four GEMM entries below: every refusal, then the instantiation that (activation, residual, prologue) name.
-template <int PIECES>
+template <int PIECES, int FMT = kBf16>
 static int conv1x1_dispatch(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
                             const float *mean, const float *var, const float *weight, const float *bias, const float *ppack,
                             float eps, int activation, float slope, skd_stream_t stream) {
@@ -404,10 +434,10 @@ static int conv1x1_dispatch(int64_t M, int K, int N, const float *x, const float
   hipStream_t st = as_stream(stream);
 #define SKD_C11(A)                                                                                                        \
   if (ppack != nullptr)                                                                                                   \
-    return residual ? launch<A, true, true, PIECES>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st)   \
-                    : launch<A, false, true, PIECES>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st); \
-  return residual ? launch<A, true, false, PIECES>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st) \
-                  : launch<A, false, false, PIECES>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st)
+    return residual ? launch<A, true, true, PIECES, false, false, FMT>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st)   \
+                    : launch<A, false, true, PIECES, false, false, FMT>(x, w, residual, out, mean, var, weight, bias, ppack, eps, slope, M, K, N, st); \
+  return residual ? launch<A, true, false, PIECES, false, false, FMT>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st) \
+                  : launch<A, false, false, PIECES, false, false, FMT>(x, w, residual, out, mean, var, weight, bias, nullptr, eps, slope, M, K, N, st)
   switch (activation) {
     case SKD_ACT_NONE: SKD_C11(SKD_ACT_NONE);
     case SKD_ACT_RELU: SKD_C11(SKD_ACT_RELU);
@@ -476,6 +506,20 @@ int skd_conv1x1_abn2_pro_nhwc(int64_t M, int K, int N, const float *x, const flo
                               const float *ppack, int activation, float slope, skd_stream_t stream) {
   if (!ppack || K > kProMaxK) return 0;
   return conv1x1_dispatch<2>(M, K, N, x, w, residual, out, mean, var, weight, bias, ppack, eps, activation, slope, stream);
+}
+
+// include_ext2/skd_split2h.h: the same two entries on two fp16 pieces per operand with the scaled residual.
+int skd_conv1x1_abn2h_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
+                           const float *mean, const float *var, const float *weight, const float *bias, float eps,
+                           int activation, float slope, skd_stream_t stream) {
+  return conv1x1_dispatch<2, kFp16>(M, K, N, x, w, residual, out, mean, var, weight, bias, nullptr, eps, activation, slope, stream);
+}
+
+int skd_conv1x1_abn2h_pro_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
+                               const float *mean, const float *var, const float *weight, const float *bias, float eps,
+                               const float *ppack, int activation, float slope, skd_stream_t stream) {
+  if (!ppack || K > kProMaxK) return 0;
+  return conv1x1_dispatch<2, kFp16>(M, K, N, x, w, residual, out, mean, var, weight, bias, ppack, eps, activation, slope, stream);
 }
 
 }  // extern "C"

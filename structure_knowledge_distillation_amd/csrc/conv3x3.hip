@@ -45,6 +45,7 @@
 #include "skd_narrow.h"
 #include "skd_planes.h"
 #include "skd_split2.h"
+#include "skd_split2h.h"
 #include "skd_stride2.h"
 #include "skd_train.h"
 
@@ -143,7 +144,7 @@ __device__ __forceinline__ void stage_load3_a(Staging3<TM, TN, PIECES, true> &s,
   }
 }
 
-template <int TM, int TN, int PIECES, bool PLANES>
+template <int TM, int TN, int PIECES, bool PLANES, int FMT = kBf16>
 __device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLANES> &s, uint4 *stage, int srow) {
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
 #pragma unroll
@@ -154,7 +155,7 @@ __device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLAN
       dst[2 * kPlaneChunks] = s.a1[h];
       dst[4 * kPlaneChunks] = s.a2[h];
     } else {
-      split_store<PIECES>(s.a[h], sa + 2 * kRPP * h);
+      split_store<PIECES, FMT>(s.a[h], sa + 2 * kRPP * h);
     }
   }
   uint4 *sb = stage + operand_chunks(PIECES) + threadIdx.x;
@@ -169,7 +170,7 @@ __device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLAN
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.  k_loop calls load for kt = 0, 1, 2, ... in order, so the
 // cursor is simply stepped behind every one: it runs as far ahead of the MFMAs as the loads do and crosses a tap boundary
 // wherever that falls.  (Behind the last tile it stands at tap 9, which nothing reads.)
-template <int TM, int TN, int PIECES = 3, bool PLANES = false>
+template <int TM, int TN, int PIECES = 3, bool PLANES = false, int FMT = kBf16>
 struct Tile3 {
   typedef Staging3<TM, TN, PIECES, PLANES> Stg;
   static constexpr int WM = wave_blocks_m(TM, TN);
@@ -190,8 +191,8 @@ struct Tile3 {
       cur.shift = tap_shift(cur.tap, W, dil, Cin);
     }
   }
-  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES, PLANES>(s, stage, srow); }
-  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES>(stage, low, acc); }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES, PLANES, FMT>(s, stage, srow); }
+  __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES, FMT>(stage, low, acc); }
 };
 
 // STRIDE = 2 (include/skd_stride2.h; padding 1, dilation 1): THE row map of that form -- output row m = (b * Ho + oy) * Wo + ox of
@@ -252,7 +253,7 @@ __device__ __forceinline__ void block_stats(const f32x16 &acc, float *__restrict
 // without it.  PLANES (include_ext/skd_planes.h): X is the piece planes of the (M, Cin) input map; the rows' addresses are byte
 // offsets of that layout and the staging set holds piece quads (stage_load3_a, stage_store3); masks, tap cursor, K loop, product order
 // and epilogue are the code without it.
-template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
+template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
                                              const float *__restrict__ R, float *__restrict__ stats,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
@@ -299,7 +300,7 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
     abase[h] = PLANES ? planes_offset(M, Cin, mm, gkq, 0) : mm * Cin + gkq;
   }
   const uint4 *bsrc = Bp + (int64_t)tn * nk * tile_chunks(TN, PIECES) + gt;
-  Tile3<TM, TN, PIECES, PLANES> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
+  Tile3<TM, TN, PIECES, PLANES, FMT> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
     tile.abase[h] = abase[h];
@@ -320,8 +321,7 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
     const float cb = cbias != nullptr ? cbias[col] : 0.f;
 #pragma unroll
     for (int bi = 0; bi < WM; ++bi) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[bi][bj][q] += low[bi][bj][q];
+      join_sets<FMT>(acc[bi][bj], low[bi][bj]);
       if (cbias != nullptr) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[bi][bj][q] += cb;
@@ -348,7 +348,7 @@ constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kM
 
 // PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h); so does
 // STRIDE = 2 (include/skd_stride2.h), whose M is that of the smaller output.
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
@@ -361,6 +361,7 @@ void conv3x3_split_kernel(
   static_assert(PIECES == 3 || (TN == kTN && !HAS_RES), "two pieces: the 128-column forward family without the residual");
   static_assert(STRIDE == 1 || (STRIDE == 2 && TN == kTN && !HAS_RES && !STATS), "stride 2: the 128-column frozen forward alone");
   static_assert(!PLANES || (TN == kTN && PIECES == 3 && !HAS_RES && !STATS && STRIDE == 1), "piece planes in: the wide stride-1 frozen forward alone");
+  static_assert(FMT == kBf16 || (PIECES == 2 && STRIDE == 1), "fp16 pieces: the two-piece stride-1 forward family alone");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -368,11 +369,11 @@ void conv3x3_split_kernel(
   if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -386,7 +387,8 @@ void conv3x3_split_kernel(
 // a wave's 64 lanes are 64 consecutive c, so each of its eight loads reads a run of 64 elements at stride sc -- 256 contiguous
 // bytes of a channels-last weight (sc = 1: the training student's, and the PSP bottleneck's channel slice).
 // PIECES = 2 (include/skd_split2.h): the first two planes alone, 4 TN chunks per (column tile, K-tile).
-template <int TN, int PIECES = 3>
+// FMT = kFp16 (include_ext2/skd_split2h.h): the two fp16 planes p0 and the scaled p1 of split4_f16, the same 4 TN chunks.
+template <int TN, int PIECES = 3, int FMT = kBf16>
 __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
     const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int Cout, int64_t fwd_tiles,
     uint4 *__restrict__ pack_fwd, uint4 *__restrict__ pack_bwd) {
@@ -407,14 +409,20 @@ __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
   // the three-piece split for either PIECES: its first two pieces ARE the two-piece split (the third is dropped unused), so the
   // two-plane image is planes 0 and 1 of the other bit for bit; the two-piece split4 overload serves split_store<2> alone
   uint2 lo[3], hi[3];
-  split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
-  split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
+  if constexpr (FMT == kFp16) {
+    static_assert(PIECES == 2, "fp16 pieces: two of them");
+    split4_f16(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1]);
+    split4_f16(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1]);
+  } else {
+    split4(make_float4(v[0], v[1], v[2], v[3]), lo[0], lo[1], lo[2]);
+    split4(make_float4(v[4], v[5], v[6], v[7]), hi[0], hi[1], hi[2]);
+  }
   uint4 *pack = fwd ? pack_fwd : pack_bwd;
 #pragma unroll
   for (int p = 0; p < PIECES; ++p) pack[(tile * PIECES + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                    int geometry, hipStream_t st, float *stats = nullptr) {
@@ -422,7 +430,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN, PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
@@ -438,7 +446,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
       X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R, stats);
   return ok();
 }
@@ -449,7 +457,7 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
 // TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
-template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false>
+template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st, float *stats = nullptr) {
@@ -458,8 +466,8 @@ static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, c
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
-      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
-    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE, PLANES>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
   }
 }
 
@@ -487,7 +495,7 @@ static int64_t pack_image_tiles(int K9, int N, const void *pack, int64_t pack_by
 }
 
 // Either image or both in one launch (include/skd_train.h); every refusal is decided here, in front of the launch.
-template <int TN, int PIECES = 3>
+template <int TN, int PIECES = 3, int FMT = kBf16>
 static int pack_pair3(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y, int64_t stride_x,
                       void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes, skd_stream_t stream) {
   if (!w || (!pack_fwd && !pack_bwd)) return 0;
@@ -495,7 +503,7 @@ static int pack_pair3(int Cin, int Cout, const float *w, int64_t stride_n, int64
   const int64_t fwd_tiles = pack_image_tiles<TN, PIECES>(Cin, Cout, pack_fwd, fwd_bytes);
   const int64_t bwd_tiles = pack_image_tiles<TN, PIECES>(Cout, Cin, pack_bwd, bwd_bytes);
   if (fwd_tiles < 0 || bwd_tiles < 0 || fwd_tiles + bwd_tiles > 2147483647) return 0;
-  conv3x3_pack_pair_kernel<TN, PIECES><<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(2 * TN), 0, as_stream(stream)>>>(
+  conv3x3_pack_pair_kernel<TN, PIECES, FMT><<<dim3((unsigned)(fwd_tiles + bwd_tiles)), dim3(2 * TN), 0, as_stream(stream)>>>(
       w, stride_n, stride_c, stride_y, stride_x, Cin, Cout, fwd_tiles, static_cast<uint4 *>(pack_fwd),
       static_cast<uint4 *>(pack_bwd));
   return ok();
@@ -504,7 +512,7 @@ static int pack_pair3(int Cin, int Cout, const float *w, int64_t stride_n, int64
 // out = act(ABN_eval(conv3x3(x) + conv_bias) [+ residual]); residual == nullptr takes the instantiations without the residual
 // read.  The kernel reads the residual through a __restrict__ pointer at the offsets it writes, so a residual that overlaps the
 // output is refused, not defined.
-template <int TN, int PIECES = 3>
+template <int TN, int PIECES = 3, int FMT = kBf16>
 static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
                 const float *residual, const float *conv_bias, const float *mean, const float *var, const float *weight,
                 const float *bias, float eps, int activation, float slope, int geometry, int max_geometry, skd_stream_t stream) {
@@ -527,7 +535,7 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st,    \
           nullptr);                                                                                                           \
     else                                                                                                                      \
-      return residual != nullptr ? 0 : launch3g<TN, ACT, false, PIECES>(                                                      \
+      return residual != nullptr ? 0 : launch3g<TN, ACT, false, PIECES, false, 1, false, FMT>(                                \
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
   switch (activation) {
     SKD_CONV3X3_CASE(SKD_ACT_NONE);
@@ -681,6 +689,21 @@ int skd_conv3x3_split2_nhwc(int B, int H, int W, int Cin, int Cout, int dilation
                             float eps, int activation, float slope, int geometry, skd_stream_t stream) {
   return run3<kTN, 2>(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation,
                       slope, geometry, 3, stream);
+}
+
+// include_ext2/skd_split2h.h: the same family on two FP16 pieces per operand with the scaled residual, and its two-plane weight image.
+int64_t skd_conv3x3_split2h_pack_bytes(int Cin, int Cout) { return pack_bytes3<kTN, 2>(Cin, Cout); }
+
+int skd_conv3x3_split2h_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                     int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
+  return pack_pair3<kTN, 2, kFp16>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
+}
+
+int skd_conv3x3_split2h_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                             const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                             float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+  return run3<kTN, 2, kFp16>(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation,
+                             slope, geometry, 3, stream);
 }
 
 // include/skd_narrow.h: the 64-column form.

@@ -64,12 +64,40 @@ __device__ __forceinline__ void split4(float4 v, uint2 &p0, uint2 &p1) {
   p1.x = pack_bf16(v.x, v.y);
   p1.y = pack_bf16(v.z, v.w);
 }
+// The piece FORMAT, beside PIECES: kBf16 everywhere but in the forms of include_ext2/skd_split2h.h, which cut an operand into two
+// FP16 pieces (PIECES = 2 only).  An fp16 piece carries 11 significant bits, so two carry 22 -- but fp16's exponent is narrow: the
+// residual v - fp16(v), about 2^-11 |v|, would be an fp16 subnormal for every |v| < 0.125.  It is therefore SCALED by 2^11 (exact)
+// before it is converted: v ~ p0 + 2^-11 p1.  The products a0 b1 and a1 b0 then carry the factor 2^11 and go into `lo`, a0 b0
+// into `hi` (tile_mma), and the epilogue joins the sets as hi + 2^-11 lo (join_sets).  Both formats are 16-bit: the LDS image, the
+// chunk map, k_loop and the stage size are the bf16 two-piece ones.
+constexpr int kBf16 = 0, kFp16 = 1;
+constexpr float kResidualScale = 2048.f, kLoScale = 1.f / 2048.f;      // 2^11, 2^-11
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+// Two fp32 -> two fp16 in one dword, round to nearest even (v_cvt_pk_f16_f32), and back (exact).
+__device__ __forceinline__ uint32_t pack_f16(float x, float y) {
+  const f32x2 v = {x, y};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+}
+__device__ __forceinline__ f32x2 unpack_f16(uint32_t u) { return __builtin_convertvector(__builtin_bit_cast(f16x2, u), f32x2); }
+// The two fp16 pieces of four consecutive k of one row: p0 = fp16(v), p1 = fp16((v - p0) * 2^11).  The residual is exact in fp32
+// (p0 agrees with v in its leading 11 bits, or is a subnormal multiple of 2^-24 below a v whose own unit is finer), and so is the
+// scaling.  |v| > 65504 rounds p0 to infinity and p1 to the opposite infinity: every product that reads the pair is NaN.
+__device__ __forceinline__ void split4_f16(float4 v, uint2 &p0, uint2 &p1) {
+  p0.x = pack_f16(v.x, v.y);
+  p0.y = pack_f16(v.z, v.w);
+  const f32x2 a = unpack_f16(p0.x), b = unpack_f16(p0.y);
+  p1.x = pack_f16((v.x - a[0]) * kResidualScale, (v.y - a[1]) * kResidualScale);
+  p1.y = pack_f16((v.z - b[0]) * kResidualScale, (v.w - b[1]) * kResidualScale);
+}
 // ... written to the thread's 8-byte slot `dst` of the PIECES planes of one operand's LDS image
-template <int PIECES = 3>
+template <int PIECES = 3, int FMT = kBf16>
 __device__ __forceinline__ void split_store(float4 v, uint2 *dst) {
   static_assert(PIECES == 2 || PIECES == 3, "two or three pieces");
+  static_assert(FMT == kBf16 || (FMT == kFp16 && PIECES == 2), "fp16 pieces: two of them");
   uint2 p0, p1, p2;
-  if constexpr (PIECES == 3) split4(v, p0, p1, p2);
+  if constexpr (FMT == kFp16) split4_f16(v, p0, p1);
+  else if constexpr (PIECES == 3) split4(v, p0, p1, p2);
   else split4(v, p0, p1);
   dst[0] = p0;
   dst[2 * kPlaneChunks] = p1;
@@ -134,7 +162,21 @@ struct Products<2> {
   static constexpr int kN = 3, kPA[3] = {0, 1, 0}, kPB[3] = {1, 0, 0};
 };
 
-template <int TM, int TN = kTN, bool SWAP = false, int PIECES = 3>
+// The fragment type and the MFMA of a piece format: both take the same cycles on gfx950.
+template <int FMT>
+struct PieceMma;
+template <>
+struct PieceMma<kBf16> {
+  typedef bf16x8 Frag;
+  static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <>
+struct PieceMma<kFp16> {
+  typedef f16x8 Frag;
+  static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
+template <int TM, int TN = kTN, bool SWAP = false, int PIECES = 3, int FMT = kBf16>
 __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_blocks_m(TM, TN)][2],
                                          f32x16 (&hi)[wave_blocks_m(TM, TN)][2]) {
   constexpr int WM = wave_blocks_m(TM, TN);
@@ -144,13 +186,15 @@ __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_b
   const int half = lane >> 5, r = lane & 31;
   const uint4 *pa = stage + half * 128 + ((wi + r) ^ (half * 4));
   const uint4 *pb = stage + operand_chunks(PIECES) + half * TN + ((wj + r) ^ (half * 4));
-  bf16x8 a[WM][PIECES], b[2][PIECES];
+  static_assert(FMT == kBf16 || PIECES == 2, "fp16 pieces: two of them");
+  typedef typename PieceMma<FMT>::Frag Frag;
+  Frag a[WM][PIECES], b[2][PIECES];
 #pragma unroll
   for (int p = 0; p < PIECES; ++p) {
 #pragma unroll
-    for (int i = 0; i < WM; ++i) a[i][p] = __builtin_bit_cast(bf16x8, pa[p * kPlaneChunks + 32 * i]);
+    for (int i = 0; i < WM; ++i) a[i][p] = __builtin_bit_cast(Frag, pa[p * kPlaneChunks + 32 * i]);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(bf16x8, pb[p * 2 * TN + 32 * j]);
+    for (int j = 0; j < 2; ++j) b[j][p] = __builtin_bit_cast(Frag, pb[p * 2 * TN + 32 * j]);
   }
   typedef Products<PIECES> P;
 #pragma unroll
@@ -160,12 +204,19 @@ __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&lo)[wave_b
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         f32x16 &dst = t < P::kN - 1 ? lo[i][j] : hi[i][j];
-        dst = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][SWAP ? P::kPB[t] : P::kPA[t]], b[j][SWAP ? P::kPA[t] : P::kPB[t]], dst, 0, 0, 0);
+        dst = PieceMma<FMT>::mma(a[i][SWAP ? P::kPB[t] : P::kPA[t]], b[j][SWAP ? P::kPA[t] : P::kPB[t]], dst);
       }
 }
 template <int TM, int PIECES = 3>
 __device__ __forceinline__ void tile_mma(const uint4 *stage, f32x16 (&acc)[TM / 64][2]) {
   tile_mma<TM, kTN, false, PIECES>(stage, acc, acc);
+}
+// The two accumulator sets of one block joined in front of the epilogue: hi + lo, or -- fp16 pieces, whose `lo` products carry the
+// residual's factor 2^11 -- hi + 2^-11 lo as one fma per element.
+template <int FMT = kBf16>
+__device__ __forceinline__ void join_sets(f32x16 &hi, const f32x16 &lo) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) hi[q] = FMT == kFp16 ? __builtin_fmaf(lo[q], kLoScale, hi[q]) : hi[q] + lo[q];
 }
 
 // The K loop of one output tile through the two LDS stages, shared by both kernels.  `Tile` supplies

@@ -253,11 +253,12 @@ def _cached(owner, attr, key, build, hold=None):
 
 
 def drop_conv3x3_packs(owner):
-    """Forget the weight packs conv3x3_pack_weights (both piece counts) / conv3x3_train_packs / conv3x3_narrow_pack_weights /
+    """Forget the weight packs conv3x3_pack_weights (both piece counts, both piece formats) / conv3x3_train_packs / conv3x3_narrow_pack_weights /
     conv3x3_split_train's narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under
-    "pack3x3" / "pack3x3_2" / "pack3x3_train")."""
+    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train")."""
     slot = owner if isinstance(owner, dict) else vars(owner)
-    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_2", "pack3x3_train") + _NARROW_PACK_ATTRS:
+    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_2", "pack3x3_2h",
+                 "pack3x3_train") + _NARROW_PACK_ATTRS:
         slot.pop(attr, None)
 
 
@@ -461,7 +462,8 @@ def ppm_fold_supported(feats, sizes):
         and _is_cl(feats) and 3 * sum(sizes) <= 64 and len(sizes) <= 4
 
 
-def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False, pieces=3):
+def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False, pieces=3,
+                         piece_format="bf16"):
     """conv3x3(cat([upsample(p) for p in priors] + [feats], 1), weight, padding=1) (pspnet_combine.py:104-111) without
     the concatenated tensor and without convolving the priors' channels: the feature-map slice of the weight goes through
     the convolution, the priors through a (B s^2) x Cm x 9 Cout GEMM each and the fold kernel (csrc/ppm.hip).
@@ -472,8 +474,9 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
     slice of the weight, so that autograd carries its gradient back into the full weight; packs once per weight version in `cache`).
     `split_wgrad`: with `split_train`, the weight gradient of that slice on the split core too (conv3x3_split_train's ``wgrad``).
     `pieces` = 2: with `split3x3`, the frozen feature-map convolution on the two-piece core (conv3x3_split_eval's ``pieces``), its
-    pack under a key of its own in `cache`; the fold's matrix products and the training form are what they were."""
-    _check_pieces(pieces)
+    pack under a key of its own in `cache`; the fold's matrix products and the training form are what they were.
+    `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include_ext2/skd_split2h.h), its pack under a third key."""
+    _check_piece_format(_check_pieces(pieces), piece_format)
     import torch.nn.functional as F
     cm = priors[0].shape[1]
     n_prior = len(priors) * cm
@@ -494,8 +497,12 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
         base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}), **extra)
     elif split3x3 and cache is not None and _conv3x3_ok(feats, weight[:, n_prior:], 1, 1, 1, 1, **_FROZEN):
         if pieces == 2:
-            base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3_2", {}), pieces=2),
-                                      cout, pieces=2)
+            if piece_format == "fp16":
+                base = conv3x3_split_eval_fp16(feats, conv3x3_pack_weights_fp16(None, weight[:, n_prior:], cache.setdefault("pack3x3_2h", {})),
+                                               cout)
+            else:
+                base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3_2", {}), pieces=2),
+                                          cout, pieces=2)
         else:
             base = conv3x3_split_eval(feats, conv3x3_pack_weights(None, weight[:, n_prior:], cache.setdefault("pack3x3", {})), cout)
     else:
@@ -504,6 +511,18 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
     # necessary flops of a 2 GFLOP product, but a single well-shaped library call instead of four skinny ones)
     p_all = torch.cat([_cl(p).permute(0, 2, 3, 1).reshape(-1, cm) for p in priors], 0)
     return _PPMFold.apply(base, sizes, torch.mm(p_all, w_all))
+
+
+def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False, pieces=3):
+    return _ppm_fold_bottleneck(priors, feats, weight, cache, split3x3, split_train, split_wgrad, pieces)
+
+
+def ppm_fold_bottleneck_fp16(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False):
+    """``ppm_fold_bottleneck`` with the frozen feature-map convolution on two FP16 pieces (``conv3x3_split_eval_fp16``)."""
+    return _ppm_fold_bottleneck(priors, feats, weight, cache, split3x3, split_train, split_wgrad, 2, "fp16")
+
+
+ppm_fold_bottleneck.__doc__ = _ppm_fold_bottleneck.__doc__
 
 
 class _MaxPool3x3s2(Function):
@@ -698,6 +717,34 @@ def _need_split2_entry(name):
         raise NotImplementedError("the active back-end does not provide %s (include/skd_split2.h)" % name)
 
 
+# include_ext2/skd_split2h.h: the two-piece form on FP16 pieces with the scaled residual, entry for entry the twin of skd_split2.h
+_SPLIT2H_ENTRIES = {"skd_conv3x3_split2_pack_bytes": "skd_conv3x3_split2h_pack_bytes",
+                    "skd_conv3x3_split2_pack_weights": "skd_conv3x3_split2h_pack_weights",
+                    "skd_conv3x3_split2_nhwc": "skd_conv3x3_split2h_nhwc",
+                    "skd_conv1x1_abn2_nhwc": "skd_conv1x1_abn2h_nhwc",
+                    "skd_conv1x1_abn2_pro_nhwc": "skd_conv1x1_abn2h_pro_nhwc"}
+
+
+def _check_piece_format(pieces, piece_format):
+    """``piece_format``: "bf16" (every form so far) or "fp16" (include_ext2/skd_split2h.h), which exists for ``pieces`` = 2 alone."""
+    if piece_format not in ("bf16", "fp16"):
+        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
+    if piece_format == "fp16" and pieces != 2:
+        raise ValueError("piece_format='fp16' requires pieces=2 (include_ext2/skd_split2h.h), not pieces=%r" % (pieces,))
+    return piece_format
+
+
+def _split2_entry(name, piece_format):
+    """The two-piece entry ``name`` of include/skd_split2.h in ``piece_format``; NotImplementedError on a back-end without it."""
+    if piece_format == "fp16":
+        name = _SPLIT2H_ENTRIES[name]
+        if not _lib.has_entry(name):
+            raise NotImplementedError("the active back-end does not provide %s (include_ext2/skd_split2h.h)" % name)
+        return name
+    _need_split2_entry(name)
+    return name
+
+
 # include_ext/skd_planes.h: piece planes -- an activation map as the three bf16 pieces the split core's consumer reads
 _PLANES_PRODUCER, _PLANES_CONSUMER = "skd_conv1x1_abn_planes_nhwc", "skd_conv3x3_split_planes_nhwc"
 _PLANES_ENTRIES = ("skd_planes_supported", "skd_planes_bytes", "skd_planes_offset", "skd_planes_split_nhwc", "skd_planes_join_nhwc",
@@ -795,8 +842,8 @@ def conv1x1_abn_planes_eval(x, conv_weight, running_mean, running_var, weight, b
     return out
 
 
-def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
-                     residual=None, pro=None, pieces=3):
+def _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
+                      residual=None, pro=None, pieces=3, piece_format="bf16"):
     """act(bn_running(conv1x1(x)) [+ residual]) as ONE GEMM with the normalisation in its epilogue (inference only;
     networks/pspnet_combine.py:65-84 for the frozen teacher).  fp32 in and out; the products run on the bf16 MFMA with both
     operands split into three bf16 pieces and the six leading products accumulated in fp32 (csrc/conv1x1.hip): within 4 x of
@@ -809,9 +856,13 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
     ``pieces`` = 2: the reduced-precision form of include/skd_split2.h -- two bf16 pieces per operand and the three products
     a0 b1, a1 b0, a0 b0: about 4e-6 of the output's largest magnitude per product instead of 3e-7 (tests/split2_ref.py is its model,
     tests/test_split2_gpu.py the comparison; profiles/r25_split2_accuracy.md); a back-end without the entries raises, the call is
-    never downgraded.  ``conv1x1_abn_planes_eval`` is the same GEMM with its result written as bf16 piece planes
+    never downgraded.  ``conv1x1_abn_eval_fp16`` is the two-piece form on FP16 pieces (include_ext2/skd_split2h.h: the residual
+    scaled by 2^11, the same three products in two accumulator sets, 22 significant bits per operand: the three-piece accuracy;
+    tests/split2h_ref.py is its model; an input beyond +-65504 gives NaN) -- an op of its own, not a keyword of this one, whose
+    bound arguments are recorded call by call in tests/golden/routing_census.json.  ``conv1x1_abn_planes_eval`` is the same GEMM with its result written as bf16 piece planes
     (include_ext/skd_planes.h)."""
     pieces = _check_pieces(pieces)
+    piece_format = _check_piece_format(pieces, piece_format)
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
         raise RuntimeError("conv1x1_abn_eval is inference-only")
     _lib.require_device(x, conv_weight, running_mean, running_var, weight, bias, residual)
@@ -832,7 +883,7 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
             raise ValueError("pro must be the (4, Cin) fp32 pack of abn_pack_eval_params")
         entry = "skd_conv1x1_abn_pro_nhwc" if pieces == 3 else "skd_conv1x1_abn2_pro_nhwc"
         if pieces == 2:
-            _need_split2_entry(entry)
+            entry = _split2_entry(entry, piece_format)
         _lib.check(getattr(_lib.get(), entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
                                               running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight),
                                               _lib.ptr(bias), float(eps), pro.data_ptr(), act, float(slope),
@@ -840,11 +891,26 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
         return out
     entry = "skd_conv1x1_abn_nhwc" if pieces == 3 else "skd_conv1x1_abn2_nhwc"
     if pieces == 2:
-        _need_split2_entry(entry)
+        entry = _split2_entry(entry, piece_format)
     _lib.check(getattr(_lib.get(), entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
                                           running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
                                           float(eps), act, float(slope), _lib.stream_of(x)), entry)
     return out
+
+
+def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
+                     residual=None, pro=None, pieces=3):
+    return _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps, activation, slope, residual, pro, pieces)
+
+
+def conv1x1_abn_eval_fp16(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
+                          residual=None, pro=None):
+    """``conv1x1_abn_eval`` on two FP16 pieces per operand with the scaled residual (include_ext2/skd_split2h.h): the arguments, the
+    refusals and the result's layout of that op; never downgraded (a back-end without the entries raises NotImplementedError)."""
+    return _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps, activation, slope, residual, pro, 2, "fp16")
+
+
+conv1x1_abn_eval.__doc__ = _conv1x1_abn_eval.__doc__
 
 
 def conv2d_square_geometry(conv):
@@ -934,7 +1000,7 @@ def _conv3x3_packs(w, owner, attr, entry, what, images, bytes_entry="skd_conv3x3
     return _cached(owner, attr, _version_key((w,), tuple(w.shape), tuple(w.stride())), build, hold=w)
 
 
-def conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3):
+def _conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3, piece_format="bf16"):
     """The three bf16 planes of a frozen 3x3 convolution's weight in the layout csrc/conv3x3.hip streams into LDS (6 bytes per
     weight), cached on ``owner`` (default: the conv module) like abn_pack_eval_params and rebuilt when the weight is written or
     moved -- by THE RULE above _version_key: a fused optimizer's step counts as a write only with
@@ -943,18 +1009,33 @@ def conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3):
     bottleneck packs the feature-map slice of its weight -- and either memory format gives the same pack.  The first call
     allocates: a frozen network makes it in its eager warm-up steps, before any graph capture.
     ``pieces`` = 2: the two-plane image of include/skd_split2.h (4 bytes per weight: the first two planes of the other), for
-    ``conv3x3_split_eval(..., pieces=2)``; cached under the same rule in a slot of its own, so both packs of one module coexist."""
+    ``conv3x3_split_eval(..., pieces=2)``; cached under the same rule in a slot of its own, so both packs of one module coexist.
+    ``conv3x3_pack_weights_fp16``: the two fp16 planes of include_ext2/skd_split2h.h (p0 and the scaled p1, 4 bytes per weight
+    again), in a third slot beside the other two."""
     pieces = _check_pieces(pieces)
+    piece_format = _check_piece_format(pieces, piece_format)
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_pack_weights is for frozen (no-grad) convolutions")
     if pieces == 2:
-        for name in (_PACK2_ENTRY, _PACK2_BYTES):
-            _need_split2_entry(name)
-        return _conv3x3_packs(w, conv if owner is None else owner, _PACK2_ATTR, _PACK2_ENTRY, "conv3x3_pack_weights", (True,),
-                              _PACK2_BYTES)[0]
+        pack_entry, bytes_entry = (_split2_entry(name, piece_format) for name in (_PACK2_ENTRY, _PACK2_BYTES))
+        return _conv3x3_packs(w, conv if owner is None else owner, _PACK2H_ATTR if piece_format == "fp16" else _PACK2_ATTR, pack_entry,
+                              "conv3x3_pack_weights", (True,), bytes_entry)[0]
     return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_pack", "skd_conv3x3_split_pack_weights",
                           "conv3x3_pack_weights", (True,))[0]
+
+
+def conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3):
+    return _conv3x3_pack_weights(conv, weight, owner, pieces)
+
+
+def conv3x3_pack_weights_fp16(conv, weight=None, owner=None):
+    """``conv3x3_pack_weights`` for ``conv3x3_split_eval_fp16``: the two-plane fp16 image of include_ext2/skd_split2h.h, cached
+    under the same rule in a slot of its own."""
+    return _conv3x3_pack_weights(conv, weight, owner, 2, "fp16")
+
+
+conv3x3_pack_weights.__doc__ = _conv3x3_pack_weights.__doc__
 
 
 def conv3x3_train_packs(weight, owner=None):
@@ -973,6 +1054,7 @@ _RES_ENTRY = "skd_conv3x3_split_res_nhwc"
 # include/skd_split2.h: the two-piece form of the frozen 128-column convolution, its pack entry, its size query, its cache slot
 _SPLIT2_ENTRY, _PACK2_ENTRY, _PACK2_BYTES = "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_pack_bytes"
 _PACK2_ATTR = "_skd_conv3x3_pack2"
+_SPLIT2H_ENTRY, _PACK2H_ATTR = _SPLIT2H_ENTRIES[_SPLIT2_ENTRY], "_skd_conv3x3_pack2h"      # include_ext2/skd_split2h.h: fp16 pieces
 # include/skd_narrow.h: the 64-column form of csrc/conv3x3.hip.  Its one convolution entry takes the residual pointer.
 _NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
 _NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
@@ -986,7 +1068,8 @@ def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, act
     lib = _lib.get()
     b, cin, h, w = x.shape
     pack_bytes = (lib.skd_conv3x3_narrow_pack_bytes if entry == _NARROW_ENTRY
-                  else getattr(lib, _PACK2_BYTES) if entry == _SPLIT2_ENTRY else lib.skd_conv3x3_split_pack_bytes)
+                  else getattr(lib, _PACK2_BYTES) if entry == _SPLIT2_ENTRY
+                  else getattr(lib, _SPLIT2H_ENTRIES[_PACK2_BYTES]) if entry == _SPLIT2H_ENTRY else lib.skd_conv3x3_split_pack_bytes)
     if pack.numel() != pack_bytes(cin, cout):
         raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
     mean = var = gamma = beta = None
@@ -1036,7 +1119,8 @@ def _residual_cl(x, cout, residual):
     return _cl(residual)
 
 
-def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0, pieces=3):
+def _conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0, pieces=3,
+                        piece_format="bf16"):
     """act(bn_running(conv3x3(x) + conv_bias)) with ``pack = conv3x3_pack_weights(...)`` (inference only; conv3x3_split_supported
     says when).  fp32 in and out, channels-last; the products run on the bf16 MFMA through the three-piece split (csrc/conv3x3.hip):
     within 4 x of the fp32 convolution's error against a float64 result and never above 2e-5 of the output's largest magnitude
@@ -1045,10 +1129,13 @@ def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activ
     ``pieces`` = 2: the reduced-precision form of include/skd_split2.h with ``pack = conv3x3_pack_weights(..., pieces=2)`` -- two
     pieces per operand, the products a0 b1, a1 b0, a0 b0: within 2e-5 of its float64 model (tests/split2_ref.py), which itself is
     about 4e-6 of the output's largest magnitude from the exact product (profiles/r25_split2_accuracy.md).  A back-end without the
-    entry raises; the call is never downgraded.
+    entry raises; the call is never downgraded.  ``conv3x3_split_eval_fp16`` is the form of include_ext2/skd_split2h.h with
+    ``pack = conv3x3_pack_weights_fp16(...)`` -- two fp16 pieces, scaled residual, the three-piece accuracy
+    (tests/split2h_ref.py); an input beyond +-65504 gives NaN.
     ``x`` may be a ``Planes`` (include_ext/skd_planes.h; three pieces only): the kernel loads the pieces instead of cutting the
     fp32 map (skd_conv3x3_split_planes_nhwc), and the result is bit for bit that of the call on the fp32 map."""
     pieces = _check_pieces(pieces)
+    piece_format = _check_piece_format(pieces, piece_format)
     if isinstance(x, Planes):
         if pieces != 3:
             raise ValueError("conv3x3_split_eval: piece planes hold three pieces")
@@ -1057,9 +1144,21 @@ def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activ
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_split_eval is inference-only")
     if pieces == 2:
-        _need_split2_entry(_SPLIT2_ENTRY)
-        return _conv3x3_launch(_SPLIT2_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry)
+        return _conv3x3_launch(_split2_entry(_SPLIT2_ENTRY, piece_format), x, pack, cout, dilation, conv_bias, bn, activation, geometry)
     return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias, bn, activation, geometry)
+
+
+def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0, pieces=3):
+    return _conv3x3_split_eval(x, pack, cout, dilation, conv_bias, bn, activation, geometry, pieces)
+
+
+def conv3x3_split_eval_fp16(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0):
+    """``conv3x3_split_eval`` on two FP16 pieces per operand with the scaled residual (include_ext2/skd_split2h.h), with
+    ``pack = conv3x3_pack_weights_fp16(...)``; never downgraded (a back-end without the entry raises NotImplementedError)."""
+    return _conv3x3_split_eval(x, pack, cout, dilation, conv_bias, bn, activation, geometry, 2, "fp16")
+
+
+conv3x3_split_eval.__doc__ = _conv3x3_split_eval.__doc__
 
 
 def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, conv_bias=None, geometry=0):

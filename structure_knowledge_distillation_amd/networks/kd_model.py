@@ -195,9 +195,13 @@ class NetModel():
         # pieces per operand and three products (pspnet_combine.set_teacher_pieces, include/skd_split2.h) -- an ACCURACY trade: its
         # outputs move by about 1.5e-5 of their largest magnitude (profiles/r25_split2_accuracy.md).  Independent of the five student
         # switches; off by default.  Set here, before any warm-up step or teacher-graph capture sees the network.
+        # args.teacher_piece_format (None: SKD_TEACHER_PIECE_FORMAT, default "bf16"): "fp16" with teacher_pieces = 2 = two FP16 pieces
+        # with a scaled residual (include_ext2/skd_split2h.h): the same three products at the three-piece accuracy.  The format
+        # without teacher_pieces = 2 is an error, not a silent three-piece run.
         self.teacher_pieces = _teacher_pieces(getattr(args, "teacher_pieces", None))
+        self.teacher_piece_format = _teacher_piece_format(getattr(args, "teacher_piece_format", None), self.teacher_pieces)
         if self.teacher_pieces == 2:
-            set_teacher_pieces(teacher, 2)
+            set_teacher_pieces(teacher, 2, piece_format=self.teacher_piece_format)
         self.parallel_teacher = self.DataParallelModelProcess(teacher, 2, "eval", device)
         self.teacher = teacher
         parallel_old.broadcast_module(teacher)
@@ -907,6 +911,19 @@ def _teacher_pieces(value):
     return int(str(value).strip())
 
 
+def _teacher_piece_format(value, pieces):
+    """``value`` (None: the environment's SKD_TEACHER_PIECE_FORMAT, default "bf16") as "bf16" or "fp16"; anything else, and "fp16"
+    with ``pieces`` other than 2, is a ValueError."""
+    if value is None:
+        value = os.environ.get("SKD_TEACHER_PIECE_FORMAT", "bf16")
+    value = str(value).strip()
+    if value not in ("bf16", "fp16"):
+        raise ValueError("teacher_piece_format / SKD_TEACHER_PIECE_FORMAT must be 'bf16' or 'fp16', not %r" % (value,))
+    if value == "fp16" and pieces != 2:
+        raise ValueError("teacher_piece_format 'fp16' requires teacher_pieces / SKD_TEACHER_PIECES = 2, not %r" % (pieces,))
+    return value
+
+
 def _teacher_planes(value):
     """``value`` as a bool; None: whether the environment's SKD_TEACHER_PLANES is "1" (default "0")."""
     return os.environ.get("SKD_TEACHER_PLANES", "0") == "1" if value is None else bool(value)
@@ -926,12 +943,14 @@ def default_args(**overrides):
         snapshot_dir=None, device=torch.device("cuda" if torch.cuda.is_available() else "cpu"),
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
-        split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None, teacher_planes=None)
+        split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None, teacher_planes=None,
+        teacher_piece_format=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     for name, env, _ in SWITCHES:      # None: the environment switch
         if getattr(a, name) is None:
             setattr(a, name, _switch(a, name, env))
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
+    a.teacher_piece_format = _teacher_piece_format(a.teacher_piece_format, a.teacher_pieces)      # "fp16": two fp16 pieces (skd_split2h.h)
     a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include_ext/skd_planes.h)
     return a

@@ -117,6 +117,16 @@ SHORTCUT_ROUTING_EXCLUDED = frozenset({(128, 64, 1, "wgrad"), (64, 128, 2, "wgra
 # than the spread is listed here as ("1x1", K, N) or ("3x3", Cin, Cout, dilation) and keeps three pieces
 # (profiles/r25_split2_isolated.md has every shape).
 SPLIT2_ROUTING_EXCLUDED = frozenset()
+# The frozen teacher on two FP16 pieces with a scaled residual (set_teacher_pieces(model, 2, piece_format="fp16"), below; a further
+# opt-in, include_ext2/skd_split2h.h): the same modules, the same call sites, the same three products as the two bf16
+# pieces above at 22 significant bits per operand instead of 16 -- the three-piece accuracy.  A shape that does not measure ahead of
+# its three-piece twin by more than the spread is listed here, as above, and keeps THREE bf16 pieces
+# (profiles/r32_split2h_isolated.md has every shape).
+# Measured on the MI355X at batch 8: fifteen of the sixteen shapes are 1.05 - 1.56 x ahead of three pieces (the 3x3 kernel 1.50 -
+# 1.56 x, within 5 - 8 % of two bf16 pieces; the 1x1 kernel, which holds two accumulator sets and runs two workgroups per CU instead
+# of three, 1.05 - 1.51 x).  layer1's tail, 64 -> 256 at 129 x 129, bound by its 137 MB of activation and residual traffic, is
+# BEHIND its three-piece twin: 70.9 - 71.3 us against 67.3 - 67.8 us, so it is listed and keeps three pieces.
+SPLIT2H_ROUTING_EXCLUDED = frozenset({("1x1", 64, 256)})
 # Batch-norm statistics from the routed convolution's epilogue (route_training_convs(bnstats=True); a seventh opt-in, on top of
 # the training form): a BasicBlock's conv1 / conv2 that the training form routes -- the 11 wide convolutions of layer2-4, and
 # with ``narrow`` layer1's four -- also writes one (mean, M2) per 32-row block and channel of its output (include/skd_bnstats.h),
@@ -160,13 +170,33 @@ _TEACHER_EARLY_ENTRIES = ("skd_conv3x3_split_s2_supported", "skd_conv3x3_split_s
                           "skd_conv3x3_split_nhwc", "skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_nhwc")
 _SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
                    "skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn2_pro_nhwc")
+_SPLIT2H_ENTRIES = ("skd_conv3x3_split2h_pack_bytes", "skd_conv3x3_split2h_pack_weights", "skd_conv3x3_split2h_nhwc",
+                    "skd_conv1x1_abn2h_nhwc", "skd_conv1x1_abn2h_pro_nhwc")
+
+
+def _piece_route(module, *shape, fp16_form=True):
+    """``(pieces, piece_format)`` of a frozen split-core call of ``module``: its marks (set_teacher_pieces; three bf16 pieces
+    without one).  Marked for two bf16 pieces: 3 for a ``shape`` that SPLIT2_ROUTING_EXCLUDED lists.  Marked for two FP16 pieces
+    (include_ext2/skd_split2h.h): ``(2, "fp16")``, and THREE bf16 pieces -- never two, which nobody asked for -- for a ``shape``
+    that SPLIT2H_ROUTING_EXCLUDED lists and for a call whose form has no fp16 twin (``fp16_form=False``: the stride-2 form)."""
+    pieces = getattr(module, "_skd_teacher_pieces", 3)
+    if pieces == 3:
+        return 3, "bf16"
+    if getattr(module, "_skd_teacher_piece_format", "bf16") == "fp16":
+        return (2, "fp16") if fp16_form and shape not in SPLIT2H_ROUTING_EXCLUDED else (3, "bf16")
+    return (3 if shape in SPLIT2_ROUTING_EXCLUDED else pieces), "bf16"
 
 
 def _pieces(module, *shape):
-    """The piece count of a frozen split-core call of ``module``: its mark (set_teacher_pieces; 3 without one), and 3 for a
-    ``shape`` that SPLIT2_ROUTING_EXCLUDED lists."""
-    pieces = getattr(module, "_skd_teacher_pieces", 3)
-    return 3 if pieces == 3 or shape in SPLIT2_ROUTING_EXCLUDED else pieces
+    """The piece count of _piece_route alone."""
+    return _piece_route(module, *shape)[0]
+
+
+def _piece_op(name, pieces, fmt):
+    """``(op, keywords)`` of the ``functional`` op ``name`` for _piece_route's answer: the op with ``pieces`` -- the call it always
+    was -- or, for fp16 pieces, its twin ``name_fp16``, which takes no piece count (looked up on ``SF`` at call time: tests patch
+    those names)."""
+    return (getattr(SF, name + "_fp16"), {}) if fmt == "fp16" else (getattr(SF, name), {"pieces": pieces})
 
 
 def _narrow_shape(conv):
@@ -318,8 +348,9 @@ def _conv1x1_bn_eval(x, conv, bn, relu, owner=None):
     where SPLIT_REDUCE routes it there -- on two pieces where ``owner`` (the calling block) is marked by set_teacher_pieces -- the
     library GEMM with the folded BN otherwise."""
     if _reduce_on_split(x, conv, bn):
-        return SF.conv1x1_abn_eval(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps,
-                                   "relu" if relu else "none", pieces=_pieces(owner, "1x1", conv.in_channels, conv.out_channels))
+        pieces, fmt = _piece_route(owner, "1x1", conv.in_channels, conv.out_channels)
+        op, kw = _piece_op("conv1x1_abn_eval", pieces, fmt)
+        return op(x, conv.weight, bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, "relu" if relu else "none", **kw)
     return SF.conv1x1_bn_blas(x, conv, bn, relu=relu)
 
 
@@ -349,8 +380,9 @@ def _split_conv(x, conv, form, bn=None, activation="none", residual=None, owner=
     """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, in the ``form`` _frozen_form
     gave: "wide"; "narrow", the 64-column form (the same file, include/skd_narrow.h) on its own pack; "s2", the stride-2 form
     (include/skd_stride2.h) on the wide form's pack.  ``owner``: the calling module of a frozen teacher; where set_teacher_pieces
-    marked it, "wide" without residual and "s2" run on two pieces (their own pack); the other two keep three."""
-    pieces = _pieces(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0])
+    marked it, "wide" without residual and "s2" run on two pieces (their own pack); the other two keep three.  Marked for fp16
+    pieces, "wide" without residual runs on them and "s2", which has no fp16 form, on three bf16 pieces (_piece_route)."""
+    pieces, fmt = _piece_route(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0], fp16_form=form != "s2")
     if form == "narrow":
         return SF.conv3x3_narrow_eval(x, SF.conv3x3_narrow_pack_weights(conv), conv.out_channels, conv.dilation[0], residual, conv.bias,
                                       bn, activation)
@@ -360,8 +392,8 @@ def _split_conv(x, conv, form, bn=None, activation="none", residual=None, owner=
     if residual is not None:
         return SF.conv3x3_split_res_eval(x, SF.conv3x3_pack_weights(conv, pieces=3), conv.out_channels, conv.dilation[0], residual, bn,
                                          activation, conv.bias)
-    return SF.conv3x3_split_eval(x, SF.conv3x3_pack_weights(conv, pieces=pieces), conv.out_channels, conv.dilation[0], conv.bias, bn,
-                                 activation, pieces=pieces)
+    (pack, pkw), (run, kw) = _piece_op("conv3x3_pack_weights", pieces, fmt), _piece_op("conv3x3_split_eval", pieces, fmt)
+    return run(x, pack(conv, **pkw), conv.out_channels, conv.dilation[0], conv.bias, bn, activation, **kw)
 
 
 class _ClassifierConvFn(torch.autograd.Function):
@@ -513,10 +545,10 @@ class Bottleneck(nn.Module):
             else:
                 residual = self.downsample(x)
             if tail:
-                return SF.conv1x1_abn_eval(c2, self.conv3.weight, self.bn3.running_mean, self.bn3.running_var, self.bn3.weight,
-                                           self.bn3.bias, self.bn3.eps, "relu", residual=residual,
-                                           pro=SF.abn_pack_eval_params(self.bn2),
-                                           pieces=_pieces(self, "1x1", self.conv3.in_channels, self.conv3.out_channels))
+                pieces, fmt = _piece_route(self, "1x1", self.conv3.in_channels, self.conv3.out_channels)
+                op, kw = _piece_op("conv1x1_abn_eval", pieces, fmt)
+                return op(c2, self.conv3.weight, self.bn3.running_mean, self.bn3.running_var, self.bn3.weight,
+                          self.bn3.bias, self.bn3.eps, "relu", residual=residual, pro=SF.abn_pack_eval_params(self.bn2), **kw)
             return self.bn3.forward_relu(self.conv3(out), residual)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -581,13 +613,14 @@ class PSPModule(nn.Module):
                 if not hasattr(self, "_fold_cache"):
                     self._fold_cache = {}
                 min_cin = getattr(self, "_skd_train_min_cin", None)
-                out = SF.ppm_fold_bottleneck(priors, feats, conv.weight, self._fold_cache,
-                                             split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
-                                             split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
-                                                          and (feats.shape[1], conv.out_channels, 1) not in TRAIN_ROUTING_EXCLUDED),
-                                             split_wgrad=_wgrad_routed(self, feats.shape[1], conv.out_channels, 1),
-                                             # the frozen feature half on two pieces (set_teacher_pieces)
-                                             pieces=3 if self.training else _pieces(self, "3x3", feats.shape[1], conv.out_channels, 1))
+                # the frozen feature half on two pieces, bf16 or fp16 (set_teacher_pieces)
+                pieces, fmt = (3, "bf16") if self.training else _piece_route(self, "3x3", feats.shape[1], conv.out_channels, 1)
+                fold, kw = _piece_op("ppm_fold_bottleneck", pieces, fmt)
+                out = fold(priors, feats, conv.weight, self._fold_cache,
+                           split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
+                           split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
+                                        and (feats.shape[1], conv.out_channels, 1) not in TRAIN_ROUTING_EXCLUDED),
+                           split_wgrad=_wgrad_routed(self, feats.shape[1], conv.out_channels, 1), **kw)
                 return self.bottleneck[2](self.bottleneck[1](out))
             return self.bottleneck(SF.ppm_concat(priors, feats))
         h, w = feats.size(2), feats.size(3)
@@ -741,7 +774,9 @@ def _prepack(module, convs):
             if form == "narrow":
                 SF.conv3x3_narrow_pack_weights(conv)
             elif form:
-                SF.conv3x3_pack_weights(conv, pieces=_pieces(module, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0]))
+                pieces, fmt = _piece_route(module, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0], fp16_form=form != "s2")
+                pack, kw = _piece_op("conv3x3_pack_weights", pieces, fmt)
+                pack(conv, **kw)
 
 
 def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False, stride2=False):
@@ -845,9 +880,9 @@ def route_teacher_planes(model, enable=True):
     return model
 
 
-def set_teacher_pieces(model, pieces=2):
-    """Mark ``model`` (a frozen Bottleneck network: the teacher) for ``pieces`` bf16 pieces per operand on the split core and
-    return it.
+def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
+    """Mark ``model`` (a frozen Bottleneck network: the teacher) for ``pieces`` pieces per operand, of ``piece_format``, on the
+    split core and return it.
 
     ``pieces=2`` -- an ACCURACY trade, opt-in: every call of the network that runs on the split core today takes the two-piece
     entries of include/skd_split2.h (three bf16 products instead of six): the Bottlenecks' reduce and stride-1 down-sample 1x1 GEMMs
@@ -857,14 +892,25 @@ def set_teacher_pieces(model, pieces=2):
     BasicBlocks (the student), the 64-column form, anything under grad or in training mode, the library GEMM for 512 -> 128, the
     PSP fold's matrix products and the heads are what they were.  Call it before the network's first forward, warm-up step or
     graph capture, so that the two-plane packs are made eagerly.
-    ``pieces=3`` clears the marks and drops the two-plane packs.  On a back-end without the entries ``pieces=2`` warns
-    (RuntimeWarning) and leaves three pieces."""
+    ``pieces=2, piece_format="fp16"`` -- opt-in, NOT an accuracy trade: the same modules are marked and the same call sites take the
+    entries of include_ext2/skd_split2h.h instead -- two FP16 pieces with the residual scaled by 2^11, the same three products: 22
+    significant bits per operand, the three-piece accuracy -- except the shapes of SPLIT2H_ROUTING_EXCLUDED.  The
+    stride-2 form (like the 64-column, residual-epilogue and piece-plane forms) has no fp16 twin: under this mark it runs on THREE
+    bf16 pieces, never on two.  An activation beyond +-65504 gives NaN outputs (the header's range contract).  ``piece_format``
+    without ``pieces=2`` is a ValueError, not a silent three-piece run.
+    ``pieces=3`` clears the marks and drops the two-plane packs of both formats.  On a back-end without the entries ``pieces=2``
+    warns (RuntimeWarning) and leaves three pieces."""
     if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
         raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
-    if pieces == 2 and not all(_lib.has_entry(n) for n in _SPLIT2_ENTRIES):
+    if piece_format not in ("bf16", "fp16"):
+        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
+    if piece_format == "fp16" and pieces != 2:
+        raise ValueError("piece_format='fp16' requires pieces=2, not pieces=%r" % (pieces,))
+    entries, header = (_SPLIT2H_ENTRIES, "include_ext2/skd_split2h.h") if piece_format == "fp16" else (_SPLIT2_ENTRIES, "include/skd_split2.h")
+    if pieces == 2 and not all(_lib.has_entry(n) for n in entries):
         import warnings
-        warnings.warn("set_teacher_pieces: this back-end lacks the two-piece entries (include/skd_split2.h); the teacher stays on "
-                      "three pieces", RuntimeWarning, stacklevel=2)
+        warnings.warn("set_teacher_pieces: this back-end lacks the two-piece entries (%s); the teacher stays on "
+                      "three pieces" % header, RuntimeWarning, stacklevel=2)
         pieces = 3
     teacher = any(isinstance(m, Bottleneck) for m in model.modules())      # a BasicBlock network (the student) is left untouched
     for m in model.modules():
@@ -873,12 +919,17 @@ def set_teacher_pieces(model, pieces=2):
         if pieces == 2:
             if teacher:
                 m._skd_teacher_pieces = 2
+                if piece_format == "fp16":
+                    m._skd_teacher_piece_format = "fp16"
+                else:
+                    vars(m).pop("_skd_teacher_piece_format", None)
             continue
         vars(m).pop("_skd_teacher_pieces", None)
+        vars(m).pop("_skd_teacher_piece_format", None)
         owners = ((m.conv2,) if isinstance(m, Bottleneck) else (m.dsn[0],) if isinstance(m, ResNet) else (getattr(m, "_fold_cache", {}),))
         for owner in owners:
             slot = owner if isinstance(owner, dict) else vars(owner)
-            for attr in ("_skd_conv3x3_pack2", "pack3x3_2"):
+            for attr in ("_skd_conv3x3_pack2", "pack3x3_2", "_skd_conv3x3_pack2h", "pack3x3_2h"):
                 slot.pop(attr, None)
     return model
 
