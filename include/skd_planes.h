@@ -21,7 +21,7 @@
  * csrc/conv_split_dev.hpp) that every kernel calls and that skd_planes_offset exports: callers and tests build and decode planes
  * through it and never hard-code the above.
  *
- * This header lives in include_ext/, not include/: like the entries of skd_eval.h ... skd_pairwise_split.h these are outside the
+ * An extension header: like the entries of skd_eval.h ... skd_pairwise_split.h these are outside the
  * frozen core ABI (skd.h) -- the plain-C oracle implements the core ABI only, so a back-end may lack them (the teacher then keeps
  * its fp32 link; kd_model warns once when the switch asks for them).  Same conventions as skd.h: int return, 1 = success, 0 =
  * refused with nothing launched; raw DEVICE pointers unless stated; NULL = optional tensor absent; outputs pre-sized by the

@@ -4,7 +4,7 @@
  * covers exactly what skd_split2.h covers -- csrc/conv3x3.hip's 128-column forward family and csrc/conv1x1.hip's GEMM, with
  * PIECES = 2 and the piece format kFp16 of csrc/conv_split_dev.hpp -- entry for entry, with the same argument lists and the same
  * host-side refusals.  Opt-in and off by default (networks.pspnet_combine.set_teacher_pieces(model, 2, piece_format="fp16")).
- * The header lives in include_ext2/ because include/ and include_ext/ are closed.  Like every extension entry these are outside the frozen core ABI
+ * Like every extension entry these are outside the frozen core ABI
  * (skd.h): the plain-C oracle implements the core ABI only, so a back-end may lack them (the teacher then stays on three bf16
  * pieces).  Conventions of skd.h: int return, 1 = success, 0 = refused with nothing launched; raw DEVICE pointers; NULL =
  * optional tensor absent; outputs pre-sized by the caller; asynchronous on `stream`.

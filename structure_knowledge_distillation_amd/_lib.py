@@ -1,9 +1,15 @@
-"""ctypes binding of libskd_hip.so (the C ABI declared in include/skd.h).
+"""ctypes binding of libskd_hip.so (the C ABI declared in the headers of include/).
 
 Replaces the reference's cffi shim (libs/_ext/__init__.py + libs/src/lib_cffi.cpp, which unwrap
 THCudaTensor*): here the Python side passes raw device pointers (``tensor.data_ptr()``) and the
 current HIP stream.  There is NO fallback: if the shared library is missing or a symbol cannot
 be resolved, every op raises -- a GPU box must never silently run an eager substitute.
+
+The registry is ``ABI``: one ``{name: (restype, argtypes)}`` table per header of include/, keyed by the header's base name,
+in the order the headers were added.  ``skd.h`` is the core (``SIGNATURES``): the plain-C double of oracle/ is typed from it
+and has exactly its entries.  Every other header is an extension: the double lacks its entries, so a caller that needs one
+asks ``has_entry()`` first.  A new feature adds one header to include/ and one table to ``ABI``; tests/test_abi.py checks
+header <-> table <-> exported symbols for every key, with nothing else to edit.
 """
 import ctypes
 import os
@@ -11,20 +17,8 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libskd_hip.so")
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd.h"))
-EXT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval.h"))
-MS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_eval_ms.h"))
-OHEM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_ohem.h"))
-INFER_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_infer.h"))
-TRAIN_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_train.h"))
-WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_wgrad.h"))
-NARROW_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow.h"))
-NARROW_WGRAD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_narrow_wgrad.h"))
-SHORTCUT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_shortcut.h"))
-SPLIT2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_split2.h"))
-BNSTATS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_bnstats.h"))
-STRIDE2_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_stride2.h"))
-PAIRWISE_SPLIT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "skd_pairwise_split.h"))
+INCLUDE_DIR = os.path.normpath(os.path.join(_HERE, "..", "include"))
+HEADER_PATH = os.path.join(INCLUDE_DIR, "skd.h")
 
 _c = ctypes
 _P = _c.c_void_p
@@ -33,9 +27,9 @@ _L = _c.c_int64
 _F = _c.c_float
 _D = _c.c_double
 
-# name -> (restype, argtypes); mirrors include/skd.h one to one (tests/test_abi.py checks that
-# every prototype in the header is listed here and exported by the .so).
-SIGNATURES = {
+# name -> (restype, argtypes) per header.  include/skd.h: the core ABI, every csrc/*.hip file not named below.
+ABI = {}
+ABI["skd.h"] = {
     "skd_abi_version": (_I, []),
     "skd_target_arch": (_I, []),
     "skd_bn_mean_var": (_I, [_I, _I, _I, _P, _P, _P, _P]),
@@ -147,10 +141,9 @@ SIGNATURES = {
     "skd_abn_sync_form_counts": (_I, [_P]),
 }
 
-# Entry points of libskd_hip.so declared in include/skd_eval.h, outside the core ABI above: the plain-C oracle is typed
-# from SIGNATURES alone and does not have them, so an op that needs one asks has_entry() first (tests/test_sliding_eval_cpu.py
-# checks header <-> table <-> exported symbols the way tests/test_abi.py does for the core).
-EXT_SIGNATURES = {
+# include/skd_eval.h (csrc/evaluate_sliding.hip, csrc/conv3x3.hip, csrc/conv1x1.hip): sliding-window evaluation, the frozen split
+# 3x3 convolution and the split GEMM's geometry queries.  The ops that need them raise on a back-end without them.
+ABI["skd_eval.h"] = {
     "skd_seg_sliding": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "skd_conv3x3_split_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "skd_conv3x3_split_pack_bytes": (_L, [_I, _I]),
@@ -160,76 +153,60 @@ EXT_SIGNATURES = {
     "skd_conv1x1_abn_tile_of": (_I, [_L, _I, _I, _I, _L, _L, _P]),
 }
 
-# Entry points declared in include/skd_eval_ms.h (csrc/evaluate_multiscale.hip): extension entries like the ones above, in a
-# table of their own (tests/test_multiscale_eval_cpu.py checks header <-> table <-> exported symbols, tests/test_multiscale_eval_gpu.py
-# holds their guard-band cases; DESIGN.md says why they are not simply rows of EXT_SIGNATURES).
-MS_SIGNATURES = {
+# include/skd_eval_ms.h (csrc/evaluate_multiscale.hip): multi-scale and flip evaluation.
+ABI["skd_eval_ms.h"] = {
     "skd_zoom_linear": (_I, [_I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
     "skd_seg_multiscale": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
-# Entry points declared in include/skd_ohem.h (csrc/ce_ohem.hip): the OHEM criterion, extension entries in a table of their own
-# for the reasons of MS_SIGNATURES (tests/test_ohem_cpu.py checks header <-> table <-> exported symbols, tests/test_ohem_gpu.py
-# holds their guard-band cases).
-OHEM_SIGNATURES = {
+# include/skd_ohem.h (csrc/ce_ohem.hip): the OHEM criterion.
+ABI["skd_ohem.h"] = {
     "skd_ce_ohem_workspace_floats": (_L, [_I, _I, _I, _I, _I, _I, _I]),
     "skd_ohem_threshold": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
     "skd_ce_ohem_dsn_forward": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
-# Entry points declared in include/skd_infer.h (csrc/conv3x3.hip): the student's fused inference path, extension entries in a
-# table of their own like the two above (tests/test_student_infer_cpu.py checks header <-> table <-> exported symbols,
-# tests/test_student_infer_gpu.py holds the guard-band case).  A back-end without them leaves the BasicBlocks on the op sequence
-# they ran before: nothing raises.
-INFER_SIGNATURES = {
+# include/skd_infer.h (csrc/conv3x3.hip): the student's fused inference path.  A back-end without them leaves the BasicBlocks on
+# the op sequence they ran before: nothing raises.
+ABI["skd_infer.h"] = {
     "skd_conv3x3_split_res_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
 }
 
-# Entry points declared in include/skd_train.h (csrc/conv3x3.hip): the training student's 3x3 convolutions on the split core,
-# extension entries in a table of their own like the three above (tests/test_conv3x3_train_cpu.py checks header <-> table <->
-# exported symbols, tests/test_conv3x3_train_gpu.py holds the guard-band case).  A back-end without them leaves the student's
-# convolutions on the library: nothing raises.
-TRAIN_SIGNATURES = {
+# include/skd_train.h (csrc/conv3x3.hip): the training student's 3x3 convolutions on the split core.  A back-end without them
+# leaves the student's convolutions on the library: nothing raises.
+ABI["skd_train.h"] = {
     "skd_conv3x3_split_train_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "skd_conv3x3_split_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
 }
 
-# Entry points declared in include/skd_wgrad.h (csrc/conv3x3_wgrad.hip): the weight gradient of those convolutions on the split
-# core, extension entries in a table of their own like the four above (tests/test_conv3x3_wgrad_cpu.py checks header <-> table
-# <-> exported symbols, tests/test_conv3x3_wgrad_gpu.py holds the guard-band cases).  A back-end without them leaves the weight
-# gradients on the library: nothing raises.
-WGRAD_SIGNATURES = {
+# include/skd_wgrad.h (csrc/conv3x3_wgrad.hip): the weight gradient of those convolutions on the split core.  A back-end without
+# them leaves the weight gradients on the library: nothing raises.
+ABI["skd_wgrad.h"] = {
     "skd_conv3x3_split_wgrad_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "skd_conv3x3_split_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "skd_conv3x3_split_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
 }
 
-# Entry points declared in include/skd_narrow.h (csrc/conv3x3.hip): the 64-column form of the split-core 3x3 convolution,
-# extension entries in a table of their own like the five above (tests/test_conv3x3_narrow_cpu.py checks header <-> table <->
-# exported symbols, tests/test_conv3x3_narrow_gpu.py holds the guard-band cases).  A back-end without them leaves the 64-channel
-# convolutions where they were: nothing raises.
-NARROW_SIGNATURES = {
+# include/skd_narrow.h (csrc/conv3x3.hip): the 64-column form of the split-core 3x3 convolution.  A back-end without them leaves
+# the 64-channel convolutions where they were: nothing raises.
+ABI["skd_narrow.h"] = {
     "skd_conv3x3_narrow_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "skd_conv3x3_narrow_pack_bytes": (_L, [_I, _I]),
     "skd_conv3x3_narrow_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
     "skd_conv3x3_narrow_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
 }
 
-# Entry points declared in include/skd_narrow_wgrad.h (csrc/conv3x3_wgrad.hip, the 128 x 64 tile form): the weight gradient of the
-# convolutions with a 64-channel side, extension entries in a table of their own like the six above
-# (tests/test_conv3x3_narrow_wgrad_cpu.py checks header <-> table <-> exported symbols, tests/test_conv3x3_narrow_wgrad_gpu.py
-# holds the guard-band cases).  A back-end without them leaves those weight gradients on the library: nothing raises.
-NARROW_WGRAD_SIGNATURES = {
+# include/skd_narrow_wgrad.h (csrc/conv3x3_wgrad.hip, the 128 x 64 tile form): the weight gradient of the convolutions with a
+# 64-channel side.  A back-end without them leaves those weight gradients on the library: nothing raises.
+ABI["skd_narrow_wgrad.h"] = {
     "skd_conv3x3_narrow_wgrad_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "skd_conv3x3_narrow_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
     "skd_conv3x3_narrow_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
 }
 
-# Entry points declared in include/skd_shortcut.h (csrc/conv1x1_train.hip; the weight gradient: csrc/conv3x3_wgrad.hip, its
-# one-tap form): the training student's 1x1 down-sample convolutions on the split core, extension entries in a table of their own
-# like the seven above (tests/test_conv1x1_train_cpu.py checks header <-> table <-> exported symbols, tests/test_conv1x1_train_gpu.py
-# holds the guard-band cases).  A back-end without them leaves the shortcut convolutions on the library: nothing raises.
-SHORTCUT_SIGNATURES = {
+# include/skd_shortcut.h (csrc/conv1x1_train.hip; the weight gradient: csrc/conv3x3_wgrad.hip, its one-tap form): the training
+# student's 1x1 down-sample convolutions on the split core.  A back-end without them leaves them on the library: nothing raises.
+ABI["skd_shortcut.h"] = {
     "skd_conv1x1_train_supported": (_I, [_I, _I, _I, _I, _I, _I, _I]),
     "skd_conv1x1_train_fwd_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "skd_conv1x1_train_fwd_cols64_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
@@ -239,11 +216,9 @@ SHORTCUT_SIGNATURES = {
     "skd_conv1x1_train_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _P]),
 }
 
-# Entry points declared in include/skd_split2.h (csrc/conv3x3.hip, csrc/conv1x1.hip with two pieces per operand): the frozen
-# teacher's reduced-precision mode, extension entries in a table of their own like the nine above (tests/test_split2_cpu.py checks
-# header <-> table <-> exported symbols, tests/test_split2_gpu.py holds the guard-band cases).  A back-end without them leaves the
-# teacher on three pieces (pspnet_combine.set_teacher_pieces warns): nothing raises.
-SPLIT2_SIGNATURES = {
+# include/skd_split2.h (csrc/conv3x3.hip, csrc/conv1x1.hip with two pieces per operand): the frozen teacher's reduced-precision
+# mode.  A back-end without them leaves the teacher on three pieces (pspnet_combine.set_teacher_pieces warns): nothing raises.
+ABI["skd_split2.h"] = {
     "skd_conv3x3_split2_pack_bytes": (_L, [_I, _I]),
     "skd_conv3x3_split2_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
     "skd_conv3x3_split2_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
@@ -251,49 +226,38 @@ SPLIT2_SIGNATURES = {
     "skd_conv1x1_abn2_pro_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _F, _P]),
 }
 
-# Entry points declared in include/skd_bnstats.h (csrc/conv3x3.hip with STATS, csrc/abn_nhwc.hip): the training forward of the
-# student's 3x3 convolutions with the batch-norm statistics records from its epilogue, and their finalize, extension entries in a
-# table of their own like the ten above (tests/test_conv3x3_bnstats_cpu.py checks header <-> table <-> exported symbols,
-# tests/test_conv3x3_bnstats_gpu.py holds the guard-band cases).  A back-end without them leaves the convolutions and the ABN
-# forward behind them where they were: nothing raises.
-BNSTATS_SIGNATURES = {
+# include/skd_bnstats.h (csrc/conv3x3.hip with STATS, csrc/abn_nhwc.hip): the student's training 3x3 forward with the batch-norm
+# statistics records from its epilogue, and their finalize.  A back-end without them leaves the convolutions and the ABN forward
+# behind them where they were: nothing raises.
+ABI["skd_bnstats.h"] = {
     "skd_conv3x3_bnstats_floats": (_L, [_L, _I]),
     "skd_conv3x3_split_stats_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P]),
     "skd_conv3x3_narrow_stats_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _L, _P]),
     "skd_abn_stats_from_partials_nhwc": (_I, [_L, _I, _P, _L, _P, _P, _P, _P, _F, _P]),
 }
 
-# Entry points declared in include/skd_stride2.h (csrc/conv3x3.hip with STRIDE = 2): the stride-2 frozen forward of the 128-column
-# 3x3 family -- the teacher's layer2.0 conv2 and the student's layer2.0 conv1 in its inference form -- extension entries in a table
-# of their own like the eleven above (tests/test_conv3x3_stride2_cpu.py checks header <-> table <-> exported symbols and sweeps the
-# host-only row map, tests/test_conv3x3_stride2_gpu.py holds the guard-band cases).  A back-end without them leaves those
-# convolutions on the library: nothing raises.
-STRIDE2_SIGNATURES = {
+# include/skd_stride2.h (csrc/conv3x3.hip with STRIDE = 2): the stride-2 frozen forward of the 128-column 3x3 family.  A back-end
+# without them leaves those convolutions on the library: nothing raises.
+ABI["skd_stride2.h"] = {
     "skd_conv3x3_split_s2_supported": (_I, [_I, _I, _I, _I, _I, _I]),
     "skd_conv3x3_split_s2_taps": (_I, [_I, _I, _L, _P, _P]),
     "skd_conv3x3_split_s2_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _P]),
 }
 
-# Entry points declared in include/skd_pairwise_split.h (csrc/pairwise_split.hip): the Gram + loss and the backward product of the
-# pair-wise similarity loss on the split core, twins of skd_pairwise_gram_loss / skd_pairwise_backward with the same argument
-# lists, extension entries in a table of their own like the twelve above (tests/test_pairwise_split_cpu.py checks header <-> table
-# <-> exported symbols, tests/test_pairwise_split_gpu.py holds the guard-band cases).  A back-end without them leaves the loss on
-# the fp32 kernels (kd_model warns when the switch asks for them): nothing raises.
-PAIRWISE_SPLIT_SIGNATURES = {
+# include/skd_pairwise_split.h (csrc/pairwise_split.hip): the pair-wise loss's Gram + loss and backward product on the split core,
+# twins of skd_pairwise_gram_loss / skd_pairwise_backward.  A back-end without them leaves the loss on the fp32 kernels (kd_model
+# warns when the switch asks for them): nothing raises.
+ABI["skd_pairwise_split.h"] = {
     "skd_pairwise_split_workspace_floats": (_L, [_I, _I, _I, _I]),
     "skd_pairwise_split_gram_loss": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "skd_pairwise_split_backward_workspace_floats": (_L, [_I, _I, _I]),
     "skd_pairwise_split_backward": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 
-# Entry points declared in include_ext/skd_planes.h (csrc/planes.hip, csrc/conv1x1.hip and csrc/conv3x3.hip with PLANES): piece
-# planes -- an activation map handed from the frozen teacher's split reduce GEMM to its 3x3 convolution as the three bf16 pieces
-# the consumer reads -- extension entries in a table of their own like the thirteen above; their header lives in include_ext/
-# because include/ is closed (tests/test_conv_planes_cpu.py checks header <-> table <-> exported symbols and sweeps the host-only
-# offset map, tests/test_conv_planes_gpu.py holds the guard-band cases).  A back-end without them leaves the teacher's link on
-# fp32 (kd_model warns when the switch asks for them): nothing raises.
-PLANES_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include_ext", "skd_planes.h"))
-PLANES_SIGNATURES = {
+# include/skd_planes.h (csrc/planes.hip, csrc/conv1x1.hip and csrc/conv3x3.hip with PLANES): piece planes, an activation map handed
+# from the frozen teacher's split reduce GEMM to its 3x3 convolution as three bf16 pieces.  A back-end without them leaves the
+# teacher's link on fp32 (kd_model warns when the switch asks for them): nothing raises.
+ABI["skd_planes.h"] = {
     "skd_planes_supported": (_I, [_I]),
     "skd_planes_bytes": (_I, [_L, _I, _P]),
     "skd_planes_offset": (_I, [_L, _I, _L, _I, _I, _P]),
@@ -303,21 +267,18 @@ PLANES_SIGNATURES = {
     "skd_conv3x3_split_planes_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _I, _P]),
 }
 
-# Entry points declared in include_ext2/skd_split2h.h (csrc/conv3x3.hip, csrc/conv1x1.hip with two FP16 pieces per operand and a
-# scaled residual): the frozen teacher's two-piece mode at the three-piece accuracy, twins of SPLIT2_SIGNATURES with the same
-# argument lists, extension entries in a table of their own like the fourteen above (tests/test_split2h_cpu.py checks header <->
-# table <-> exported symbols, tests/test_split2h_gpu.py holds the guard-band cases).  include/ is closed at 14 headers and
-# include_ext/ at skd_planes.h (tests/test_conv_planes_cpu.py pins both listings and the count of *_SIGNATURES tables here), so
-# the header lives in include_ext2/ and the table is named SPLIT2H_TABLE.  A back-end without them leaves the teacher on
-# three pieces (pspnet_combine.set_teacher_pieces warns): nothing raises.
-SPLIT2H_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include_ext2", "skd_split2h.h"))
-SPLIT2H_TABLE = {
+# include/skd_split2h.h (csrc/conv3x3.hip, csrc/conv1x1.hip with two FP16 pieces per operand and a scaled residual): the frozen
+# teacher's two-piece mode at the three-piece accuracy, twins of skd_split2.h.  A back-end without them leaves the teacher on three
+# pieces (pspnet_combine.set_teacher_pieces warns): nothing raises.
+ABI["skd_split2h.h"] = {
     "skd_conv3x3_split2h_pack_bytes": (_L, [_I, _I]),
     "skd_conv3x3_split2h_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
     "skd_conv3x3_split2h_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
     "skd_conv1x1_abn2h_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _P]),
     "skd_conv1x1_abn2h_pro_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _F, _P]),
 }
+
+SIGNATURES = ABI["skd.h"]      # the core ABI: what the plain-C double of oracle/ is typed from
 
 _lib = None
 _test_backend = None  # see install_test_backend()
@@ -327,11 +288,36 @@ class SkdLibraryError(RuntimeError):
     pass
 
 
-def header_prototypes(path=HEADER_PATH):
-    """Names of all functions declared in include/skd.h (used by tests/test_abi.py)."""
+def header_path(header):
+    """Path of the header ``header`` (a key of ``ABI``) in include/."""
+    return os.path.join(INCLUDE_DIR, header)
+
+
+def signature(name):
+    """(restype, argtypes) of the entry ``name``, whichever header declares it (names are disjoint across headers)."""
+    for table in ABI.values():
+        if name in table:
+            return table[name]
+    raise KeyError(name)
+
+
+def _header_text(path):
     with open(path) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(skd_[a-z0-9_]+)\s*\(", text)))
+        return re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
+
+
+def header_prototypes(path=HEADER_PATH):
+    """Names of all functions declared in the header at ``path`` (used by tests/test_abi.py)."""
+    return sorted(set(re.findall(r"\b(skd_[a-z0-9_]+)\s*\(", _header_text(path))))
+
+
+def header_arg_counts(path=HEADER_PATH):
+    """{name: number of arguments} of the prototypes in the header at ``path`` (used by tests/test_abi.py)."""
+    counts = {}
+    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", _header_text(path), flags=re.S):
+        args = m.group(2).strip()
+        counts[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
+    return counts
 
 
 def load(path=None):
@@ -348,10 +334,7 @@ def load(path=None):
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover
         raise SkdLibraryError("cannot load %s: %s" % (path, e))
-    for table in (SIGNATURES, EXT_SIGNATURES, MS_SIGNATURES, OHEM_SIGNATURES, INFER_SIGNATURES, TRAIN_SIGNATURES,
-                  WGRAD_SIGNATURES, NARROW_SIGNATURES, NARROW_WGRAD_SIGNATURES, SHORTCUT_SIGNATURES, SPLIT2_SIGNATURES,
-                  BNSTATS_SIGNATURES, STRIDE2_SIGNATURES, PAIRWISE_SPLIT_SIGNATURES, PLANES_SIGNATURES,
-                  SPLIT2H_TABLE):
+    for table in ABI.values():
         for name, (res, args) in table.items():
             try:
                 fn = getattr(lib, name)

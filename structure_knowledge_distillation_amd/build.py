@@ -1,4 +1,4 @@
-"""Build libskd_hip.so (all gfx950 kernels + the C ABI of include/skd.h) in-tree with hipcc.
+"""Build libskd_hip.so (all gfx950 kernels + the C ABI of include/*.h) in-tree with hipcc.
 
     python -m structure_knowledge_distillation_amd.build [--force] [--verbose]
 
@@ -13,8 +13,6 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
-INCLUDE_EXT = os.path.normpath(os.path.join(HERE, "..", "include_ext"))      # headers added since include/ was closed (skd_planes.h)
-INCLUDE_EXT2 = os.path.normpath(os.path.join(HERE, "..", "include_ext2"))    # ... and since include_ext/ was (skd_split2h.h)
 LIB_PATH = os.path.join(HERE, "libskd_hip.so")
 STAMP = LIB_PATH + ".stamp"
 ARCH = "gfx950"
@@ -30,8 +28,6 @@ def _digest():
     h = hashlib.sha256()
     files = sources() + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
     files += sorted(os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h"))
-    files += sorted(os.path.join(INCLUDE_EXT, f) for f in os.listdir(INCLUDE_EXT) if f.endswith(".h"))
-    files += sorted(os.path.join(INCLUDE_EXT2, f) for f in os.listdir(INCLUDE_EXT2) if f.endswith(".h"))
     for f in files:
         h.update(f.encode())
         with open(f, "rb") as fh:
@@ -53,7 +49,7 @@ def build(force=False, verbose=False):
         with open(STAMP) as fh:
             if fh.read().strip() == digest:
                 return LIB_PATH
-    cmd = [hipcc_path()] + FLAGS + ["-I", INCLUDE, "-I", INCLUDE_EXT, "-I", INCLUDE_EXT2, "-I", CSRC] + sources() + ["-o", LIB_PATH]
+    cmd = [hipcc_path()] + FLAGS + ["-I", INCLUDE, "-I", CSRC] + sources() + ["-o", LIB_PATH]
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -114,7 +114,7 @@ __device__ __forceinline__ void stage_store(const Staging<TM> &s, uint4 *stage, 
 }
 
 // The accumulator set of the products below a0 b0.  bf16 pieces: the one set `acc` itself (lo and hi are the same array, see
-// tile_mma).  fp16 pieces (include_ext2/skd_split2h.h): a set of its own -- those products carry the factor 2^11 -- of 32 WM registers.
+// tile_mma).  fp16 pieces (include/skd_split2h.h): a set of its own -- those products carry the factor 2^11 -- of 32 WM registers.
 template <int WM, int FMT>
 struct LowSet {
   typedef f32x16 Set[WM][2];
@@ -143,7 +143,7 @@ struct Tile1 {
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, kTN, false, PIECES, FMT>(stage, low, acc); }
 };
 
-// PLANES (include_ext/skd_planes.h): the epilogue of one 32 x 32 accumulator block that writes the three bf16 pieces of
+// PLANES (include/skd_planes.h): the epilogue of one 32 x 32 accumulator block that writes the three bf16 pieces of
 // act(bn(acc)) -- store_block's fp32 value, the same expression -- into the piece planes of an (M, N) map (planes_offset,
 // conv_split_dev.hpp) and no fp32 output.  A lane holds one column of sixteen rows, and neighbouring columns' pieces are
 // neighbouring bf16, so lanes l and l ^ 1 trade every other row first: the even lane keeps rows q = 0, 2, ... of both columns, the
@@ -315,8 +315,8 @@ __host__ __device__ __forceinline__ TileOf conv1x1_tile_of(unsigned block, int64
 
 // PIECES = 2 (include/skd_split2.h): two pieces per operand, the three products a0 b1, a1 b0, a0 b0 into the one accumulator; the
 // grid, the tile order and the half-height round are those of the three-piece launch (32 KB of LDS + the prologue's table).
-// PLANES (include_ext/skd_planes.h): Y is the piece planes of the output (conv1x1_tile); grid and tile order as the fp32 launch.
-// FMT = kFp16 (include_ext2/skd_split2h.h): two fp16 pieces, the three products into TWO accumulator sets (128 registers at 128 rows),
+// PLANES (include/skd_planes.h): Y is the piece planes of the output (conv1x1_tile); grid and tile order as the fp32 launch.
+// FMT = kFp16 (include/skd_split2h.h): two fp16 pieces, the three products into TWO accumulator sets (128 registers at 128 rows),
 // so the kernel is compiled for two workgroups per CU; grid, tile order and half-height round stay the three-piece launch's.
 constexpr int conv1x1_wgs(int FMT) { return FMT == kFp16 ? 2 : kMinWG; }
 template <int ACT, bool HAS_RES, bool PRO, bool NT, int PIECES = 3, bool PLANES = false, int FMT = kBf16>
@@ -482,7 +482,7 @@ int skd_conv1x1_abn2_nhwc(int64_t M, int K, int N, const float *x, const float *
   return conv1x1_dispatch<2>(M, K, N, x, w, residual, out, mean, var, weight, bias, nullptr, eps, activation, slope, stream);
 }
 
-// include_ext/skd_planes.h: the plain three-piece GEMM with the pieces of its epilogue's value written to piece planes.
+// include/skd_planes.h: the plain three-piece GEMM with the pieces of its epilogue's value written to piece planes.
 int skd_conv1x1_abn_planes_nhwc(int64_t M, int K, int N, const float *x, const float *w, void *planes_out, const float *mean,
                                 const float *var, const float *weight, const float *bias, float eps, int activation, float slope,
                                 skd_stream_t stream) {
@@ -508,7 +508,7 @@ int skd_conv1x1_abn2_pro_nhwc(int64_t M, int K, int N, const float *x, const flo
   return conv1x1_dispatch<2>(M, K, N, x, w, residual, out, mean, var, weight, bias, ppack, eps, activation, slope, stream);
 }
 
-// include_ext2/skd_split2h.h: the same two entries on two fp16 pieces per operand with the scaled residual.
+// include/skd_split2h.h: the same two entries on two fp16 pieces per operand with the scaled residual.
 int skd_conv1x1_abn2h_nhwc(int64_t M, int K, int N, const float *x, const float *w, const float *residual, float *out,
                            const float *mean, const float *var, const float *weight, const float *bias, float eps,
                            int activation, float slope, skd_stream_t stream) {

@@ -71,7 +71,7 @@ static_assert(conv3x3_lds(kTN) == kConvLds, "the 128-column form fills both stag
 static_assert(conv3x3_lds(kTN, 2) == conv_lds(2) && tile_chunks(kTN, 2) == 2 * kThreads, "... of two pieces too: 32 KB, two copies");
 
 // One panel row's four k of a K-tile in the staging registers: the fp32 quad that stage_store3 splits, or -- PLANES
-// (include_ext/skd_planes.h): the activation is the piece planes of the map -- its three 8-byte piece quads, ready to store: two
+// (include/skd_planes.h): the activation is the piece planes of the map -- its three 8-byte piece quads, ready to store: two
 // registers more per panel row and staging set, four per 64 rows of the tile over k_loop's two sets.
 // (Native vector types, one array per piece: with HIP's uint2 / uint4 structs in this set the copies of the first weight chunk
 // stayed memcpys and the set in scratch, 56 bytes per lane.)
@@ -250,7 +250,7 @@ __device__ __forceinline__ void block_stats(const f32x16 &acc, float *__restrict
 // One output tile of TM x TN pixels x channels.  HAS_RES: the residual R (the output's shape) is added behind the BN expression,
 // in front of the activation (store_block): the second convolution of a BasicBlock.  STRIDE = 2: M counts the rows of the
 // (B, Ho, Wo) output, H and W stay the input's, and the rows' addresses and masks come from s2_row_map; STRIDE = 1 is the code
-// without it.  PLANES (include_ext/skd_planes.h): X is the piece planes of the (M, Cin) input map; the rows' addresses are byte
+// without it.  PLANES (include/skd_planes.h): X is the piece planes of the (M, Cin) input map; the rows' addresses are byte
 // offsets of that layout and the staging set holds piece quads (stage_load3_a, stage_store3); masks, tap cursor, K loop, product order
 // and epilogue are the code without it.
 template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
@@ -387,7 +387,7 @@ void conv3x3_split_kernel(
 // a wave's 64 lanes are 64 consecutive c, so each of its eight loads reads a run of 64 elements at stride sc -- 256 contiguous
 // bytes of a channels-last weight (sc = 1: the training student's, and the PSP bottleneck's channel slice).
 // PIECES = 2 (include/skd_split2.h): the first two planes alone, 4 TN chunks per (column tile, K-tile).
-// FMT = kFp16 (include_ext2/skd_split2h.h): the two fp16 planes p0 and the scaled p1 of split4_f16, the same 4 TN chunks.
+// FMT = kFp16 (include/skd_split2h.h): the two fp16 planes p0 and the scaled p1 of split4_f16, the same 4 TN chunks.
 template <int TN, int PIECES = 3, int FMT = kBf16>
 __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
     const float *__restrict__ Wt, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int Cin, int Cout, int64_t fwd_tiles,
@@ -546,7 +546,7 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
 #undef SKD_CONV3X3_CASE
 }
 
-// include_ext/skd_planes.h: run3<kTN> without residual whose activation operand is the piece planes of the (B, H, W, Cin) map --
+// include/skd_planes.h: run3<kTN> without residual whose activation operand is the piece planes of the (B, H, W, Cin) map --
 // run3's refusals, the planes pointer in x's place (16-byte aligned, as x).
 static int run3_planes(int B, int H, int W, int Cin, int Cout, int dilation, const void *planes, const void *wpack, float *out,
                        const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
@@ -691,7 +691,7 @@ int skd_conv3x3_split2_nhwc(int B, int H, int W, int Cin, int Cout, int dilation
                       slope, geometry, 3, stream);
 }
 
-// include_ext2/skd_split2h.h: the same family on two FP16 pieces per operand with the scaled residual, and its two-plane weight image.
+// include/skd_split2h.h: the same family on two FP16 pieces per operand with the scaled residual, and its two-plane weight image.
 int64_t skd_conv3x3_split2h_pack_bytes(int Cin, int Cout) { return pack_bytes3<kTN, 2>(Cin, Cout); }
 
 int skd_conv3x3_split2h_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
@@ -742,7 +742,7 @@ int skd_conv3x3_narrow_stats_nhwc(int B, int H, int W, int Cin, int Cout, int di
   return run3_stats<kNarrowTN>(B, H, W, Cin, Cout, dilation, x, wpack, out, conv_bias, geometry, 1, stats, stats_floats, stream);
 }
 
-// include_ext/skd_planes.h: the wide stride-1 frozen forward on the piece planes of its input.
+// include/skd_planes.h: the wide stride-1 frozen forward on the piece planes of its input.
 int skd_conv3x3_split_planes_nhwc(int B, int H, int W, int Cin, int Cout, const void *planes_in, const void *wpack, float *out,
                                   const float *conv_bias, const float *mean, const float *var, const float *weight,
                                   const float *bias, float eps, int activation, float slope, int dilation, int geometry,

@@ -64,7 +64,7 @@ __device__ __forceinline__ void split4(float4 v, uint2 &p0, uint2 &p1) {
   p1.x = pack_bf16(v.x, v.y);
   p1.y = pack_bf16(v.z, v.w);
 }
-// The piece FORMAT, beside PIECES: kBf16 everywhere but in the forms of include_ext2/skd_split2h.h, which cut an operand into two
+// The piece FORMAT, beside PIECES: kBf16 everywhere but in the forms of include/skd_split2h.h, which cut an operand into two
 // FP16 pieces (PIECES = 2 only).  An fp16 piece carries 11 significant bits, so two carry 22 -- but fp16's exponent is narrow: the
 // residual v - fp16(v), about 2^-11 |v|, would be an fp16 subnormal for every |v| < 0.125.  It is therefore SCALED by 2^11 (exact)
 // before it is converted: v ~ p0 + 2^-11 p1.  The products a0 b1 and a1 b0 then carry the factor 2^11 and go into `lo`, a0 b0
@@ -112,7 +112,7 @@ __device__ __forceinline__ void split_store(float4 v, uint2 *dst, int plane) {
   dst[2 * plane] = p2;
 }
 
-// PIECE PLANES (include_ext/skd_planes.h): an (M, C) fp32 activation map stored as its three bf16 pieces, C % 16 == 0, so that a
+// PIECE PLANES (include/skd_planes.h): an (M, C) fp32 activation map stored as its three bf16 pieces, C % 16 == 0, so that a
 // consumer stages a K-tile without split4.  THE layout, the one function every kernel and the host entry skd_planes_offset use:
 // byte offset of piece `piece` of element (row, channel c).  Interleaved per QUAD of four channels: a row's four consecutive k
 // are 24 contiguous bytes (piece 0 | piece 1 | piece 2, 8 bytes each), a row's quads follow each other, rows follow each other:

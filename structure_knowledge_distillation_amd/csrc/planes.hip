@@ -1,4 +1,4 @@
-// planes.hip -- piece planes (include_ext/skd_planes.h): an (M, C) fp32 channels-last activation map stored as the three bf16
+// planes.hip -- piece planes (include/skd_planes.h): an (M, C) fp32 channels-last activation map stored as the three bf16
 // pieces of the split core, p0 = bf16(v), p1 = bf16(v - p0), p2 = bf16(v - p0 - p1) (split4, conv_split_dev.hpp), in the layout of
 // planes_offset (the same header: one function for these kernels, the producer's epilogue in conv1x1.hip, the consumer's loader
 // in conv3x3.hip and the host entry below).

@@ -475,7 +475,7 @@ def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, spli
     `split_wgrad`: with `split_train`, the weight gradient of that slice on the split core too (conv3x3_split_train's ``wgrad``).
     `pieces` = 2: with `split3x3`, the frozen feature-map convolution on the two-piece core (conv3x3_split_eval's ``pieces``), its
     pack under a key of its own in `cache`; the fold's matrix products and the training form are what they were.
-    `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include_ext2/skd_split2h.h), its pack under a third key."""
+    `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include/skd_split2h.h), its pack under a third key."""
     _check_piece_format(_check_pieces(pieces), piece_format)
     import torch.nn.functional as F
     cm = priors[0].shape[1]
@@ -717,7 +717,7 @@ def _need_split2_entry(name):
         raise NotImplementedError("the active back-end does not provide %s (include/skd_split2.h)" % name)
 
 
-# include_ext2/skd_split2h.h: the two-piece form on FP16 pieces with the scaled residual, entry for entry the twin of skd_split2.h
+# include/skd_split2h.h: the two-piece form on FP16 pieces with the scaled residual, entry for entry the twin of skd_split2.h
 _SPLIT2H_ENTRIES = {"skd_conv3x3_split2_pack_bytes": "skd_conv3x3_split2h_pack_bytes",
                     "skd_conv3x3_split2_pack_weights": "skd_conv3x3_split2h_pack_weights",
                     "skd_conv3x3_split2_nhwc": "skd_conv3x3_split2h_nhwc",
@@ -726,11 +726,11 @@ _SPLIT2H_ENTRIES = {"skd_conv3x3_split2_pack_bytes": "skd_conv3x3_split2h_pack_b
 
 
 def _check_piece_format(pieces, piece_format):
-    """``piece_format``: "bf16" (every form so far) or "fp16" (include_ext2/skd_split2h.h), which exists for ``pieces`` = 2 alone."""
+    """``piece_format``: "bf16" (every form so far) or "fp16" (include/skd_split2h.h), which exists for ``pieces`` = 2 alone."""
     if piece_format not in ("bf16", "fp16"):
         raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
     if piece_format == "fp16" and pieces != 2:
-        raise ValueError("piece_format='fp16' requires pieces=2 (include_ext2/skd_split2h.h), not pieces=%r" % (pieces,))
+        raise ValueError("piece_format='fp16' requires pieces=2 (include/skd_split2h.h), not pieces=%r" % (pieces,))
     return piece_format
 
 
@@ -739,30 +739,30 @@ def _split2_entry(name, piece_format):
     if piece_format == "fp16":
         name = _SPLIT2H_ENTRIES[name]
         if not _lib.has_entry(name):
-            raise NotImplementedError("the active back-end does not provide %s (include_ext2/skd_split2h.h)" % name)
+            raise NotImplementedError("the active back-end does not provide %s (include/skd_split2h.h)" % name)
         return name
     _need_split2_entry(name)
     return name
 
 
-# include_ext/skd_planes.h: piece planes -- an activation map as the three bf16 pieces the split core's consumer reads
+# include/skd_planes.h: piece planes -- an activation map as the three bf16 pieces the split core's consumer reads
 _PLANES_PRODUCER, _PLANES_CONSUMER = "skd_conv1x1_abn_planes_nhwc", "skd_conv3x3_split_planes_nhwc"
 _PLANES_ENTRIES = ("skd_planes_supported", "skd_planes_bytes", "skd_planes_offset", "skd_planes_split_nhwc", "skd_planes_join_nhwc",
                    _PLANES_PRODUCER, _PLANES_CONSUMER)
 
 
 def planes_supported():
-    """True when the active back-end has the seven entries of include_ext/skd_planes.h (the tests' plain-C double has none)."""
+    """True when the active back-end has the seven entries of include/skd_planes.h (the tests' plain-C double has none)."""
     return all(_lib.has_entry(n) for n in _PLANES_ENTRIES)
 
 
 def _need_planes():
     if not planes_supported():
-        raise NotImplementedError("the active back-end does not provide the entries of include_ext/skd_planes.h")
+        raise NotImplementedError("the active back-end does not provide the entries of include/skd_planes.h")
 
 
 class Planes:
-    """The piece planes of a (B, C, H, W) fp32 channels-last map (include_ext/skd_planes.h): ``data``, the byte tensor of
+    """The piece planes of a (B, C, H, W) fp32 channels-last map (include/skd_planes.h): ``data``, the byte tensor of
     skd_planes_bytes(M, C) bytes in the layout of skd_planes_offset; ``M`` = B * H * W rows, ``C`` channels, ``shape`` =
     (B, H, W, C).  Made by ``conv1x1_abn_planes_eval`` or ``planes_split``, read by ``conv3x3_split_eval`` in place
     of ``x`` and by ``planes_join``.  Holds exactly the bf16 pieces the consumer would cut from the fp32 map itself."""
@@ -822,7 +822,7 @@ def planes_join(planes):
 
 def conv1x1_abn_planes_eval(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01):
     """``conv1x1_abn_eval(...)`` -- three pieces, no residual, no ``pro`` -- with the result returned as a ``Planes``
-    (include_ext/skd_planes.h): the three bf16 pieces of the very fp32 values that call would return, written by the GEMM's epilogue
+    (include/skd_planes.h): the three bf16 pieces of the very fp32 values that call would return, written by the GEMM's epilogue
     (skd_conv1x1_abn_planes_nhwc) for ``conv3x3_split_eval`` to read in place of ``x``; no fp32 tensor is written.  (An op of its
     own and not a keyword of conv1x1_abn_eval: that op's bound arguments are what tests/golden/routing_census.json records call by
     call.)  Inference only; a back-end without the entries raises."""
@@ -856,11 +856,11 @@ def _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, e
     ``pieces`` = 2: the reduced-precision form of include/skd_split2.h -- two bf16 pieces per operand and the three products
     a0 b1, a1 b0, a0 b0: about 4e-6 of the output's largest magnitude per product instead of 3e-7 (tests/split2_ref.py is its model,
     tests/test_split2_gpu.py the comparison; profiles/r25_split2_accuracy.md); a back-end without the entries raises, the call is
-    never downgraded.  ``conv1x1_abn_eval_fp16`` is the two-piece form on FP16 pieces (include_ext2/skd_split2h.h: the residual
+    never downgraded.  ``conv1x1_abn_eval_fp16`` is the two-piece form on FP16 pieces (include/skd_split2h.h: the residual
     scaled by 2^11, the same three products in two accumulator sets, 22 significant bits per operand: the three-piece accuracy;
     tests/split2h_ref.py is its model; an input beyond +-65504 gives NaN) -- an op of its own, not a keyword of this one, whose
     bound arguments are recorded call by call in tests/golden/routing_census.json.  ``conv1x1_abn_planes_eval`` is the same GEMM with its result written as bf16 piece planes
-    (include_ext/skd_planes.h)."""
+    (include/skd_planes.h)."""
     pieces = _check_pieces(pieces)
     piece_format = _check_piece_format(pieces, piece_format)
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
@@ -905,7 +905,7 @@ def conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, ep
 
 def conv1x1_abn_eval_fp16(x, conv_weight, running_mean, running_var, weight, bias, eps=1e-5, activation="relu", slope=0.01,
                           residual=None, pro=None):
-    """``conv1x1_abn_eval`` on two FP16 pieces per operand with the scaled residual (include_ext2/skd_split2h.h): the arguments, the
+    """``conv1x1_abn_eval`` on two FP16 pieces per operand with the scaled residual (include/skd_split2h.h): the arguments, the
     refusals and the result's layout of that op; never downgraded (a back-end without the entries raises NotImplementedError)."""
     return _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, eps, activation, slope, residual, pro, 2, "fp16")
 
@@ -1010,7 +1010,7 @@ def _conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3, piece_format=
     allocates: a frozen network makes it in its eager warm-up steps, before any graph capture.
     ``pieces`` = 2: the two-plane image of include/skd_split2.h (4 bytes per weight: the first two planes of the other), for
     ``conv3x3_split_eval(..., pieces=2)``; cached under the same rule in a slot of its own, so both packs of one module coexist.
-    ``conv3x3_pack_weights_fp16``: the two fp16 planes of include_ext2/skd_split2h.h (p0 and the scaled p1, 4 bytes per weight
+    ``conv3x3_pack_weights_fp16``: the two fp16 planes of include/skd_split2h.h (p0 and the scaled p1, 4 bytes per weight
     again), in a third slot beside the other two."""
     pieces = _check_pieces(pieces)
     piece_format = _check_piece_format(pieces, piece_format)
@@ -1030,7 +1030,7 @@ def conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3):
 
 
 def conv3x3_pack_weights_fp16(conv, weight=None, owner=None):
-    """``conv3x3_pack_weights`` for ``conv3x3_split_eval_fp16``: the two-plane fp16 image of include_ext2/skd_split2h.h, cached
+    """``conv3x3_pack_weights`` for ``conv3x3_split_eval_fp16``: the two-plane fp16 image of include/skd_split2h.h, cached
     under the same rule in a slot of its own."""
     return _conv3x3_pack_weights(conv, weight, owner, 2, "fp16")
 
@@ -1054,7 +1054,7 @@ _RES_ENTRY = "skd_conv3x3_split_res_nhwc"
 # include/skd_split2.h: the two-piece form of the frozen 128-column convolution, its pack entry, its size query, its cache slot
 _SPLIT2_ENTRY, _PACK2_ENTRY, _PACK2_BYTES = "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_pack_bytes"
 _PACK2_ATTR = "_skd_conv3x3_pack2"
-_SPLIT2H_ENTRY, _PACK2H_ATTR = _SPLIT2H_ENTRIES[_SPLIT2_ENTRY], "_skd_conv3x3_pack2h"      # include_ext2/skd_split2h.h: fp16 pieces
+_SPLIT2H_ENTRY, _PACK2H_ATTR = _SPLIT2H_ENTRIES[_SPLIT2_ENTRY], "_skd_conv3x3_pack2h"      # include/skd_split2h.h: fp16 pieces
 # include/skd_narrow.h: the 64-column form of csrc/conv3x3.hip.  Its one convolution entry takes the residual pointer.
 _NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
 _NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
@@ -1087,7 +1087,7 @@ def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, act
 
 
 def _conv3x3_planes_launch(planes, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0):
-    """_conv3x3_launch for skd_conv3x3_split_planes_nhwc (include_ext/skd_planes.h): the input is a ``Planes``; the entry takes
+    """_conv3x3_launch for skd_conv3x3_split_planes_nhwc (include/skd_planes.h): the input is a ``Planes``; the entry takes
     dilation and geometry behind the epilogue arguments."""
     lib = _lib.get()
     b, h, w, cin = planes.shape
@@ -1129,10 +1129,10 @@ def _conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, acti
     ``pieces`` = 2: the reduced-precision form of include/skd_split2.h with ``pack = conv3x3_pack_weights(..., pieces=2)`` -- two
     pieces per operand, the products a0 b1, a1 b0, a0 b0: within 2e-5 of its float64 model (tests/split2_ref.py), which itself is
     about 4e-6 of the output's largest magnitude from the exact product (profiles/r25_split2_accuracy.md).  A back-end without the
-    entry raises; the call is never downgraded.  ``conv3x3_split_eval_fp16`` is the form of include_ext2/skd_split2h.h with
+    entry raises; the call is never downgraded.  ``conv3x3_split_eval_fp16`` is the form of include/skd_split2h.h with
     ``pack = conv3x3_pack_weights_fp16(...)`` -- two fp16 pieces, scaled residual, the three-piece accuracy
     (tests/split2h_ref.py); an input beyond +-65504 gives NaN.
-    ``x`` may be a ``Planes`` (include_ext/skd_planes.h; three pieces only): the kernel loads the pieces instead of cutting the
+    ``x`` may be a ``Planes`` (include/skd_planes.h; three pieces only): the kernel loads the pieces instead of cutting the
     fp32 map (skd_conv3x3_split_planes_nhwc), and the result is bit for bit that of the call on the fp32 map."""
     pieces = _check_pieces(pieces)
     piece_format = _check_piece_format(pieces, piece_format)
@@ -1153,7 +1153,7 @@ def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activ
 
 
 def conv3x3_split_eval_fp16(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0):
-    """``conv3x3_split_eval`` on two FP16 pieces per operand with the scaled residual (include_ext2/skd_split2h.h), with
+    """``conv3x3_split_eval`` on two FP16 pieces per operand with the scaled residual (include/skd_split2h.h), with
     ``pack = conv3x3_pack_weights_fp16(...)``; never downgraded (a back-end without the entry raises NotImplementedError)."""
     return _conv3x3_split_eval(x, pack, cout, dilation, conv_bias, bn, activation, geometry, 2, "fp16")
 

@@ -196,7 +196,7 @@ class NetModel():
         # outputs move by about 1.5e-5 of their largest magnitude (profiles/r25_split2_accuracy.md).  Independent of the five student
         # switches; off by default.  Set here, before any warm-up step or teacher-graph capture sees the network.
         # args.teacher_piece_format (None: SKD_TEACHER_PIECE_FORMAT, default "bf16"): "fp16" with teacher_pieces = 2 = two FP16 pieces
-        # with a scaled residual (include_ext2/skd_split2h.h): the same three products at the three-piece accuracy.  The format
+        # with a scaled residual (include/skd_split2h.h): the same three products at the three-piece accuracy.  The format
         # without teacher_pieces = 2 is an error, not a silent three-piece run.
         self.teacher_pieces = _teacher_pieces(getattr(args, "teacher_pieces", None))
         self.teacher_piece_format = _teacher_piece_format(getattr(args, "teacher_piece_format", None), self.teacher_pieces)
@@ -218,7 +218,7 @@ class NetModel():
             route_teacher_early(teacher)
         # args.teacher_planes (None: SKD_TEACHER_PLANES, default "0"; handled like teacher_pieces, outside SWITCHES): the teacher's
         # Bottlenecks hand conv1 -> bn1 -> relu to their 3x3 convolution as bf16 piece planes instead of fp32
-        # (pspnet_combine.route_teacher_planes, include_ext/skd_planes.h) -- bit-identical outputs, a speed feature.  Independent of
+        # (pspnet_combine.route_teacher_planes, include/skd_planes.h) -- bit-identical outputs, a speed feature.  Independent of
         # every other switch; inert under teacher_pieces = 2 (the planes hold three pieces).  route_teacher_planes warns once on a
         # back-end without the entries and the teacher keeps its present path.
         self.teacher_planes = _teacher_planes(getattr(args, "teacher_planes", None))
@@ -952,5 +952,5 @@ def default_args(**overrides):
             setattr(a, name, _switch(a, name, env))
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     a.teacher_piece_format = _teacher_piece_format(a.teacher_piece_format, a.teacher_pieces)      # "fp16": two fp16 pieces (skd_split2h.h)
-    a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include_ext/skd_planes.h)
+    a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include/skd_planes.h)
     return a

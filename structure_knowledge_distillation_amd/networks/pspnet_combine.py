@@ -118,7 +118,7 @@ SHORTCUT_ROUTING_EXCLUDED = frozenset({(128, 64, 1, "wgrad"), (64, 128, 2, "wgra
 # (profiles/r25_split2_isolated.md has every shape).
 SPLIT2_ROUTING_EXCLUDED = frozenset()
 # The frozen teacher on two FP16 pieces with a scaled residual (set_teacher_pieces(model, 2, piece_format="fp16"), below; a further
-# opt-in, include_ext2/skd_split2h.h): the same modules, the same call sites, the same three products as the two bf16
+# opt-in, include/skd_split2h.h): the same modules, the same call sites, the same three products as the two bf16
 # pieces above at 22 significant bits per operand instead of 16 -- the three-piece accuracy.  A shape that does not measure ahead of
 # its three-piece twin by more than the spread is listed here, as above, and keeps THREE bf16 pieces
 # (profiles/r32_split2h_isolated.md has every shape).
@@ -155,7 +155,7 @@ TEACHER_EARLY_ROUTING_EXCLUDED = frozenset()
 # (Cin, Cout) and keeps conv -> forward_relu: none does (64 -> 128 at 257 x 513, batch 1: 3.06 x ahead of convolution + ABN pass).
 STRIDE2_ROUTING_EXCLUDED = frozenset()
 # The frozen teacher's conv1 -> bn1 -> relu -> conv2 link as bf16 PIECE PLANES (route_teacher_planes(model), below; a further
-# opt-in, include_ext/skd_planes.h): a flagged Bottleneck whose conv1 runs on the split reduce GEMM and whose conv2 runs on the
+# opt-in, include/skd_planes.h): a flagged Bottleneck whose conv1 runs on the split reduce GEMM and whose conv2 runs on the
 # wide 3x3 kernel anyway, both on three pieces, has the GEMM's epilogue write the three bf16 pieces of its result and the 3x3
 # load them instead of cutting the fp32 map nine times per output tile -- layer3's 23 blocks and layer4's 3.  The outputs are bit
 # for bit what they were (tests/test_conv_planes_gpu.py).  A pair whose {planes-out reduce + planes-in 3x3} does not measure
@@ -177,7 +177,7 @@ _SPLIT2H_ENTRIES = ("skd_conv3x3_split2h_pack_bytes", "skd_conv3x3_split2h_pack_
 def _piece_route(module, *shape, fp16_form=True):
     """``(pieces, piece_format)`` of a frozen split-core call of ``module``: its marks (set_teacher_pieces; three bf16 pieces
     without one).  Marked for two bf16 pieces: 3 for a ``shape`` that SPLIT2_ROUTING_EXCLUDED lists.  Marked for two FP16 pieces
-    (include_ext2/skd_split2h.h): ``(2, "fp16")``, and THREE bf16 pieces -- never two, which nobody asked for -- for a ``shape``
+    (include/skd_split2h.h): ``(2, "fp16")``, and THREE bf16 pieces -- never two, which nobody asked for -- for a ``shape``
     that SPLIT2H_ROUTING_EXCLUDED lists and for a call whose form has no fp16 twin (``fp16_form=False``: the stride-2 form)."""
     pieces = getattr(module, "_skd_teacher_pieces", 3)
     if pieces == 3:
@@ -359,7 +359,7 @@ _UNASKED = object()      # _planes_link: conv2's form has not been asked for yet
 
 def _planes_link(block, x):
     """``(link, form)``: whether the flagged Bottleneck ``block`` (route_teacher_planes) hands conv1 -> bn1 -> relu to conv2 as bf16
-    piece planes (include_ext/skd_planes.h) for the input ``x``, decided ONCE, before conv1 runs, from the modules and ``x`` alone:
+    piece planes (include/skd_planes.h) for the input ``x``, decided ONCE, before conv1 runs, from the modules and ``x`` alone:
     the block is flagged, in eval mode, under no grad; the back-end has the entries; (conv1 Cin, planes, dilation) is not in
     PLANES_ROUTING_EXCLUDED; both convolutions run on three pieces (a block set_teacher_pieces marked keeps its present path);
     conv1 would go to the split reduce GEMM anyway (_reduce_on_split, so not 512 -> 128); conv2 would take the "wide" form anyway
@@ -858,7 +858,7 @@ def route_teacher_planes(model, enable=True):
 
     A flagged Bottleneck in eval mode, under no grad, whose ``conv1`` runs on the split reduce GEMM and whose ``conv2`` runs on the
     wide split-core 3x3 kernel anyway, both on three pieces, has the GEMM's epilogue write relu(bn1(conv1(x))) as its three bf16
-    pieces (include_ext/skd_planes.h, ``SF.conv1x1_abn_planes_eval``) and the 3x3 load those pieces instead of
+    pieces (include/skd_planes.h, ``SF.conv1x1_abn_planes_eval``) and the 3x3 load those pieces instead of
     splitting the fp32 map itself (_planes_link has the whole rule) -- except the pairs of PLANES_ROUTING_EXCLUDED.  With today's
     rules that is layer3's 23 blocks and layer4's 3; layer1 (64 columns), layer2 (library 512 -> 128, or the early forms) and a
     block marked by ``set_teacher_pieces(model, 2)`` keep their present path.  The outputs are bit for bit what they were: the
@@ -869,7 +869,7 @@ def route_teacher_planes(model, enable=True):
     blocks = [m for m in model.modules() if isinstance(m, Bottleneck)]
     if enable and blocks and not SF.planes_supported():
         import warnings
-        warnings.warn("route_teacher_planes: this back-end lacks the piece-plane entries (include_ext/skd_planes.h); the teacher "
+        warnings.warn("route_teacher_planes: this back-end lacks the piece-plane entries (include/skd_planes.h); the teacher "
                       "keeps its fp32 link between conv1 and conv2", RuntimeWarning, stacklevel=2)
         enable = False
     for m in blocks:
@@ -893,7 +893,7 @@ def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
     PSP fold's matrix products and the heads are what they were.  Call it before the network's first forward, warm-up step or
     graph capture, so that the two-plane packs are made eagerly.
     ``pieces=2, piece_format="fp16"`` -- opt-in, NOT an accuracy trade: the same modules are marked and the same call sites take the
-    entries of include_ext2/skd_split2h.h instead -- two FP16 pieces with the residual scaled by 2^11, the same three products: 22
+    entries of include/skd_split2h.h instead -- two FP16 pieces with the residual scaled by 2^11, the same three products: 22
     significant bits per operand, the three-piece accuracy -- except the shapes of SPLIT2H_ROUTING_EXCLUDED.  The
     stride-2 form (like the 64-column, residual-epilogue and piece-plane forms) has no fp16 twin: under this mark it runs on THREE
     bf16 pieces, never on two.  An activation beyond +-65504 gives NaN outputs (the header's range contract).  ``piece_format``
@@ -906,7 +906,7 @@ def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
         raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
     if piece_format == "fp16" and pieces != 2:
         raise ValueError("piece_format='fp16' requires pieces=2, not pieces=%r" % (pieces,))
-    entries, header = (_SPLIT2H_ENTRIES, "include_ext2/skd_split2h.h") if piece_format == "fp16" else (_SPLIT2_ENTRIES, "include/skd_split2.h")
+    entries, header = (_SPLIT2H_ENTRIES, "include/skd_split2h.h") if piece_format == "fp16" else (_SPLIT2_ENTRIES, "include/skd_split2.h")
     if pieces == 2 and not all(_lib.has_entry(n) for n in entries):
         import warnings
         warnings.warn("set_teacher_pieces: this back-end lacks the two-piece entries (%s); the teacher stays on "

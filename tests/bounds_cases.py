@@ -205,7 +205,7 @@ def compare(got, want, tols, what):
 def pointer_entries():
     """Every entry of the two signature tables that takes at least one pointer."""
     out = []
-    for table in (_lib.SIGNATURES, _lib.EXT_SIGNATURES):
+    for table in (_lib.SIGNATURES, _lib.ABI["skd_eval.h"]):
         out += [n for n, (_, args) in table.items() if ctypes.c_void_p in args]
     return out
 

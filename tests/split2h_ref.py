@@ -1,4 +1,4 @@
-"""The float64 MODEL of the fp16 two-piece mode of include_ext2/skd_split2h.h (CPU only; helper of tests/test_split2h_cpu.py and
+"""The float64 MODEL of the fp16 two-piece mode of include/skd_split2h.h (CPU only; helper of tests/test_split2h_cpu.py and
 tests/test_split2h_gpu.py).
 
 An fp32 operand a is cut into two FP16 pieces, round to nearest even through torch's float16 cast (subnormals kept):

@@ -1,12 +1,17 @@
-"""The C-ABI library loads without a GPU and exports every symbol include/skd.h declares; the
-ctypes table in _lib.py mirrors the header one to one; the plain-C oracle exports the same ABI."""
+"""The C-ABI library loads without a GPU; for EVERY header of include/ the ctypes table in _lib.ABI mirrors the header one to
+one and the library exports and types every entry; the plain-C oracle has the core ABI (skd.h) and no extension entry.  A new
+header is one file in include/ and one table in _lib.ABI: every case here is parametrised over the registry's keys."""
 import ctypes
+import itertools
 import os
-import re
+import shutil
 
 import pytest
 
 from structure_knowledge_distillation_amd import _lib, build
+
+HEADERS = list(_lib.ABI)
+REPO = os.path.dirname(build.INCLUDE)
 
 
 @pytest.fixture(scope="module")
@@ -14,19 +19,60 @@ def so_path():
     return build.build()
 
 
-def test_header_and_ctypes_table_agree():
-    protos = _lib.header_prototypes()
-    assert protos, "no prototypes parsed from include/skd.h"
-    assert sorted(protos) == sorted(_lib.SIGNATURES.keys())
+def test_registry_starts_with_the_core():
+    assert HEADERS[0] == "skd.h" and _lib.SIGNATURES is _lib.ABI["skd.h"]
+    assert _lib.HEADER_PATH == _lib.header_path("skd.h") and os.path.dirname(_lib.HEADER_PATH) == build.INCLUDE == _lib.INCLUDE_DIR
 
 
-def test_header_argument_counts_match_ctypes_table():
-    with open(_lib.HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        n = 0 if args in ("", "void") else args.count(",") + 1
-        assert n == len(_lib.SIGNATURES[name][1]), name
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_and_ctypes_table_agree(header):
+    protos = _lib.header_prototypes(_lib.header_path(header))
+    assert protos, "no prototypes parsed from include/%s" % header
+    assert protos == sorted(_lib.ABI[header])
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_argument_counts_match_ctypes_table(header):
+    counts = _lib.header_arg_counts(_lib.header_path(header))
+    assert sorted(counts) == sorted(_lib.ABI[header]), "a table entry was not found as a prototype in include/%s" % header
+    for name, (_, argtypes) in _lib.ABI[header].items():
+        assert counts[name] == len(argtypes), name
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_library_exports_and_types_every_entry(header, so_path):
+    raw, typed = ctypes.CDLL(so_path), _lib.load()
+    for name, (restype, argtypes) in _lib.ABI[header].items():
+        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
+        fn = getattr(typed, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+        assert _lib.signature(name) == (restype, argtypes)
+
+
+def test_entries_are_disjoint_across_headers():
+    parsed = {h: set(_lib.header_prototypes(_lib.header_path(h))) for h in HEADERS}
+    for a, b in itertools.combinations(HEADERS, 2):
+        assert not set(_lib.ABI[a]) & set(_lib.ABI[b]), (a, b)
+        assert not parsed[a] & parsed[b], (a, b)
+    with pytest.raises(KeyError):
+        _lib.signature("skd_no_such_entry")
+
+
+def test_every_header_on_disk_is_in_the_registry():
+    assert sorted(f for f in os.listdir(build.INCLUDE) if f.endswith(".h")) == sorted(_lib.ABI)
+    for gone in ("ext", "ext2"):      # the two side directories headers once had to live in
+        assert not os.path.exists(os.path.join(REPO, "include_" + gone)), gone
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_build_digest_covers_the_header(header, tmp_path, monkeypatch):
+    inc = tmp_path / "include"
+    shutil.copytree(build.INCLUDE, str(inc))
+    monkeypatch.setattr(build, "INCLUDE", str(inc))
+    before = build._digest()
+    with open(str(inc / header), "a") as fh:
+        fh.write("/* touched */\n")
+    assert build._digest() != before, "a change to include/%s would not rebuild libskd_hip.so" % header
 
 
 def test_library_exports_every_symbol(so_path):
@@ -56,6 +102,11 @@ def test_c_oracle_exports_same_abi():
     from oracle import cref
     ref = cref.load(_lib.SIGNATURES)
     assert ref.skd_target_arch() == 0 and ref.skd_pairwise_ldm(129) == 256
+    for name in _lib.SIGNATURES:
+        assert hasattr(ref, name), "the C double lacks the core entry %s" % name
+    for header in HEADERS[1:]:
+        for name in _lib.ABI[header]:
+            assert not hasattr(ref, name), "the C double has the extension entry %s (%s)" % (name, header)
 
 
 def test_no_cpu_fallback_for_ops():

@@ -1,11 +1,10 @@
 """The training form of the student's 1x1 down-sample (shortcut) convolutions on the split core, the parts that need no GPU: the C
-ABI of include/skd_shortcut.h (header <-> table <-> exported symbols, the truth table of the predicate, the host-side refusals of
+ABI of include/skd_shortcut.h (the pinned names and argument lists, the truth table of the predicate, the host-side refusals of
 the launch entries, the split-K plan swept over sizes), the routing and the wiring of a student flagged with ``shortcut=True`` (a
 torch-implemented double of the entries on raw HOST addresses, on top of the plain-C double) and NetModel's ``split_shortcut``
 switch."""
 import copy
 import ctypes
-import re
 
 import pytest
 import torch
@@ -13,7 +12,7 @@ import torch.nn.functional as F
 
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from test_conv3x3_train_cpu import _input, _step, _student
 from test_student_infer_cpu import _host
@@ -98,34 +97,8 @@ def _shapes(calls):
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_shortcut_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.SHORTCUT_HEADER_PATH) == sorted(_lib.SHORTCUT_SIGNATURES) == sorted(NAMES)
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES, _lib.NARROW_SIGNATURES, _lib.NARROW_WGRAD_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH, _lib.NARROW_HEADER_PATH, _lib.NARROW_WGRAD_HEADER_PATH)
-    assert len(tables) == len(headers) == 9 and _lib.SHORTCUT_HEADER_PATH not in headers
-    for table in tables:
-        assert not set(_lib.SHORTCUT_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.SHORTCUT_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.SHORTCUT_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.SHORTCUT_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.SHORTCUT_SIGNATURES) == 7
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.SHORTCUT_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.SHORTCUT_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.SHORTCUT_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    # the C double has the core ABI only, and that is not an error
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in _lib.SHORTCUT_SIGNATURES)
+    """What is particular to skd_shortcut.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_shortcut.h"]) == sorted(NAMES) and len(NAMES) == 7
 
 
 def test_shortcut_supported_truth_table():

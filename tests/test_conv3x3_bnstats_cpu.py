@@ -1,11 +1,9 @@
 """Batch-norm statistics from the epilogue of the split-core 3x3 convolution (include/skd_bnstats.h), the parts that need no GPU:
 the numpy restatement of the record and of the fixed-order combine (tests/bnstats_ref.py) against float64 at the project's
-statistics bounds, the C ABI (header <-> table <-> exported symbols, host-side refusals), the wiring of a student flagged with
+statistics bounds, the C ABI (the pinned names and argument lists, host-side refusals), the wiring of a student flagged with
 ``bnstats=True`` (a double of the four entries on raw HOST addresses, computed by the restatement, on top of the training form's
 torch-implemented double), the plain-C double (no entry: nothing changes, bit for bit) and NetModel's ``split_bnstats`` switch."""
 import copy
-import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,7 @@ import torch
 import bnstats_ref as R
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from test_conv3x3_train_cpu import TrainDouble, _input, _step, _student
 from test_student_infer_cpu import _host
@@ -66,37 +64,10 @@ def test_restatement_is_exact_on_a_constant_channel_and_on_a_single_row():
 # ---- 2. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_bnstats_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.BNSTATS_HEADER_PATH) == sorted(_lib.BNSTATS_SIGNATURES) == sorted(NAMES)
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES, _lib.NARROW_SIGNATURES, _lib.NARROW_WGRAD_SIGNATURES,
-              _lib.SHORTCUT_SIGNATURES, _lib.SPLIT2_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH, _lib.NARROW_HEADER_PATH, _lib.NARROW_WGRAD_HEADER_PATH,
-               _lib.SHORTCUT_HEADER_PATH, _lib.SPLIT2_HEADER_PATH)
-    assert len(tables) == len(headers) == 11 and _lib.BNSTATS_HEADER_PATH not in headers
-    for table in tables:
-        assert not set(_lib.BNSTATS_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.BNSTATS_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.BNSTATS_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.BNSTATS_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.BNSTATS_SIGNATURES) == 4
+    """What is particular to skd_bnstats.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_bnstats.h"]) == sorted(NAMES) and len(NAMES) == 4
     # the two convolution entries take the same list: the training forward's arguments, then the workspace
-    assert _lib.BNSTATS_SIGNATURES["skd_conv3x3_split_stats_nhwc"] == _lib.BNSTATS_SIGNATURES["skd_conv3x3_narrow_stats_nhwc"]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.BNSTATS_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.BNSTATS_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.BNSTATS_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    core = cref.load(_lib.SIGNATURES)      # the C double has the core ABI only, and that is not an error
-    assert not any(hasattr(core, n) for n in _lib.BNSTATS_SIGNATURES)
+    assert _lib.signature("skd_conv3x3_split_stats_nhwc") == _lib.signature("skd_conv3x3_narrow_stats_nhwc")
 
 
 def test_workspace_size_and_host_side_refusals():
@@ -345,7 +316,7 @@ def test_netmodel_split_bnstats_switch(monkeypatch):
 
 def test_docs_name_the_statistics_form():
     assert "skd_bnstats.h" in SF.conv3x3_split_train.__doc__ and "BNSTATS_ROUTING_EXCLUDED" in PC.route_training_convs.__doc__
-    with open(_lib.BNSTATS_HEADER_PATH) as fh:
+    with open(_lib.header_path("skd_bnstats.h")) as fh:
         text = fh.read()
     for phrase in ("32-row", "M2", "no pivot", "same bits on every call", "not 8-byte aligned"):
         assert phrase in text, phrase

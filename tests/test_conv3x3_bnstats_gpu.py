@@ -291,7 +291,7 @@ class Counting:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name not in _lib.BNSTATS_SIGNATURES or name == "skd_conv3x3_bnstats_floats":
+        if name not in _lib.ABI["skd_bnstats.h"] or name == "skd_conv3x3_bnstats_floats":
             return fn
 
         def counted(*args):

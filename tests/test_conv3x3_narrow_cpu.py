@@ -3,8 +3,6 @@ table <-> exported symbols, the truth table of the query, the pack size, host-si
 student in its inference and training forms (a recording double of the entries on top of the plain-C double), the wiring against
 the plain op sequence (a torch-implemented double), NetModel's ``split_narrow`` flag and the rebuilding of a stale narrow pack."""
 import copy
-import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,7 @@ import torch.nn.functional as F
 
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from test_conv3x3_train_cpu import TrainDouble
 from test_student_infer_cpu import ENTRY, RES_ENTRY, _host
@@ -84,38 +82,13 @@ def computing():
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_narrow_header_table_and_library_agree():
-    names = sorted([SUPPORTED, PACK_BYTES, PACK_PAIR, NARROW])
-    assert _lib.header_prototypes(_lib.NARROW_HEADER_PATH) == sorted(_lib.NARROW_SIGNATURES) == names
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES)
-    paths = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-             _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH)
-    for table in tables:
-        assert not set(_lib.NARROW_SIGNATURES) & set(table)
-    for path in paths:
-        assert not set(_lib.NARROW_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.NARROW_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.NARROW_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.NARROW_SIGNATURES) == 4
+    """What is particular to skd_narrow.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_narrow.h"]) == sorted([SUPPORTED, PACK_BYTES, PACK_PAIR, NARROW]) and len(_lib.ABI["skd_narrow.h"]) == 4
     # the argument lists of the wide entries
-    assert _lib.NARROW_SIGNATURES[SUPPORTED] == _lib.EXT_SIGNATURES["skd_conv3x3_split_supported"]
-    assert _lib.NARROW_SIGNATURES[PACK_BYTES] == _lib.EXT_SIGNATURES["skd_conv3x3_split_pack_bytes"]
-    assert _lib.NARROW_SIGNATURES[PACK_PAIR] == _lib.TRAIN_SIGNATURES["skd_conv3x3_split_pack_pair"]
-    assert _lib.NARROW_SIGNATURES[NARROW] == _lib.INFER_SIGNATURES[RES_ENTRY]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.NARROW_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.NARROW_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.NARROW_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in _lib.NARROW_SIGNATURES)
+    assert _lib.signature(SUPPORTED) == _lib.signature("skd_conv3x3_split_supported")
+    assert _lib.signature(PACK_BYTES) == _lib.signature("skd_conv3x3_split_pack_bytes")
+    assert _lib.signature(PACK_PAIR) == _lib.signature("skd_conv3x3_split_pack_pair")
+    assert _lib.signature(NARROW) == _lib.signature(RES_ENTRY)
 
 
 def test_narrow_supported_truth_table_and_pack_bytes():
@@ -340,7 +313,7 @@ def test_plain_c_double_keeps_todays_sequence():
     """A back-end without the entries: flagged networks run what they ran, nothing raises."""
     _lib.install_test_backend(cref.load(_lib.SIGNATURES))
     try:
-        assert not any(_lib.has_entry(n) for n in _lib.NARROW_SIGNATURES)
+        assert not any(_lib.has_entry(n) for n in _lib.ABI["skd_narrow.h"])
         net, x = _student(), _input()
         with torch.no_grad():
             want = net(x)

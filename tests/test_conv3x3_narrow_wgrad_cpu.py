@@ -1,11 +1,10 @@
 """The weight gradient of the student's 64-channel 3x3 convolutions on the split core, the parts that need no GPU: the C ABI of
-include/skd_narrow_wgrad.h (header <-> table <-> exported symbols, the truth table of the predicate, the host-side refusals of
+include/skd_narrow_wgrad.h (the pinned names and argument lists, the truth table of the predicate, the host-side refusals of
 the launch entry, the split-K plan swept over sizes), the routing and the wiring of a student flagged with ``narrow_wgrad=True`` (a
 torch-implemented double: NarrowDouble + WgradDouble + the three new entries, the weight gradient computed by
 ``torch.nn.grad.conv2d_weight``) and NetModel's ``split_narrow_wgrad`` switch."""
 import copy
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +12,7 @@ import torch
 
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from test_conv3x3_narrow_cpu import NarrowDouble
 from test_conv3x3_train_cpu import ROUTED, _input, _step, _student
@@ -70,40 +69,15 @@ def computing():
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_narrow_wgrad_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.NARROW_WGRAD_HEADER_PATH) == sorted(_lib.NARROW_WGRAD_SIGNATURES) == sorted([SUPPORTED, PLAN, RUN])
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES, _lib.NARROW_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH, _lib.NARROW_HEADER_PATH)
-    assert len(tables) == len(headers) == 8 and _lib.NARROW_WGRAD_HEADER_PATH not in headers
-    for table in tables:
-        assert not set(_lib.NARROW_WGRAD_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.NARROW_WGRAD_SIGNATURES) & set(_lib.header_prototypes(path))
+    """What is particular to skd_narrow_wgrad.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    table = _lib.ABI["skd_narrow_wgrad.h"]
+    assert sorted(table) == sorted([SUPPORTED, PLAN, RUN]) and len(table) == 3
     # the two tables the neighbouring tests pin have not grown
-    assert len(_lib.WGRAD_SIGNATURES) == 3 and len(_lib.NARROW_SIGNATURES) == 4
-    with open(_lib.NARROW_WGRAD_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.NARROW_WGRAD_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.NARROW_WGRAD_SIGNATURES) == 3
+    assert len(_lib.ABI["skd_wgrad.h"]) == 3 and len(_lib.ABI["skd_narrow.h"]) == 4
     # the argument lists of the wide entries
     for new, old in zip((SUPPORTED, PLAN, RUN), ("skd_conv3x3_split_wgrad_supported", "skd_conv3x3_split_wgrad_plan",
                                                  "skd_conv3x3_split_wgrad_nhwc")):
-        assert _lib.NARROW_WGRAD_SIGNATURES[new] == _lib.WGRAD_SIGNATURES[old]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.NARROW_WGRAD_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.NARROW_WGRAD_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.NARROW_WGRAD_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    # the C double has the core ABI only, and that is not an error
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in _lib.NARROW_WGRAD_SIGNATURES)
+        assert table[new] == _lib.ABI["skd_wgrad.h"][old]
 
 
 def test_narrow_wgrad_supported_truth_table():

@@ -1,12 +1,11 @@
 """The stride-2 forward form of the split-core 3x3 convolution and the frozen teacher's early routing, the parts that need no GPU:
-the C ABI of include/skd_stride2.h (header <-> table <-> exported symbols, the truth table of the query, the host-side refusals),
+the C ABI of include/skd_stride2.h (the pinned names and argument lists, the truth table of the query, the host-side refusals),
 the kernel's row map swept on the host against a numpy restatement, the routing of a teacher flagged by ``route_teacher_early`` and
 of a student flagged by ``fuse_for_inference(stride2=True)`` (a torch-implemented double of the entries on raw host addresses,
 on top of the plain-C double), the wiring against the plain op sequence, the public switches and the packs behind a fused
 optimizer step."""
 import copy
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -29,39 +28,12 @@ SPLIT2 = "skd_conv3x3_split2_nhwc"
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_stride2_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.STRIDE2_HEADER_PATH) == sorted(_lib.STRIDE2_SIGNATURES) == sorted([SUPPORTED, TAPS, S2])
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES, _lib.NARROW_SIGNATURES, _lib.NARROW_WGRAD_SIGNATURES,
-              _lib.SHORTCUT_SIGNATURES, _lib.SPLIT2_SIGNATURES, _lib.BNSTATS_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH, _lib.NARROW_HEADER_PATH, _lib.NARROW_WGRAD_HEADER_PATH,
-               _lib.SHORTCUT_HEADER_PATH, _lib.SPLIT2_HEADER_PATH, _lib.BNSTATS_HEADER_PATH)
-    assert len(tables) == len(headers) == 12 and _lib.STRIDE2_HEADER_PATH not in headers      # the thirteenth header
-    for table in tables:
-        assert not set(_lib.STRIDE2_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.STRIDE2_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.STRIDE2_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.STRIDE2_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.STRIDE2_SIGNATURES) == 3
+    """What is particular to skd_stride2.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_stride2.h"]) == sorted([SUPPORTED, TAPS, S2]) and len(_lib.ABI["skd_stride2.h"]) == 3
     # the argument list of the stride-1 entry without ``dilation``, with ``pieces`` in front of ``geometry``
-    one = list(_lib.EXT_SIGNATURES[ENTRY][1])
-    assert _lib.STRIDE2_SIGNATURES[S2][1] == one[:5] + one[6:17] + [ctypes.c_int] + one[17:]
-    assert _lib.STRIDE2_SIGNATURES[SUPPORTED] == _lib.EXT_SIGNATURES["skd_conv3x3_split_supported"]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.STRIDE2_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.STRIDE2_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.STRIDE2_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    core = cref.load(_lib.SIGNATURES)      # the C double has the core ABI only, and that is not an error
-    assert not any(hasattr(core, n) for n in _lib.STRIDE2_SIGNATURES)
+    one = list(_lib.signature(ENTRY)[1])
+    assert _lib.signature(S2)[1] == one[:5] + one[6:17] + [ctypes.c_int] + one[17:]
+    assert _lib.signature(SUPPORTED) == _lib.signature("skd_conv3x3_split_supported")
 
 
 def test_supported_truth_table():

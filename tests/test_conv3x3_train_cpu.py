@@ -4,8 +4,6 @@ recording double of the entries on top of the plain-C double), the wiring of the
 torch-implemented double: its "packs" are handles to w and to the flipped, transposed Wd, its run entry is F.conv2d) and NetModel's
 ``split_train`` flag."""
 import copy
-import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,7 @@ import torch
 
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from test_student_infer_cpu import Conv3x3Double, _host
 
@@ -62,34 +60,12 @@ def computing():
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_train_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.TRAIN_HEADER_PATH) == sorted(_lib.TRAIN_SIGNATURES) == sorted([SUPPORTED, PACK_PAIR])
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.MS_SIGNATURES) | set(_lib.OHEM_SIGNATURES)
-              | set(_lib.INFER_SIGNATURES))
-    assert not set(_lib.TRAIN_SIGNATURES) & others
-    for path in (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH):
-        assert not set(_lib.TRAIN_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.TRAIN_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.TRAIN_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.TRAIN_SIGNATURES)
+    """What is particular to skd_train.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_train.h"]) == sorted([SUPPORTED, PACK_PAIR])
     # the supported query has the arguments of the existing one; pack_pair those of pack_weights with a second (pack, bytes) pair
-    assert _lib.TRAIN_SIGNATURES[SUPPORTED] == _lib.EXT_SIGNATURES["skd_conv3x3_split_supported"]
-    old, new = _lib.EXT_SIGNATURES["skd_conv3x3_split_pack_weights"], _lib.TRAIN_SIGNATURES[PACK_PAIR]
+    assert _lib.signature(SUPPORTED) == _lib.signature("skd_conv3x3_split_supported")
+    old, new = _lib.signature("skd_conv3x3_split_pack_weights"), _lib.signature(PACK_PAIR)
     assert new[0] == old[0] and new[1] == old[1][:9] + old[1][7:9] + old[1][9:]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.TRAIN_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.TRAIN_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.TRAIN_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    # the C double has the core ABI only, and that is not an error
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in _lib.TRAIN_SIGNATURES)
 
 
 def test_train_supported_truth_table():

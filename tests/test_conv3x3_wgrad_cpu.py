@@ -1,11 +1,10 @@
 """The weight gradient of the student's 3x3 convolutions on the split core, the parts that need no GPU: the C ABI of
-include/skd_wgrad.h (header <-> table <-> exported symbols, the truth table of the predicate, the host-side refusals of the launch
+include/skd_wgrad.h (the pinned names and argument lists, the truth table of the predicate, the host-side refusals of the launch
 entry, the split-K plan swept over sizes), the routing and the wiring of a student flagged with ``wgrad=True`` (a torch-implemented
 double: TrainDouble + the three entries, the weight gradient computed by ``torch.nn.grad.conv2d_weight``) and NetModel's
 ``split_wgrad`` switch."""
 import copy
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +12,7 @@ import torch
 
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from test_conv3x3_train_cpu import ROUTED, TrainDouble, _input, _step, _student
 from test_student_infer_cpu import _host
@@ -60,35 +59,9 @@ def computing():
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_wgrad_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.WGRAD_HEADER_PATH) == sorted(_lib.WGRAD_SIGNATURES) == sorted([SUPPORTED, PLAN, RUN])
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH)
-    for table in tables:
-        assert not set(_lib.WGRAD_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.WGRAD_SIGNATURES) & set(_lib.header_prototypes(path))
-        assert not set(_lib.header_prototypes(_lib.WGRAD_HEADER_PATH)) & set(_lib.header_prototypes(path))
-    with open(_lib.WGRAD_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.WGRAD_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.WGRAD_SIGNATURES) == 3
-    assert _lib.WGRAD_SIGNATURES[SUPPORTED] == _lib.TRAIN_SIGNATURES["skd_conv3x3_split_train_supported"]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.WGRAD_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.WGRAD_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.WGRAD_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    # the C double has the core ABI only, and that is not an error
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in _lib.WGRAD_SIGNATURES)
+    """What is particular to skd_wgrad.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_wgrad.h"]) == sorted([SUPPORTED, PLAN, RUN]) and len(_lib.ABI["skd_wgrad.h"]) == 3
+    assert _lib.signature(SUPPORTED) == _lib.signature("skd_conv3x3_split_train_supported")
 
 
 def test_wgrad_supported_truth_table():

@@ -1,5 +1,4 @@
-"""Piece planes (include_ext/skd_planes.h), the parts that need no GPU: the C ABI (header <-> table <-> exported symbols, the
-build digest), the layout as the host-only offset map gives it, the host-side refusals, the routing of
+"""Piece planes (include/skd_planes.h), the parts that need no GPU: the C ABI (the names and the twins' argument lists; the rest is tests/test_abi.py), the layout as the host-only offset map gives it, the host-side refusals, the routing of
 ``route_teacher_planes`` under a recording double, the ``teacher_planes`` switch and the documents.
 
 The routing tests empty ``PLANES_ROUTING_EXCLUDED``: they check the mechanism, the set is the policy (one test reads the committed
@@ -7,7 +6,6 @@ set and sees it respected)."""
 import ctypes
 import inspect
 import os
-import re
 import warnings
 
 import pytest
@@ -15,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF, networks
+from structure_knowledge_distillation_amd import _lib, functional as SF, networks
 from structure_knowledge_distillation_amd.networks import kd_model, pspnet_combine as PC
 from structure_knowledge_distillation_amd.networks.kd_model import NetModel, default_args
 
@@ -28,45 +26,13 @@ HOST_ONLY = NAMES[:3]
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------------
 
 def test_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.PLANES_HEADER_PATH) == sorted(_lib.PLANES_SIGNATURES) == sorted(NAMES)
-    assert os.path.dirname(_lib.PLANES_HEADER_PATH) == build.INCLUDE_EXT == os.path.join(ROOT, "include_ext")
-    assert len([f for f in os.listdir(build.INCLUDE) if f.endswith(".h")]) == 14, "include/ is closed"
-    assert sorted(os.listdir(build.INCLUDE_EXT)) == ["skd_planes.h"]
-    others = [getattr(_lib, n) for n in dir(_lib) if n.endswith("SIGNATURES") and n != "PLANES_SIGNATURES"]
-    assert len(others) == 14 and not any(set(_lib.PLANES_SIGNATURES) & set(t) for t in others)
-    with open(_lib.PLANES_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert args.count(",") + 1 == len(_lib.PLANES_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.PLANES_SIGNATURES) == 7
+    """What is particular to skd_planes.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    table = _lib.ABI["skd_planes.h"]
+    assert sorted(table) == sorted(NAMES) and len(table) == 7
     # the consumer takes its twin's arguments (dilation moved behind the epilogue), the producer its twin's without the residual
-    twin = _lib.EXT_SIGNATURES["skd_conv3x3_split_nhwc"][1]
-    assert sorted(map(str, _lib.PLANES_SIGNATURES["skd_conv3x3_split_planes_nhwc"][1])) == sorted(map(str, twin))
-    assert len(_lib.PLANES_SIGNATURES["skd_conv1x1_abn_planes_nhwc"][1]) == len(_lib.SIGNATURES["skd_conv1x1_abn_nhwc"][1]) - 1
-    raw = ctypes.CDLL(build.build())
-    for name in NAMES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.PLANES_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    # the C double has the core ABI only, and that is not an error
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in NAMES)
-
-
-def test_build_digest_covers_the_header(tmp_path, monkeypatch):
-    ext = tmp_path / "include_ext"
-    ext.mkdir()
-    with open(_lib.PLANES_HEADER_PATH, "rb") as src, open(str(ext / "skd_planes.h"), "wb") as dst:
-        dst.write(src.read())
-    monkeypatch.setattr(build, "INCLUDE_EXT", str(ext))
-    before = build._digest()
-    with open(str(ext / "skd_planes.h"), "ab") as fh:
-        fh.write(b"\n/* edited */\n")
-    assert build._digest() != before
+    twin = _lib.signature("skd_conv3x3_split_nhwc")[1]
+    assert sorted(map(str, table["skd_conv3x3_split_planes_nhwc"][1])) == sorted(map(str, twin))
+    assert len(table["skd_conv1x1_abn_planes_nhwc"][1]) == len(_lib.signature("skd_conv1x1_abn_nhwc")[1]) - 1
 
 
 # ---- 2. the layout -----------------------------------------------------------------------------------------------------------------
@@ -454,6 +420,6 @@ def test_documents_name_the_header_and_the_switch():
     for fn in (SF.conv1x1_abn_eval, SF.conv1x1_abn_planes_eval, SF.conv3x3_split_eval, SF.Planes, networks.route_teacher_planes, PC._planes_link):
         assert "skd_planes.h" in fn.__doc__, fn
     assert "SKD_TEACHER_PLANES" in kd_model._teacher_planes.__doc__
-    with open(_lib.PLANES_HEADER_PATH) as fh:
+    with open(_lib.header_path("skd_planes.h")) as fh:
         header = fh.read()
     assert "SKD_TEACHER_PLANES" in header and "BIT FOR BIT" in header and "skd_planes_offset" in header

@@ -1,4 +1,4 @@
-"""-m gpu: piece planes (include_ext/skd_planes.h) -- the stand-alone split and join kernels, the producer (the split reduce GEMM
+"""-m gpu: piece planes (include/skd_planes.h) -- the stand-alone split and join kernels, the producer (the split reduce GEMM
 whose epilogue writes the three bf16 pieces of its result: csrc/conv1x1.hip with PLANES), the consumer (the wide stride-1 3x3
 convolution that loads the pieces instead of splitting an fp32 map: csrc/conv3x3.hip with PLANES), and the frozen teacher flagged by
 ``route_teacher_planes``.

@@ -233,8 +233,8 @@ def test_entries_stay_inside_their_buffers(name):
 
 def test_every_multiscale_entry_has_a_guard_band_case():
     covered = {entry for entry, _, _ in GUARD_CASES.values()}
-    assert covered == set(_lib.MS_SIGNATURES)
-    assert all(_lib.ctypes.c_void_p in args for _, args in _lib.MS_SIGNATURES.values()), "both entries take pointers"
+    assert covered == set(_lib.ABI["skd_eval_ms.h"])
+    assert all(_lib.ctypes.c_void_p in args for _, args in _lib.ABI["skd_eval_ms.h"].values()), "both entries take pointers"
 
 
 # ---- 4. end to end ------------------------------------------------------------------------------------------------------

@@ -1,16 +1,14 @@
 """OHEM criterion, the parts that need no GPU: the restatement (tests/ohem_ref.py) against the reference's recorded results
 (tests/golden/reference_ohem.pt), against the live reference where its tree exists and against scipy's zoom; the C ABI of
-include/skd_ohem.h (header <-> table <-> exported symbols, host-side refusals); the module surface (constructor signatures,
+include/skd_ohem.h (the pinned names and argument lists, host-side refusals); the module surface (constructor signatures,
 refusals, the C double has no OHEM entries); NetModel's choice of criterion.
 
 Bounds.  ``tau`` (stored by the generator: 4 x the largest difference between the reference's fp32 label probability and the
 restatement's float64 one) is the distance from the threshold within which two evaluations may disagree about a pixel; farther
 away they must agree.  On the reference's own mask the float64 loss and gradients are within 1e-6 (relative) of the recorded
 fp32 ones, the bound the generator itself held before writing the fixture."""
-import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -163,23 +161,8 @@ OHEM_ENTRIES = ["skd_ce_ohem_dsn_forward", "skd_ce_ohem_workspace_floats", "skd_
 
 
 def test_ohem_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.OHEM_HEADER_PATH) == sorted(_lib.OHEM_SIGNATURES) == OHEM_ENTRIES
-    assert not set(_lib.OHEM_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.MS_SIGNATURES))
-    with open(_lib.OHEM_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.OHEM_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.OHEM_SIGNATURES)
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.OHEM_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.OHEM_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.OHEM_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
+    """What is particular to skd_ohem.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_ohem.h"]) == OHEM_ENTRIES
     assert os.path.join(build.CSRC, "ce_ohem.hip") in build.sources()
 
 
@@ -255,7 +238,7 @@ def test_plain_c_double_has_no_ohem_entries():
 
 def test_argument_checks_of_the_op():
     prev = _lib._test_backend                                 # a back-end that has the entries and may not be called: the checks come first
-    _lib.install_test_backend(type("B", (), {n: staticmethod(lambda *a: 1 / 0) for n in _lib.OHEM_SIGNATURES})())
+    _lib.install_test_backend(type("B", (), {n: staticmethod(lambda *a: 1 / 0) for n in _lib.ABI["skd_ohem.h"]})())
     try:
         lm, tg = torch.zeros(1, 3, 4, 4), torch.zeros(1, 16, 16, dtype=torch.int64)
         with pytest.raises(TypeError):

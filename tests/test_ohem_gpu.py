@@ -220,7 +220,7 @@ def test_entries_stay_inside_their_buffers(name):
 
 def test_every_pointer_taking_ohem_entry_has_a_guard_band_case():
     covered = {e for entries, _ in GUARD_CASES.values() for e in entries}
-    pointer_taking = {n for n, (_, args) in _lib.OHEM_SIGNATURES.items() if _lib.ctypes.c_void_p in args}
+    pointer_taking = {n for n, (_, args) in _lib.ABI["skd_ohem.h"].items() if _lib.ctypes.c_void_p in args}
     assert covered == pointer_taking == {"skd_ohem_threshold", "skd_ce_ohem_dsn_forward"}
 
 

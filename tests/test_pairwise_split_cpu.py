@@ -1,10 +1,9 @@
-"""The pair-wise loss on the split core, the parts that need no GPU: the C ABI of include/skd_pairwise_split.h (header <-> table
-<-> exported symbols, the workspace queries on a host without a device), the routing of ``pair_wise_loss(..., split=True)`` under
+"""The pair-wise loss on the split core, the parts that need no GPU: the C ABI of include/skd_pairwise_split.h (the pinned names and argument lists; header <-> table <-> library is
+tests/test_abi.py, the workspace queries on a host without a device), the routing of ``pair_wise_loss(..., split=True)`` under
 a recording double of the four entries, the wiring under a torch-implemented double of the two split entries (on raw HOST
 addresses, on top of the plain-C double), NetModel's ``split_pairwise`` switch and the documents."""
 import ctypes
 import os
-import re
 import warnings
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 import torch
 
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd.utils.criterion import CriterionPairWiseforWholeFeatAfterPool
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -144,42 +143,12 @@ def pairwise_calls(double):
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------------
 
 def test_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.PAIRWISE_SPLIT_HEADER_PATH) == sorted(_lib.PAIRWISE_SPLIT_SIGNATURES) == sorted(NAMES)
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES, _lib.NARROW_SIGNATURES, _lib.NARROW_WGRAD_SIGNATURES,
-              _lib.SHORTCUT_SIGNATURES, _lib.SPLIT2_SIGNATURES, _lib.BNSTATS_SIGNATURES, _lib.STRIDE2_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH, _lib.NARROW_HEADER_PATH, _lib.NARROW_WGRAD_HEADER_PATH,
-               _lib.SHORTCUT_HEADER_PATH, _lib.SPLIT2_HEADER_PATH, _lib.BNSTATS_HEADER_PATH, _lib.STRIDE2_HEADER_PATH)
-    assert len(tables) == len(headers) == 13 and _lib.PAIRWISE_SPLIT_HEADER_PATH not in headers      # the fourteenth header
-    assert sorted(f for f in os.listdir(build.INCLUDE) if f.endswith(".h")) == sorted(
-        os.path.basename(p) for p in headers + (_lib.PAIRWISE_SPLIT_HEADER_PATH,))
-    for table in tables:
-        assert not set(_lib.PAIRWISE_SPLIT_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.PAIRWISE_SPLIT_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.PAIRWISE_SPLIT_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.PAIRWISE_SPLIT_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.PAIRWISE_SPLIT_SIGNATURES) == 4
+    """What is particular to skd_pairwise_split.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_pairwise_split.h"]) == sorted(NAMES) and len(NAMES) == 4
     # the argument lists are the fp32 twins': a caller can hand both the same buffers
     for twin, name in (("skd_pairwise_gram_loss", "skd_pairwise_split_gram_loss"), ("skd_pairwise_backward", "skd_pairwise_split_backward"),
                        ("skd_pairwise_backward_workspace_floats", "skd_pairwise_split_backward_workspace_floats")):
-        assert _lib.SIGNATURES[twin] == _lib.PAIRWISE_SPLIT_SIGNATURES[name]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.PAIRWISE_SPLIT_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.PAIRWISE_SPLIT_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.PAIRWISE_SPLIT_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    # the C double has the core ABI only, and that is not an error
-    core = cref.load(_lib.SIGNATURES)
-    assert not any(hasattr(core, n) for n in _lib.PAIRWISE_SPLIT_SIGNATURES)
+        assert _lib.SIGNATURES[twin] == _lib.signature(name)
 
 
 def test_workspace_queries_need_no_device_and_grow():

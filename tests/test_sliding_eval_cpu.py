@@ -8,10 +8,8 @@ the restatement as ``skd_seg_sliding``).  The plain-C double alone has no ``skd_
 Bounds: probabilities within 2^-22 max|logit| of the reference's (one fp32 ulp of the interpolated value each way: the
 reference's CPU upsample rounds the four-term sum differently); argmax disagreements at most 1e-5 pixels + 2 per case (the
 near-tie cap of tests/test_eval_golden.py; the generator measured 0); evaluate_main: the bounds of tests/test_eval_golden.py."""
-import ctypes
 import importlib.util
 import os
-import re
 import sys
 
 import numpy as np
@@ -19,7 +17,7 @@ import pytest
 import torch
 
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build
+from structure_knowledge_distillation_amd import _lib
 from structure_knowledge_distillation_amd import functional as SF
 from structure_knowledge_distillation_amd.networks import evaluate as E
 
@@ -304,39 +302,10 @@ def test_missing_pil_is_a_clear_import_error(tmp_path, monkeypatch):
 # ---- 6. header <-> table <-> exported symbols ----------------------------------------------------------------------
 
 def test_extension_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.EXT_HEADER_PATH) == sorted(_lib.EXT_SIGNATURES)
-    assert not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES)
-    with open(_lib.EXT_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        n = 0 if args in ("", "void") else args.count(",") + 1
-        assert n == len(_lib.EXT_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.EXT_SIGNATURES)
-    so = build.build()
-    raw = ctypes.CDLL(so)
-    for name in _lib.EXT_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
+    """What is particular to skd_eval.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
     typed = _lib.load()
-    assert typed.skd_seg_sliding.argtypes == _lib.EXT_SIGNATURES["skd_seg_sliding"][1]
-    with open(so, "rb") as fh:
-        assert b"gfx950" in fh.read()
+    assert typed.skd_seg_sliding.argtypes == _lib.ABI["skd_eval.h"]["skd_seg_sliding"][1]
     # host-side refusals need no device: class counts the kernel was not built for, missing tensors
     assert typed.skd_seg_sliding(1, 33, 2, 2, 4, 4, 4, 4, 1, 1, None, 255, None, None, None, None, None) == 0
     assert typed.skd_seg_sliding(1, 19, 2, 2, 4, 4, 4, 4, None, None, None, 255, None, None, None, None, None) == 0
     assert typed.skd_seg_sliding(1, 19, 2, 2, 4, 4, 4, 4, 1, 1, 1, 255, None, None, None, None, None) == 0
-
-
-def test_build_digest_covers_the_extension_header(tmp_path, monkeypatch):
-    inc = tmp_path / "include"
-    inc.mkdir()
-    for f in os.listdir(build.INCLUDE):
-        with open(os.path.join(build.INCLUDE, f), "rb") as src, open(str(inc / f), "wb") as dst:
-            dst.write(src.read())
-    monkeypatch.setattr(build, "INCLUDE", str(inc))
-    before = build._digest()
-    with open(str(inc / "skd_eval.h"), "ab") as fh:
-        fh.write(b"\n/* edited */\n")
-    assert build._digest() != before

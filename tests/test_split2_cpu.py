@@ -1,11 +1,9 @@
-"""The frozen teacher's two-piece mode (include/skd_split2.h), the parts that need no GPU: the C ABI (header <-> table <-> exported
-symbols, the pack size, the host-side refusals of the five entries), the ops' ``pieces`` parameter, the routing of a network marked
+"""The frozen teacher's two-piece mode (include/skd_split2.h), the parts that need no GPU: the C ABI (the pinned names and argument lists; header <-> table <-> library is tests/test_abi.py, the pack size, the host-side refusals of the five entries), the ops' ``pieces`` parameter, the routing of a network marked
 by ``set_teacher_pieces`` (a recording double of the 1x1 entries on top of the plain-C double; the 3x3 ops, which refuse host
 tensors, are recorded at the op), the public switch, the caches behind a fused optimizer step, and the float64 model of the mode
 itself (tests/split2_ref.py)."""
 import copy
 import ctypes
-import re
 import warnings
 
 import pytest
@@ -15,7 +13,7 @@ import torch.nn.functional as F
 import split2_ref as R
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from structure_knowledge_distillation_amd.networks.kd_model import NetModel, advance_versions_after_step, default_args
 
@@ -26,46 +24,22 @@ NAMES = ["skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "sk
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_split2_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.SPLIT2_HEADER_PATH) == sorted(_lib.SPLIT2_SIGNATURES) == sorted(NAMES)
-    tables = (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.MS_SIGNATURES, _lib.OHEM_SIGNATURES, _lib.INFER_SIGNATURES,
-              _lib.TRAIN_SIGNATURES, _lib.WGRAD_SIGNATURES, _lib.NARROW_SIGNATURES, _lib.NARROW_WGRAD_SIGNATURES,
-              _lib.SHORTCUT_SIGNATURES)
-    headers = (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH, _lib.INFER_HEADER_PATH,
-               _lib.TRAIN_HEADER_PATH, _lib.WGRAD_HEADER_PATH, _lib.NARROW_HEADER_PATH, _lib.NARROW_WGRAD_HEADER_PATH,
-               _lib.SHORTCUT_HEADER_PATH)
-    assert len(tables) == len(headers) == 10 and _lib.SPLIT2_HEADER_PATH not in headers
-    for table in tables:
-        assert not set(_lib.SPLIT2_SIGNATURES) & set(table)
-    for path in headers:
-        assert not set(_lib.SPLIT2_SIGNATURES) & set(_lib.header_prototypes(path))
-    with open(_lib.SPLIT2_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.SPLIT2_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.SPLIT2_SIGNATURES) == 5
+    """What is particular to skd_split2.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_split2.h"]) == sorted(NAMES) and len(NAMES) == 5
     # the parameter lists are the twins'
-    for two, three, table in (("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split_pack_bytes", _lib.EXT_SIGNATURES),
-                              ("skd_conv3x3_split2_pack_weights", "skd_conv3x3_split_pack_weights", _lib.EXT_SIGNATURES),
-                              ("skd_conv3x3_split2_nhwc", "skd_conv3x3_split_nhwc", _lib.EXT_SIGNATURES),
-                              ("skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn_nhwc", _lib.SIGNATURES),
-                              ("skd_conv1x1_abn2_pro_nhwc", "skd_conv1x1_abn_pro_nhwc", _lib.SIGNATURES)):
-        assert _lib.SPLIT2_SIGNATURES[two] == table[three], two
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.SPLIT2_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.SPLIT2_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.SPLIT2_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
-    core = cref.load(_lib.SIGNATURES)      # the C double has the core ABI only, and that is not an error
-    assert not any(hasattr(core, n) for n in _lib.SPLIT2_SIGNATURES)
+    for two, three in (("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split_pack_bytes"),
+                       ("skd_conv3x3_split2_pack_weights", "skd_conv3x3_split_pack_weights"),
+                       ("skd_conv3x3_split2_nhwc", "skd_conv3x3_split_nhwc"),
+                       ("skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn_nhwc"),
+                       ("skd_conv1x1_abn2_pro_nhwc", "skd_conv1x1_abn_pro_nhwc")):
+        assert _lib.signature(two) == _lib.signature(three), two
+    assert all(three in _lib.ABI["skd_eval.h"] for three in ("skd_conv3x3_split_pack_bytes", "skd_conv3x3_split_pack_weights",
+                                                             "skd_conv3x3_split_nhwc"))
+    assert "skd_conv1x1_abn_nhwc" in _lib.SIGNATURES and "skd_conv1x1_abn_pro_nhwc" in _lib.SIGNATURES
 
 
 def test_header_states_the_numerics():
-    with open(_lib.SPLIT2_HEADER_PATH) as fh:
+    with open(_lib.header_path("skd_split2.h")) as fh:
         text = fh.read()
     for phrase in ("a0 b1,  a1 b0,  a0 b0", "a1 b1", "DROPPED", "2^24", "at most 8 significant bits", "3.39e38", "NaN"):
         assert phrase in text, phrase

@@ -1,12 +1,11 @@
-"""The frozen teacher on two FP16 pieces with a scaled residual (include_ext2/skd_split2h.h), the parts that need no GPU: the float64
-model of the mode (tests/split2h_ref.py) and why the residual is scaled, the C ABI (header <-> table <-> exported symbols, the host-side
+"""The frozen teacher on two FP16 pieces with a scaled residual (include/skd_split2h.h), the parts that need no GPU: the float64
+model of the mode (tests/split2h_ref.py) and why the residual is scaled, the C ABI (the pinned names and argument lists, the host-side
 refusals of the five entries), the fp16 ops beside the four recorded ones, the routing of a network marked by
 ``set_teacher_pieces(model, 2, piece_format="fp16")`` (a recording double of the 1x1 entries on top of the plain-C double; the 3x3
 ops, which refuse host tensors, are recorded at the op) and the public switch."""
 import ctypes
 import json
 import os
-import re
 import sys
 import warnings
 
@@ -17,7 +16,7 @@ import torch.nn.functional as F
 import split2h_ref as R
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 from structure_knowledge_distillation_amd.networks.kd_model import NetModel, default_args
 
@@ -111,33 +110,14 @@ def test_three_product_model_against_the_exact_product():
 # ---- 2. the C ABI ----------------------------------------------------------------------------------------------------------------
 
 def test_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.SPLIT2H_HEADER_PATH) == sorted(_lib.SPLIT2H_TABLE) == sorted(NAMES)
-    assert os.path.dirname(_lib.SPLIT2H_HEADER_PATH) == build.INCLUDE_EXT2, "include/ and include_ext/ are closed"
-    assert sorted(os.listdir(build.INCLUDE_EXT2)) == ["skd_split2h.h"]
-    others = [getattr(_lib, n) for n in dir(_lib) if n.endswith("SIGNATURES")]
-    assert not any(set(_lib.SPLIT2H_TABLE) & set(t) for t in others), "a table of its own"
-    with open(_lib.SPLIT2H_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert args.count(",") + 1 == len(_lib.SPLIT2H_TABLE[name][1]), name
-        found += 1
-    assert found == len(_lib.SPLIT2H_TABLE) == 5
+    """What is particular to skd_split2h.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_split2h.h"]) == sorted(NAMES) and len(NAMES) == 5
     for name, twin in TWINS.items():      # entry for entry the argument lists of include/skd_split2.h
-        assert _lib.SPLIT2H_TABLE[name] == _lib.SPLIT2_SIGNATURES[twin], name
-    raw = ctypes.CDLL(build.build())
-    for name in NAMES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.SPLIT2H_TABLE.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    core = cref.load(_lib.SIGNATURES)      # the C double has the core ABI only, and that is not an error
-    assert not any(hasattr(core, n) for n in NAMES)
+        assert _lib.signature(name) == _lib.signature(twin), name
 
 
 def test_header_states_the_numerics():
-    with open(_lib.SPLIT2H_HEADER_PATH) as fh:
+    with open(_lib.header_path("skd_split2h.h")) as fh:
         text = fh.read()
     for phrase in ("a0 = fp16(a)", "(a - a0) * 2^11", "lo += a0 b1", "lo += a1 b0", "hi += a0 b0", "fma(lo, 2^-11, hi)", "a1 b1",
                    "DROPPED", "at most 11 significant bits", "at most 22", "65504", "2^24", "NaN", "skd_split2.h", "SUBNORMAL",

@@ -1,4 +1,4 @@
-"""-m gpu: the fp16 two-piece forms of include_ext2/skd_split2h.h -- csrc/conv3x3.hip's 128-column forward family and
+"""-m gpu: the fp16 two-piece forms of include/skd_split2h.h -- csrc/conv3x3.hip's 128-column forward family and
 csrc/conv1x1.hip's GEMM with two FP16 pieces per operand and the residual scaled by 2^11 -- on small shapes:
 
   3x3: B = 1, 2; H x W = 9 x 13, 7 x 7; Cin = 16, 48; Cout = 128, 256; dilation 1, 2; every geometry 0 .. 3

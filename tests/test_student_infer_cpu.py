@@ -1,9 +1,7 @@
-"""The student's fused inference path, the parts that need no GPU: the C ABI of include/skd_infer.h (header <-> table <-> exported
-symbols, host-side refusals), the routing of flagged BasicBlocks (a recording double of the two 3x3 entries on top of the plain-C
+"""The student's fused inference path, the parts that need no GPU: the C ABI of include/skd_infer.h (the pinned names and argument lists; header <-> table <-> library is tests/test_abi.py, host-side refusals), the routing of flagged BasicBlocks (a recording double of the two 3x3 entries on top of the plain-C
 double), the wiring of the inference form against the plain op sequence (a torch-implemented double of the two entries) and
 NetModel's ``fused_eval`` flag."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,7 @@ import torch.nn.functional as F
 
 import structure_knowledge_distillation_amd.networks.pspnet_combine as PC
 from oracle import cref
-from structure_knowledge_distillation_amd import _lib, build, functional as SF
+from structure_knowledge_distillation_amd import _lib, functional as SF
 from structure_knowledge_distillation_amd import networks
 
 ENTRY, RES_ENTRY = "skd_conv3x3_split_nhwc", "skd_conv3x3_split_res_nhwc"
@@ -99,29 +97,11 @@ def computing():
 # ---- 1. the C ABI ------------------------------------------------------------------------------------------------------------
 
 def test_infer_header_table_and_library_agree():
-    assert _lib.header_prototypes(_lib.INFER_HEADER_PATH) == sorted(_lib.INFER_SIGNATURES) == [RES_ENTRY]
-    others = set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.MS_SIGNATURES) | set(_lib.OHEM_SIGNATURES)
-    assert not set(_lib.INFER_SIGNATURES) & others
-    for path in (_lib.HEADER_PATH, _lib.EXT_HEADER_PATH, _lib.MS_HEADER_PATH, _lib.OHEM_HEADER_PATH):
-        assert RES_ENTRY not in _lib.header_prototypes(path)
-    with open(_lib.INFER_HEADER_PATH) as fh:
-        text = re.sub(r"/\*.*?\*/", "", fh.read(), flags=re.S)
-    found = 0
-    for m in re.finditer(r"\b(skd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        assert (0 if args in ("", "void") else args.count(",") + 1) == len(_lib.INFER_SIGNATURES[name][1]), name
-        found += 1
-    assert found == len(_lib.INFER_SIGNATURES)
+    """What is particular to skd_infer.h; header <-> table <-> library <-> build digest: tests/test_abi.py, for every header."""
+    assert sorted(_lib.ABI["skd_infer.h"]) == [RES_ENTRY]
     # the existing entry's arguments with `residual` behind `out`
-    old, new = _lib.EXT_SIGNATURES[ENTRY], _lib.INFER_SIGNATURES[RES_ENTRY]
+    old, new = _lib.signature(ENTRY), _lib.signature(RES_ENTRY)
     assert new[0] == old[0] and new[1] == old[1][:9] + [ctypes.c_void_p] + old[1][9:]
-    raw = ctypes.CDLL(build.build())
-    for name in _lib.INFER_SIGNATURES:
-        assert hasattr(raw, name), "libskd_hip.so does not export %s" % name
-    typed = _lib.load()
-    for name, (res, args) in _lib.INFER_SIGNATURES.items():
-        assert getattr(typed, name).argtypes == args and getattr(typed, name).restype == res
-    assert _lib.INFER_HEADER_PATH.startswith(build.INCLUDE), "build._digest() covers every include/*.h"
 
 
 def test_infer_host_side_refusals():

@@ -1,5 +1,5 @@
 """GPU tool: the frozen teacher's conv1 -> bn1 -> relu -> conv2 link as bf16 piece planes (route_teacher_planes,
-include_ext/skd_planes.h), isolated -- writes the table of profiles/r31_planes_isolated.md.
+include/skd_planes.h), isolated -- writes the table of profiles/r31_planes_isolated.md.
 The four (reduce GEMM, 3x3) pairs a teacher forward has at batch 8 on 65 x 65 maps (a 512 x 512 step): PARENT {reduce GEMM with
 fp32 output + 3x3 on the fp32 map} against NEW {reduce GEMM with piece planes out + 3x3 on the planes}, the producer alone, the
 consumer alone and the pair back to back (the consumer then finds its input where the producer left it, as in the network).

@@ -30,7 +30,7 @@ def demangle(names):
 
 def one(src, tmp):
     flags = [f for f in B.FLAGS if f not in ("-shared",)]
-    cmd = [B.hipcc_path()] + flags + ["-c", "-I", B.INCLUDE, "-I", B.INCLUDE_EXT, "-I", B.INCLUDE_EXT2, "-I", B.CSRC, src, "-Rpass-analysis=kernel-resource-usage", "-o",
+    cmd = [B.hipcc_path()] + flags + ["-c", "-I", B.INCLUDE, "-I", B.CSRC, src, "-Rpass-analysis=kernel-resource-usage", "-o",
                                       os.path.join(tmp, os.path.basename(src) + ".o")]
     err = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], None

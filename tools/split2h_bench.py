@@ -1,4 +1,4 @@
-"""GPU tool: two fp16 pieces with a scaled residual (include_ext2/skd_split2h.h) against three bf16 pieces and against two bf16
+"""GPU tool: two fp16 pieces with a scaled residual (include/skd_split2h.h) against three bf16 pieces and against two bf16
 pieces (include/skd_split2.h), isolated, at the frozen teacher's batch-8 shapes of tools/split2_bench.py.  Three interleaved rounds
 (three, fp16 two, bf16 two, three, ...) of tools/_timing.warm_timed per shape on the same tensors; one JSON line per shape with the
 three rounds of each leg, the speed-ups (fastest round over fastest round) and whether the fp16 leg's rounds overlap the three-piece
