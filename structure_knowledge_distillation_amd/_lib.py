@@ -278,7 +278,16 @@ ABI["skd_split2h.h"] = {
     "skd_conv1x1_abn2h_pro_nhwc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _F, _P]),
 }
 
-SIGNATURES = ABI["skd.h"]      # the core ABI: what the plain-C double of oracle/ is typed from
+# include/skd_train2.h (csrc/conv3x3.hip, csrc/conv3x3_wgrad.hip with two pieces per operand): the training student's wide 3x3
+# convolutions at reduced precision, twins of skd_train.h / skd_wgrad.h.  A back-end without them leaves the student on three
+# pieces (route_training_convs(pieces=2) then routes the three-piece ops; the two-piece ops themselves raise NotImplementedError).
+ABI["skd_train2.h"] = {
+    "skd_conv3x3_split2_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
+    "skd_conv3x3_split2_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "skd_conv3x3_split2_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
+}
+
+SIGNATURES = ABI["skd.h"]     # the core ABI: what the plain-C double of oracle/ is typed from
 
 _lib = None
 _test_backend = None  # see install_test_backend()

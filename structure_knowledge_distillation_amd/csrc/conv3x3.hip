@@ -48,6 +48,7 @@
 #include "skd_split2h.h"
 #include "skd_stride2.h"
 #include "skd_train.h"
+#include "skd_train2.h"
 
 namespace skd {
 namespace {
@@ -682,6 +683,13 @@ int64_t skd_conv3x3_split2_pack_bytes(int Cin, int Cout) { return pack_bytes3<kT
 int skd_conv3x3_split2_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
                                     int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
   return pack_pair3<kTN, 2>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
+}
+
+// include/skd_train2.h: both two-plane images of a trained weight in one launch
+int skd_conv3x3_split2_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                 int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
+                                 skd_stream_t stream) {
+  return pack_pair3<kTN, 2>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack_fwd, fwd_bytes, pack_bwd, bwd_bytes, stream);
 }
 
 int skd_conv3x3_split2_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,

@@ -4,7 +4,7 @@
 //     dW[n][c][ty][tx] = sum_{m = (b, y, x)} g[m][n] * X[b, y + (ty - 1) d, x + (tx - 1) d, c]      (0 outside the image)
 //
 // with channels-last x (B, H, W, Cin) and g (B, H, W, Cout): nine GEMMs (Cout x P) (P x Cin), one per tap, reduced over the
-// P = B H W pixels.  One kernel, conv3x3_wgrad_kernel<NARROW>, in two tile forms.
+// P = B H W pixels.  One kernel, conv3x3_wgrad_kernel<NARROW, TAPS, PIECES>, in two tile forms.
 //
 // WIDE (skd_wgrad.h; Cin and Cout multiples of 128).  Operand A rows = 128 output channels of g, operand B rows = 128 input
 // channels of the shifted x, K = the pixel index in K-tiles of 16 pixels; tile_mma<128> with its two accumulator sets, k_loop<2>
@@ -67,6 +67,7 @@
 #include "conv_split_dev.hpp"
 #include "skd_narrow_wgrad.h"
 #include "skd_shortcut.h"
+#include "skd_train2.h"
 #include "skd_wgrad.h"
 
 #ifndef SKD_WGRAD_GRID_ORDER
@@ -98,7 +99,7 @@ struct StagingW {
   float4 v[4];                                         // pixels 4 q .. 4 q + 3, channels 4 r .. 4 r + 3
 };
 
-template <bool NARROW, int TAPS = 9>
+template <bool NARROW, int TAPS = 9, int PIECES = 3>
 struct TileW {
   typedef StagingW Stg;
   static constexpr int WM = NARROW ? 1 : 2;
@@ -184,12 +185,12 @@ struct TileW {
       const float4 row = make_float4(p[0][j], p[1][j], p[2][j], p[3][j]);
       // NARROW: g's 64-row image has its pieces 2 * 128 slots apart; a wave-uniform branch keeps both distances immediates
       if (NARROW && !is_x) split_store(row, base + slot[j], 2 * 2 * kUnit);
-      else split_store(row, base + slot[j]);
+      else split_store<PIECES>(row, base + slot[j]);
     }
   }
   __device__ __forceinline__ void mma(const uint4 *stage) const {
     if constexpr (NARROW) tile_mma<kTM, kUnit, true>(stage, low, acc);
-    else tile_mma<kTM>(stage, low, acc);
+    else tile_mma<kTM, kTN, false, PIECES>(stage, low, acc);
   }
 };
 
@@ -197,13 +198,18 @@ struct TileW {
 // NARROW: 64 accumulator registers: three per CU, the LDS ring's limit (3 x 48 KB of 160).
 // TAPS == 1 (skd_shortcut.h): the weight gradient of a 1x1 convolution of stride `dil` without padding as the one-tap form of both:
 // H, W are the output's sizes (the pixels of g), Hin, Win the input's; the one tap is the centre (no shift, always inside).
-template <bool NARROW, int TAPS = 9>
+// PIECES = 2 (skd_train2.h; WIDE with nine taps alone): both operands are cut into two pieces in the staging and three products
+// are kept per K-tile -- a0 b1 and a1 b0 into `low`, a0 b0 into `acc`, the two-set rule as it is.  The LDS ring shrinks to
+// conv_lds(2) = 32 KB; the 128 accumulator registers stay, so the two workgroups per CU stay too (three would leave 168
+// registers a lane for 128 accumulators, two staging sets and the fragments: profiles/r33_kernel_resources.md).
+template <bool NARROW, int TAPS = 9, int PIECES = 3>
 __global__ __launch_bounds__(kThreads, Form<NARROW>::per_cu)
 __attribute__((amdgpu_waves_per_eu(Form<NARROW>::per_cu, Form<NARROW>::per_cu)))
 void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ part, int P, int H, int W,
                           int Cin, int Cout, int dil, int nk, int tiles_per_slice, int slices, unsigned rcp_hw, unsigned rcp_w,
                           int total, int Hin, int Win) {
   static_assert(TAPS == 9 || TAPS == 1, "the 3x3 convolution, or its centre tap alone");
+  static_assert(PIECES == 3 || (PIECES == 2 && !NARROW && TAPS == 9), "two pieces: the wide nine-tap form alone");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   constexpr int WM = NARROW ? 1 : 2;
   const int per_xcd = (int)(gridDim.x >> 3);
@@ -281,14 +287,14 @@ void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__
     const int s = (r >> 1) & 3;
     const int C = is_x ? Cin : Cout;
     const float *src = (is_x ? X + tc * kTN : G + tn * kTM) + 4 * r;
-    TileW<false, TAPS> tile = {src,
+    TileW<false, TAPS, PIECES> tile = {src,
                          is_x ? ((int64_t)(ty - 1) * W + (tx - 1)) * dil : 0,
                          C, P, H, W, H * W, rcp_hw, rcp_w,
                          is_x ? (ty - 1) * dil : 0, is_x ? (tx - 1) * dil : 0,
                          kt0 * kBK + 4 * q, is_x, true, s, {}, Hin * Win, dil * Win, dil, low, acc};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) tile.slot[j] = (is_x ? 2 * kOperandChunks : 0) + plane_slot(4 * r + (j ^ s), 4 * q);
-    k_loop<kWgDepth>(tile, nks, lds);
+    for (int j = 0; j < 4; ++j) tile.slot[j] = (is_x ? 2 * operand_chunks(PIECES) : 0) + plane_slot(4 * r + (j ^ s), 4 * q);
+    k_loop<kWgDepth, PIECES>(tile, nks, lds);
 
     // ---- epilogue: the slice's 128 x 128 block of part[slice][n][tap][c], every element written ----
     const int wi = (wid >> 1) * (kTM / 2), wj = (wid & 1) * 64;
@@ -435,7 +441,7 @@ int plan_of(int B, int H, int W, int Cin, int Cout, int slices, int cus, int64_t
 }
 
 // TAPS == 1: `dilation` is 1, x has H x W pixels an image and g (H - 1) / stride + 1 by (W - 1) / stride + 1 (plan_of).
-template <bool NARROW, int TAPS = 9>
+template <bool NARROW, int TAPS = 9, int PIECES = 3>
 int launch(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const float *g, float *dw, int64_t sn, int64_t sc,
            int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes, int slices, skd_stream_t stream, int stride = 1) {
   if (!x || !g || !dw || !workspace || B < 1 || H < 1 || W < 1 || stride < 1) return 0;
@@ -460,13 +466,13 @@ int launch(int B, int H, int W, int Cin, int Cout, int dilation, const float *x,
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel<NARROW, TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)kConvLds) != hipSuccess) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel<NARROW, TAPS, PIECES>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)conv_lds(PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
   hipStream_t st = as_stream(stream);
   float *part = static_cast<float *>(workspace);
-  conv3x3_wgrad_kernel<NARROW, TAPS><<<dim3((unsigned)grid), dim3(kThreads), kConvLds, st>>>(
+  conv3x3_wgrad_kernel<NARROW, TAPS, PIECES><<<dim3((unsigned)grid), dim3(kThreads), conv_lds(PIECES), st>>>(
       x, g, part, (int)P, Ho, Wo, Cin, Cout, TAPS == 1 ? stride : dilation, (int)nk, (int)per_slice, (int)used,
       reciprocal32((unsigned)(Ho * Wo)), reciprocal32((unsigned)Wo), (int)total, H, W);
   if (!ok()) return 0;
@@ -515,6 +521,18 @@ int skd_conv3x3_narrow_wgrad_nhwc(int B, int H, int W, int Cin, int Cout, int di
                                   int64_t sn, int64_t sc, int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes,
                                   int slices, skd_stream_t stream) {
   return launch<true>(B, H, W, Cin, Cout, dilation, x, g, dw, sn, sc, sy, sx, workspace, workspace_bytes, slices, stream);
+}
+
+// Two pieces per operand (skd_train2.h): the predicate, the plan and the workspace of the three-piece entries, the wide kernel
+// with PIECES = 2 and the same reduce launch.
+int skd_conv3x3_split2_wgrad_plan(int B, int H, int W, int Cin, int Cout, int slices, int cus, int64_t *plan) {
+  return plan_of<false>(B, H, W, Cin, Cout, slices, cus, plan);
+}
+
+int skd_conv3x3_split2_wgrad_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const float *g, float *dw,
+                                  int64_t sn, int64_t sc, int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes,
+                                  int slices, skd_stream_t stream) {
+  return launch<false, 9, 2>(B, H, W, Cin, Cout, dilation, x, g, dw, sn, sc, sy, sx, workspace, workspace_bytes, slices, stream);
 }
 
 // The 1x1 convolution of stride 1 or 2 (skd_shortcut.h): the one-tap form of the kernel, the 128 x 128 tiles where both channel

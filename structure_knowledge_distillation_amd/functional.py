@@ -255,10 +255,10 @@ def _cached(owner, attr, key, build, hold=None):
 def drop_conv3x3_packs(owner):
     """Forget the weight packs conv3x3_pack_weights (both piece counts, both piece formats) / conv3x3_train_packs / conv3x3_narrow_pack_weights /
     conv3x3_split_train's narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under
-    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train")."""
+    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train"; the two-plane training pair of include/skd_train2.h too)."""
     slot = owner if isinstance(owner, dict) else vars(owner)
-    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", "pack3x3", "pack3x3_2", "pack3x3_2h",
-                 "pack3x3_train") + _NARROW_PACK_ATTRS:
+    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", _TRAIN2_PACK_ATTR, "pack3x3", "pack3x3_2",
+                 "pack3x3_2h", "pack3x3_train") + _NARROW_PACK_ATTRS:
         slot.pop(attr, None)
 
 
@@ -474,7 +474,8 @@ def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, spli
     slice of the weight, so that autograd carries its gradient back into the full weight; packs once per weight version in `cache`).
     `split_wgrad`: with `split_train`, the weight gradient of that slice on the split core too (conv3x3_split_train's ``wgrad``).
     `pieces` = 2: with `split3x3`, the frozen feature-map convolution on the two-piece core (conv3x3_split_eval's ``pieces``), its
-    pack under a key of its own in `cache`; the fold's matrix products and the training form are what they were.
+    pack under a key of its own in `cache`; with `split_train`, the training form on two bf16 pieces (conv3x3_split_train2,
+    include/skd_train2.h), its pack pair in a slot of its own; the fold's matrix products are what they were.
     `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include/skd_split2h.h), its pack under a third key."""
     _check_piece_format(_check_pieces(pieces), piece_format)
     import torch.nn.functional as F
@@ -494,7 +495,8 @@ def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, spli
     wf, w_all = _cached(cache if frozen else None, "mats", _version_key((weight,), tuple(weight.shape)), mats)
     if train:
         extra = dict(wgrad=True) if split_wgrad else {}
-        base = conv3x3_split_train(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}), **extra)
+        train_op = conv3x3_split_train2 if pieces == 2 and piece_format == "bf16" else conv3x3_split_train
+        base = train_op(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}), **extra)
     elif split3x3 and cache is not None and _conv3x3_ok(feats, weight[:, n_prior:], 1, 1, 1, 1, **_FROZEN):
         if pieces == 2:
             if piece_format == "fp16":
@@ -1038,15 +1040,49 @@ def conv3x3_pack_weights_fp16(conv, weight=None, owner=None):
 conv3x3_pack_weights.__doc__ = _conv3x3_pack_weights.__doc__
 
 
-def conv3x3_train_packs(weight, owner=None):
+# include/skd_train2.h: the two-piece forms of the training student's wide convolutions -- the pack pair, the weight gradient's
+# plan and launch -- and the slot the two-plane pair is cached in (its own: switching the piece count never serves the other image)
+_TRAIN2_PACK_PAIR, _TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD = ("skd_conv3x3_split2_pack_pair", "skd_conv3x3_split2_wgrad_plan",
+                                                        "skd_conv3x3_split2_wgrad_nhwc")
+_TRAIN2_PACK_ATTR = "_skd_conv3x3_train_pack2"
+
+
+def _need_train2_entry(name):
+    if not _lib.has_entry(name):
+        raise NotImplementedError("the active back-end does not provide %s (include/%s)"
+                                  % (name, "skd_train2.h" if name in _lib.ABI["skd_train2.h"] else "skd_split2.h"))
+
+
+def _conv3x3_train_packs(weight, owner=None, pieces=3):
     """``(pack_fwd, pack_bwd)`` of a trained (Cout, Cin, 3, 3) weight: the image csrc/conv3x3.hip streams for the forward
     convolution and the image of the flipped, transposed weight for its data gradient, written by ONE launch of
     skd_conv3x3_split_pack_pair under no_grad.  Cached on ``owner`` (a dict or any object that takes attributes; None: no cache)
     as conv3x3_pack_weights does: one split per weight version, so once per optimizer step -- provided the optimizer advances
     ``_version`` (torch's fused multi-tensor optimizers do not: networks.kd_model.advance_versions_after_step is the step
-    post-hook that does it for them)."""
+    post-hook that does it for them).
+    ``conv3x3_train_packs2``: the two-plane images of include/skd_train2.h (skd_conv3x3_split2_pack_pair, 4 bytes per weight),
+    for skd_conv3x3_split2_nhwc in both directions; cached under the same rule in a slot of its own, so the pairs of both piece
+    counts coexist on one owner and neither is ever served for the other.  A back-end without the entry raises
+    NotImplementedError.  (A twin, not a ``pieces`` argument: tests/golden/routing_census.json records every call of the public
+    conv3x3_* ops with its defaults filled in, so their signatures stay what they are -- as for the ``_fp16`` twins.)"""
+    if _check_pieces(pieces) == 2:
+        for name in (_TRAIN2_PACK_PAIR, _PACK2_BYTES):
+            _need_train2_entry(name)
+        return _conv3x3_packs(weight, owner, _TRAIN2_PACK_ATTR, _TRAIN2_PACK_PAIR, "conv3x3_train_packs", (True, True), _PACK2_BYTES)
     return _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack", "skd_conv3x3_split_pack_pair", "conv3x3_train_packs",
                           (True, True))
+
+
+def conv3x3_train_packs(weight, owner=None):
+    return _conv3x3_train_packs(weight, owner, 3)
+
+
+def conv3x3_train_packs2(weight, owner=None):
+    """``conv3x3_train_packs`` for ``conv3x3_split_train2``: the two-plane pair of include/skd_train2.h, in a slot of its own."""
+    return _conv3x3_train_packs(weight, owner, 2)
+
+
+conv3x3_train_packs.__doc__ = _conv3x3_train_packs.__doc__
 
 
 _ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
@@ -1176,9 +1212,10 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
                            _residual_cl(x, cout, residual))
 
 
-def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None):
-    """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc."""
-    return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias)
+def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None, pieces=3):
+    """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc, or
+    -- ``pieces`` = 2, ``pack`` a two-plane image -- of skd_conv3x3_split2_nhwc."""
+    return _conv3x3_launch(_SPLIT2_ENTRY if pieces == 2 else "skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias)
 
 
 def _conv3x3_narrow_launch(x, pack, cout, dilation, conv_bias=None):
@@ -1379,14 +1416,34 @@ def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilati
     return dw
 
 
-def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
+def _conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0, pieces=3):
     """The weight gradient of the same-size 3x3 convolution ``F.conv2d(x, w, None, 1, dilation, dilation)`` for the output gradient
     ``g``, on the split core (csrc/conv3x3_wgrad.hip: both operands split in the loop, split-K over the pixels into a workspace,
     a second launch that sums the slices in a fixed order -- the same bits on every call).  ``x`` (B, Cin, H, W) and ``g``
     (B, Cout, H, W): fp32, channels-last, 16-byte aligned.  ``weight_like`` gives shape, device and layout of the result: its own
     strides when it is non-overlapping and dense, channels-last otherwise (a channel slice of a wider weight).  ``slices``: 0 =
-    the plan's choice for the tensor's device."""
+    the plan's choice for the tensor's device.
+    ``conv3x3_split_wgrad2``: the two-piece form of include/skd_train2.h -- both operands cut into two bf16 pieces, three
+    products, the same plan, workspace and slice sum (the numerics of conv3x3_split_eval's ``pieces=2``).  A back-end without
+    the entries raises NotImplementedError."""
+    if _check_pieces(pieces) == 2:
+        for name in (_TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD):
+            _need_train2_entry(name)
+        return _conv3x3_wgrad_launch("conv3x3_split_wgrad", _TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD, x, g, weight_like, dilation, slices)
     return _conv3x3_wgrad_launch("conv3x3_split_wgrad", _WGRAD_ENTRIES[1], _WGRAD_ENTRIES[2], x, g, weight_like, dilation, slices)
+
+
+def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
+    return _conv3x3_split_wgrad(x, g, weight_like, dilation, slices, 3)
+
+
+def conv3x3_split_wgrad2(x, g, weight_like, dilation, slices=0):
+    """``conv3x3_split_wgrad`` on two bf16 pieces per operand and three products (include/skd_train2.h): the same arguments, the
+    same plan and result layout."""
+    return _conv3x3_split_wgrad(x, g, weight_like, dilation, slices, 2)
+
+
+conv3x3_split_wgrad.__doc__ = _conv3x3_split_wgrad.__doc__
 
 
 _NARROW_WGRAD_ENTRIES = ("skd_conv3x3_narrow_wgrad_supported", "skd_conv3x3_narrow_wgrad_plan", "skd_conv3x3_narrow_wgrad_nhwc")
@@ -1418,7 +1475,9 @@ class _Conv3x3SplitTrain(Function):
     conv3x3_split_wgrad's where the back-end has its entries, and the library computes the bias gradient alone; ``"narrow"`` in
     its place (conv3x3_split_train's ``narrow_wgrad``) asks for conv3x3_narrow_wgrad's in the same way.  A fourth optional argument
     (conv3x3_split_train's ``stats``) makes the forward return ``(y, partials)`` -- the same ``y`` and the statistics records of
-    include/skd_bnstats.h, marked non-differentiable; the backward is the same."""
+    include/skd_bnstats.h, marked non-differentiable; the backward is the same.  A fifth (2, from conv3x3_split_train2) is the
+    piece count of the wide form's products: the packs are two-plane images, forward and data gradient run
+    skd_conv3x3_split2_nhwc and ``wgrad`` is conv3x3_split_wgrad2's (include/skd_train2.h)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, *wgrad):
@@ -1429,13 +1488,14 @@ class _Conv3x3SplitTrain(Function):
         ctx.narrow_wgrad = bool(wgrad) and wgrad[0] == "narrow"
         # (forward?, backward?) on the narrow entry: the third optional argument (conv3x3_split_train's ``narrow``)
         fwd_narrow, ctx.bwd_narrow = wgrad[1] if len(wgrad) > 1 else (False, False)
+        ctx.two = two = dict(pieces=2) if len(wgrad) > 3 and wgrad[3] == 2 else {}      # the keyword only where it says 2
         if len(wgrad) > 2 and wgrad[2]:
             y, partials = _conv3x3_stats_launch(fwd_narrow, x, pack_fwd, int(weight.shape[0]), dilation, bias)
             ctx.mark_non_differentiable(partials)
             return y, partials
         if fwd_narrow:
             return _conv3x3_narrow_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
-        return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
+        return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias, **two)
 
     @staticmethod
     @once_differentiable
@@ -1447,10 +1507,16 @@ class _Conv3x3SplitTrain(Function):
             g = g.clone(memory_format=torch.channels_last)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = (_conv3x3_narrow_launch if ctx.bwd_narrow else _conv3x3_split_launch)(g, ctx.pack_bwd, int(weight.shape[1]), d)
+            if ctx.bwd_narrow:
+                dx = _conv3x3_narrow_launch(g, ctx.pack_bwd, int(weight.shape[1]), d)
+            else:
+                dx = _conv3x3_split_launch(g, ctx.pack_bwd, int(weight.shape[1]), d, **ctx.two)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         if ctx.wgrad and need_w and all(_lib.has_entry(n) for n in (_NARROW_WGRAD_ENTRIES if ctx.narrow_wgrad else _WGRAD_ENTRIES)):
-            dw = (conv3x3_narrow_wgrad if ctx.narrow_wgrad else conv3x3_split_wgrad)(x, g, weight, d)
+            if ctx.narrow_wgrad:
+                dw = conv3x3_narrow_wgrad(x, g, weight, d)
+            else:
+                dw = (conv3x3_split_wgrad2 if ctx.two else conv3x3_split_wgrad)(x, g, weight, d)
             need_w = False
         if need_w or need_b:
             _, lw, db = torch.ops.aten.convolution_backward(g, x, weight, [int(weight.shape[0])] if ctx.has_bias else None,
@@ -1459,7 +1525,8 @@ class _Conv3x3SplitTrain(Function):
         return (dx, dw, db) + (None,) * (ctx.n_inputs - 3)
 
 
-def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False):
+def _conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False,
+                         pieces=3):
     """``F.conv2d(x, weight, bias, 1, dilation, dilation)`` for a call conv3x3_train_supported accepted, differentiable: forward
     and data gradient are one launch each of the split-core implicit GEMM (csrc/conv3x3.hip: fp32 in and out, three bf16 pieces,
     six products, fp32 accumulation; the numerics of conv3x3_split_eval in both directions), the weight and bias gradients come
@@ -1475,21 +1542,47 @@ def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=Fal
     ``(y, partials)`` -- ``y`` bit for bit what the call returns without it, and ``partials``, the batch-norm statistics records the
     forward's epilogue wrote (include/skd_bnstats.h: one (mean, M2) per 32-row block of B * H * W and output channel), not
     differentiable, for ``abn_relu_train(y, ..., partials=partials)``.  The backward, and ``wgrad`` / ``narrow`` /
-    ``narrow_wgrad``, are what they are without it."""
+    ``narrow_wgrad``, are what they are without it.
+    ``conv3x3_split_train2`` (opt-in, an ACCURACY trade; include/skd_train2.h): forward, data gradient and -- with ``wgrad`` -- weight
+    gradient of the WIDE form on two bf16 pieces per operand and three products: 16 significant bits per operand, every element
+    within 2^-15 of the sum of absolute products of the exact result.  The packs are the two-plane pair (conv3x3_train_packs2),
+    cached apart from the three-piece pair.  A direction ``narrow`` puts on the 64-column form and a call with
+    ``stats`` have no two-piece form: they keep three pieces.  The library's weight gradient (``wgrad=False``) and the bias gradient
+    are what they were.  A back-end without the entries raises NotImplementedError."""
+    pieces = _check_pieces(pieces)
     if stats and not conv3x3_bnstats_supported():
         raise NotImplementedError("this back-end has no include/skd_bnstats.h entries")
+    if pieces == 2:
+        for name in (_TRAIN2_PACK_PAIR, _SPLIT2_ENTRY, _PACK2_BYTES) + ((_TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD) if wgrad else ()):
+            _need_train2_entry(name)
     if narrow:
         pack_fwd, pack_bwd, fwd_narrow, bwd_narrow = _conv3x3_narrow_train_packs(weight, owner)
         if fwd_narrow or bwd_narrow:
             tail = (True,) if stats else ()
             return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, "narrow" if narrow_wgrad else False,
                                             (fwd_narrow, bwd_narrow), *tail)
+    if pieces == 2 and not stats:
+        pack_fwd, pack_bwd = conv3x3_train_packs2(weight, owner)
+        return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), False, 2)
     pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
     if stats:
         return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), True)
     if wgrad:
         return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, True)
     return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd)
+
+
+def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False):
+    return _conv3x3_split_train(x, weight, dilation, bias, owner, wgrad=wgrad, narrow=narrow, narrow_wgrad=narrow_wgrad, stats=stats)
+
+
+def conv3x3_split_train2(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False):
+    """``conv3x3_split_train`` with the wide form on two bf16 pieces per operand and three products (include/skd_train2.h)."""
+    return _conv3x3_split_train(x, weight, dilation, bias, owner, wgrad=wgrad, narrow=narrow, narrow_wgrad=narrow_wgrad, stats=stats,
+                                pieces=2)
+
+
+conv3x3_split_train.__doc__ = _conv3x3_split_train.__doc__
 
 
 # ---- the training student's 1x1 down-sample (shortcut) convolutions on the split core (include/skd_shortcut.h) ----

@@ -182,9 +182,18 @@ class NetModel():
         # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
         if getattr(args, "fused_eval", False):
             fuse_for_inference(student, narrow=self.split_narrow, stride2=self.split_stride2)
+        # args.student_pieces (None: SKD_STUDENT_PIECES, default "3"; outside SWITCHES, like teacher_pieces): 2 = the student's 13 wide
+        # training convolutions on two bf16 pieces per operand and three products (route_training_convs(pieces=2),
+        # include/skd_train2.h) -- an ACCURACY trade, effective only together with split_train: without it nothing is routed.
+        self.student_pieces = _student_pieces(getattr(args, "student_pieces", None))
+        if self.student_pieces == 2 and not self.split_train:
+            import warnings
+            warnings.warn("student_pieces / SKD_STUDENT_PIECES = 2 takes effect only together with split_train / SKD_SPLIT_TRAIN: "
+                          "nothing is routed and the student's convolutions are what they were", RuntimeWarning, stacklevel=2)
         if self.split_train:
             route_training_convs(student, wgrad=self.split_wgrad, narrow=self.split_narrow, narrow_wgrad=self.split_narrow_wgrad,
-                                 shortcut=self.split_shortcut, bnstats=self.split_bnstats)
+                                 shortcut=self.split_shortcut, bnstats=self.split_bnstats,
+                                 **(dict(pieces=2) if self.student_pieces == 2 else {}))
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -911,6 +920,15 @@ def _teacher_pieces(value):
     return int(str(value).strip())
 
 
+def _student_pieces(value):
+    """``value`` (None: the environment's SKD_STUDENT_PIECES, default "3") as 2 or 3; anything else is a ValueError."""
+    if value is None:
+        value = os.environ.get("SKD_STUDENT_PIECES", "3")
+    if isinstance(value, bool) or str(value).strip() not in ("2", "3"):
+        raise ValueError("student_pieces / SKD_STUDENT_PIECES must be 2 or 3, not %r" % (value,))
+    return int(str(value).strip())
+
+
 def _teacher_piece_format(value, pieces):
     """``value`` (None: the environment's SKD_TEACHER_PIECE_FORMAT, default "bf16") as "bf16" or "fp16"; anything else, and "fp16"
     with ``pieces`` other than 2, is a ValueError."""
@@ -944,7 +962,7 @@ def default_args(**overrides):
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
         split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None, teacher_planes=None,
-        teacher_piece_format=None)
+        teacher_piece_format=None, student_pieces=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     for name, env, _ in SWITCHES:      # None: the environment switch
@@ -952,5 +970,6 @@ def default_args(**overrides):
             setattr(a, name, _switch(a, name, env))
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     a.teacher_piece_format = _teacher_piece_format(a.teacher_piece_format, a.teacher_pieces)      # "fp16": two fp16 pieces (skd_split2h.h)
+    a.student_pieces = _student_pieces(a.student_pieces)      # 2: the student's wide training convolutions on two pieces; default 3
     a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include/skd_planes.h)
     return a

@@ -86,6 +86,16 @@ TRAIN_ROUTING_EXCLUDED = frozenset()
 # library by more than the spread is listed here as (Cin, Cout, dilation) and keeps the library for its weight gradient
 # (profiles/r20_conv3x3_wgrad_isolated.md has every shape).
 WGRAD_ROUTING_EXCLUDED = frozenset()
+# The wide convolutions of the training form on TWO bf16 pieces per operand and three products (route_training_convs(pieces=2); a
+# further opt-in on top of the training form, an ACCURACY trade: include/skd_train2.h): forward, data gradient
+# and -- with ``wgrad`` -- weight gradient of the 13 convolutions above take the two-piece entries.  A shape that does not measure
+# ahead of its three-piece twin by more than the spread is listed here as (Cin, Cout, dilation) and keeps three pieces
+# (profiles/r33_student_pieces_isolated.md).
+# Measured on the MI355X at batch 8, 65 x 65: all seven shapes are ahead -- forward + data gradient + pack pair 1.57 - 1.67 x, the
+# weight gradient 1.35 - 1.48 x, spreads of at most 3.2 % -- so the set is empty and the weight gradient needs no set of its own.
+STUDENT_PIECES_ROUTING_EXCLUDED = frozenset()
+_TRAIN2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_pair",
+                   "skd_conv3x3_split2_wgrad_plan", "skd_conv3x3_split2_wgrad_nhwc")
 # The 64-channel convolutions (fuse_for_inference(narrow=True), route_training_convs(narrow=True); a further opt-in on top of either):
 # the stem's conv2 (64 -> 64) and layer1's four convolutions (128 -> 64, then three 64 -> 64) on the 64-column form of the kernel
 # (csrc/conv3x3.hip with 64-column tiles), the stem's conv3 (64 -> 128) on the wide kernel in the forward and on the narrow one for its data
@@ -268,6 +278,16 @@ def _wgrad_routed(module, cin, cout, dilation):
     return bool(getattr(module, "_skd_train_wgrad", False)) and (cin, cout, dilation) not in WGRAD_ROUTING_EXCLUDED
 
 
+def _student_pieces(module, cin, cout, dilation):
+    """The piece count of a WIDE convolution the flagged ``module`` routes: 2 where route_training_convs(pieces=2) marked it, the
+    back-end has the entries of include/skd_train2.h (and the two of skd_split2.h they build on) and the shape is outside
+    STUDENT_PIECES_ROUTING_EXCLUDED; 3 otherwise."""
+    if (getattr(module, "_skd_train_pieces", 3) == 2 and (cin, cout, dilation) not in STUDENT_PIECES_ROUTING_EXCLUDED
+            and all(_lib.has_entry(n) for n in _TRAIN2_ENTRIES)):
+        return 2
+    return 3
+
+
 def _train_form(module, x, conv, bn=None):
     """``(form, wgrad, stats)``: how the flagged ``module`` (route_training_convs) in training mode runs ``conv(x)``.
     ``form``: "wide" -- SF.conv3x3_split_train: at least ``_skd_train_min_cin`` input channels, outside TRAIN_ROUTING_EXCLUDED
@@ -306,8 +326,11 @@ def _train_conv(module, conv, x, bn=None):
     if form is None:
         return conv(x), None
     narrow = form == "narrow"
-    out = SF.conv3x3_split_train(x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=wgrad and not narrow, narrow=narrow,
-                                 narrow_wgrad=wgrad and narrow, stats=stats)
+    # two pieces: the wide form without statistics alone (the twin op only where the count is 2: every other call is what it was)
+    two = not narrow and not stats and _student_pieces(module, conv.in_channels, conv.out_channels, conv.dilation[0]) == 2
+    out = (SF.conv3x3_split_train2 if two else SF.conv3x3_split_train)(
+        x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=wgrad and not narrow, narrow=narrow,
+        narrow_wgrad=wgrad and narrow, stats=stats)
     return out if stats else (out, None)
 
 
@@ -613,8 +636,10 @@ class PSPModule(nn.Module):
                 if not hasattr(self, "_fold_cache"):
                     self._fold_cache = {}
                 min_cin = getattr(self, "_skd_train_min_cin", None)
-                # the frozen feature half on two pieces, bf16 or fp16 (set_teacher_pieces)
-                pieces, fmt = (3, "bf16") if self.training else _piece_route(self, "3x3", feats.shape[1], conv.out_channels, 1)
+                # the frozen feature half on two pieces, bf16 or fp16 (set_teacher_pieces); the trained one on two bf16 pieces
+                # (route_training_convs(pieces=2))
+                pieces, fmt = ((_student_pieces(self, feats.shape[1], conv.out_channels, 1), "bf16") if self.training
+                               else _piece_route(self, "3x3", feats.shape[1], conv.out_channels, 1))
                 fold, kw = _piece_op("ppm_fold_bottleneck", pieces, fmt)
                 out = fold(priors, feats, conv.weight, self._fold_cache,
                            split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
@@ -935,7 +960,7 @@ def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
 
 
 def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False, narrow=False, narrow_wgrad=False,
-                         shortcut=False, bnstats=False):
+                         shortcut=False, bnstats=False, pieces=3):
     """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
 
     A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
@@ -965,8 +990,19 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     the forward_relu behind it finishes them and applies, except for the shapes of BNSTATS_ROUTING_EXCLUDED; replicated
     (synchronised) normalisations, dsn[0], the stem, the PSP bottleneck and the shortcuts are what they were, and so are the
     convolution's output bits and every backward.  On a back-end without the entries nothing changes.
+    ``pieces=2`` -- an ACCURACY trade, opt-in: the 13 WIDE convolutions (layer2.0.conv2 to layer4, dsn[0], the feature half of the
+    PSP bottleneck) run forward and data gradient on two bf16 pieces per operand and three products (include/skd_train2.h,
+    SF.conv3x3_split_train2: skd_conv3x3_split2_nhwc on the two-plane pack pair), and with ``wgrad`` their weight gradients too
+    (SF.conv3x3_split_wgrad2, the two-piece form of csrc/conv3x3_wgrad.hip) except for the shapes of WGRAD_ROUTING_EXCLUDED,
+    whose weight gradients stay with the library; the shapes of STUDENT_PIECES_ROUTING_EXCLUDED keep three pieces.  16 significant bits per operand: every output element within
+    2^-15 of the sum of absolute products of the exact result (profiles/r33_student_pieces_accuracy.md).  These keep three
+    pieces, or the library, whatever ``pieces`` says: the 64-column forms of ``narrow`` and their weight gradients; the 1x1
+    shortcut convolutions of ``shortcut``; a convolution that writes statistics (``bnstats``); every stride-2 convolution.  On a
+    back-end without the entries the student stays on three pieces.  Anything but the integers 2 and 3 is a ValueError.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
+    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
+        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
     for m in model.modules():
         if not isinstance(m, (BasicBlock, ResNet, PSPModule)):
             continue
@@ -974,6 +1010,10 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
         m._skd_train_wgrad = bool(wgrad and enable)
         m._skd_train_narrow = bool(narrow and enable)
         m._skd_train_narrow_wgrad = bool(narrow_wgrad and enable)
+        if enable and pieces == 2:
+            m._skd_train_pieces = 2
+        else:
+            vars(m).pop("_skd_train_pieces", None)
         if isinstance(m, BasicBlock):
             m._skd_train_shortcut = bool(shortcut and enable)
             m._skd_train_bnstats = bool(bnstats and enable)

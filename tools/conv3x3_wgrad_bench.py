@@ -8,7 +8,10 @@ median of one side's rounds, the larger of the two sides.  ``--slices a,b,c``: f
 build of the library (say, one compiled with -DSKD_WGRAD_GRID_ORDER=1) timed in the same rounds, one more column.
 ``--narrow``: the six 64-channel convolutions of the stem (256 x 256) and layer1 (129 x 129) on skd_conv3x3_narrow_wgrad_nhwc
 instead -- the table of profiles/r23_conv3x3_narrow_wgrad_isolated.md; ``--hw`` is ignored.
-    python tools/conv3x3_wgrad_bench.py [--rounds 3] [--slices 1,2,4,8] [--lib other/libskd_hip.so] [--narrow]
+``--pieces 2``: the table of profiles/r33_student_pieces_wgrad_isolated.md instead -- the "parent" side is the THREE-piece
+skd_conv3x3_split_wgrad_nhwc, the other side skd_conv3x3_split2_wgrad_nhwc (include/skd_train2.h) on the same plan; the library is
+not timed.  Not with ``--narrow``, which has no two-piece form.
+    python tools/conv3x3_wgrad_bench.py [--rounds 3] [--slices 1,2,4,8] [--lib other/libskd_hip.so] [--narrow] [--pieces 2]
 """
 import argparse
 import ctypes
@@ -45,7 +48,10 @@ def main():
     ap.add_argument("--slices", default="")
     ap.add_argument("--lib", default=None)
     ap.add_argument("--narrow", action="store_true")
+    ap.add_argument("--pieces", type=int, default=3, choices=(2, 3))
     a = ap.parse_args()
+    if a.pieces == 2 and a.narrow:
+        ap.error("--pieces 2: the 128 x 64 form has no two-piece twin")
     import torch
     import structure_knowledge_distillation_amd as _skd
     _skd.configure_miopen()
@@ -59,10 +65,11 @@ def main():
     extra = [int(s) for s in a.slices.split(",") if s]
     med = statistics.median
     fmt = lambda runs: " / ".join("%.1f" % (1e3 * t) for t in runs)
-    form = "narrow" if a.narrow else "split"
+    form = "narrow" if a.narrow else "split2" if a.pieces == 2 else "split"
+    sides = ("three pieces", "two pieces") if a.pieces == 2 else ("parent", "split")
     print("%d compute units; batch %d, %s" % (cus, B, "the step's map sizes" if a.narrow else "%d x %d" % (hw, hw)))
     print()
-    print("| convolution | per step | slices (K-tiles each) | parent us (runs) | split us (runs) | parent / split | spread | verdict |"
+    print("| convolution | per step | slices (K-tiles each) | %s us (runs) | %s us (runs) | %s / %s | spread | verdict |" % (sides + sides)
           + (" --lib us (runs) |" if other else "") + "".join(" %d slices us |" % s for s in extra))
     print("|---|---|---|---|---|---|---|---|" + "---|" * (len(extra) + bool(other)))
     total_p = total_s = 0.0
@@ -77,7 +84,7 @@ def main():
             dw = torch.empty_like(w)
             st = _lib.stream_of(x)
 
-            def split_side(slices, lib=lib):
+            def split_side(slices, lib=lib, form=form):
                 assert getattr(lib, "skd_conv3x3_%s_wgrad_plan" % form)(B, hw, hw, cin, cout, slices, cus, ctypes.cast(plan, ctypes.c_void_p))
                 used, per_slice, nbytes = int(plan[0]), int(plan[1]), int(plan[2])
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -89,6 +96,8 @@ def main():
             run_s, used, per_slice = split_side(0)
             run_p = lambda: torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [d, d], [d, d], False, [0, 0], 1,
                                                                 (False, True, False))
+            if a.pieces == 2:
+                run_p = split_side(0, lib, "split")[0]
             run_o = split_side(0, other)[0] if other else None
             runs = {"p": [], "s": [], "o": []}
             for _ in range(a.rounds):
@@ -109,7 +118,8 @@ def main():
             print("| %s | %d | %d (%d) | %s | %s | %.2f | %.1f %% | %s |%s" % (
                 name, count, used, per_slice, fmt(runs["p"]), fmt(runs["s"]), parent / split, 100 * spread, verdict, cols), flush=True)
     print()
-    print("Per student step (the counts above): parent %.2f ms, split %.2f ms, difference %.2f ms." % (total_p, total_s, total_p - total_s))
+    print("Per student step (the counts above): %s %.2f ms, %s %.2f ms, difference %.2f ms." % (sides[0], total_p, sides[1], total_s,
+                                                                                            total_p - total_s))
 
 
 if __name__ == "__main__":
