@@ -287,7 +287,19 @@ ABI["skd_train2.h"] = {
     "skd_conv3x3_split2_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _I, _P]),
 }
 
-SIGNATURES = ABI["skd.h"]     # the core ABI: what the plain-C double of oracle/ is typed from
+# include/skd_infer2h.h (csrc/conv3x3.hip's residual-epilogue, 64-column and stride-2 forms with two FP16 pieces per operand): the
+# student's fused inference form at three products per K-step and the three-piece accuracy, twins of skd_infer.h / skd_narrow.h /
+# skd_stride2.h.  A back-end without them leaves the student on three bf16 pieces (pspnet_combine.fuse_for_inference warns; the
+# fp16 ops themselves raise NotImplementedError).
+ABI["skd_infer2h.h"] = {
+    "skd_conv3x3_split2h_res_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+    "skd_conv3x3_narrow2h_pack_bytes": (_L, [_I, _I]),
+    "skd_conv3x3_narrow2h_pack_weights": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P]),
+    "skd_conv3x3_narrow2h_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+    "skd_conv3x3_split2h_s2_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
+}
+
+SIGNATURES = ABI["skd.h"]    # the core ABI: what the plain-C double of oracle/ is typed from
 
 _lib = None
 _test_backend = None  # see install_test_backend()

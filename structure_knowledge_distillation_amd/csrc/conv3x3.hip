@@ -42,6 +42,7 @@
 #include "conv_split_dev.hpp"
 #include "skd_bnstats.h"
 #include "skd_infer.h"
+#include "skd_infer2h.h"
 #include "skd_narrow.h"
 #include "skd_planes.h"
 #include "skd_split2.h"
@@ -349,6 +350,10 @@ constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kM
 
 // PIECES = 2 keeps the residencies, the grid and the tile heights of its three-piece twin (include/skd_split2.h); so does
 // STRIDE = 2 (include/skd_stride2.h), whose M is that of the smaller output.
+// FMT = kFp16 (two fp16 pieces, include/skd_split2h.h) also has the residual-epilogue, 64-column and stride-2 forms
+// (include/skd_infer2h.h: the student's inference form); two bf16 pieces have the wide forms without residual alone.  The 64-column
+// two-piece form takes 28 KB of LDS: a stage is 512 chunks of A and 256 of B -- one copy per thread -- the second stage
+// stage_chunks(2) = 1024 chunks behind the first.
 template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
@@ -359,10 +364,10 @@ void conv3x3_split_kernel(
     int p_full, const float *__restrict__ R, float *__restrict__ stats) {
   static_assert(TALL || TN == kTN, "64-row panels exist for the 128-column form only");
   static_assert(!STATS || (ACT == SKD_ACT_NONE && !HAS_RES && PIECES == 3), "statistics: the training forward's raw epilogue alone");
-  static_assert(PIECES == 3 || (TN == kTN && !HAS_RES), "two pieces: the 128-column forward family without the residual");
+  static_assert(PIECES == 3 || FMT == kFp16 || (TN == kTN && !HAS_RES), "two bf16 pieces: the 128-column forward family without the residual");
   static_assert(STRIDE == 1 || (STRIDE == 2 && TN == kTN && !HAS_RES && !STATS), "stride 2: the 128-column frozen forward alone");
   static_assert(!PLANES || (TN == kTN && PIECES == 3 && !HAS_RES && !STATS && STRIDE == 1), "piece planes in: the wide stride-1 frozen forward alone");
-  static_assert(FMT == kBf16 || (PIECES == 2 && STRIDE == 1), "fp16 pieces: the two-piece stride-1 forward family alone");
+  static_assert(FMT == kBf16 || (PIECES == 2 && !STATS && !PLANES), "fp16 pieces: two of them, the frozen forward families alone (include/skd_infer2h.h)");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -463,7 +468,8 @@ static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, c
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
                     int geometry, hipStream_t st, float *stats = nullptr) {
   if constexpr (TN < kTN) {
-    return launch3<TN, ACT, true, HAS_RES, 3, STATS>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, 1, st, stats);
+    static_assert(STRIDE == 1 && !PLANES, "the 64-column form: stride 1 on an fp32 map");
+    return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, 1, false, FMT>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, 1, st, stats);
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
@@ -533,6 +539,11 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
   case ACT:                                                                                                                   \
     if constexpr (PIECES == 3)                                                                                                \
       return (residual != nullptr ? launch3g<TN, ACT, true> : launch3g<TN, ACT, false>)(                                     \
+          x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st,    \
+          nullptr);                                                                                                           \
+    else if constexpr (FMT == kFp16) /* include/skd_infer2h.h: the fp16 form has the residual epilogue */                     \
+      return (residual != nullptr ? launch3g<TN, ACT, true, PIECES, false, 1, false, FMT>                                     \
+                                  : launch3g<TN, ACT, false, PIECES, false, 1, false, FMT>)(                                  \
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st,    \
           nullptr);                                                                                                           \
     else                                                                                                                      \
@@ -610,7 +621,8 @@ static int taps_s2(int H, int W, int64_t m, int64_t *pixel, unsigned *mask) {
 
 // out (B, Ho, Wo, Cout) = act(ABN_eval(conv3x3_stride2(x) + conv_bias)): run3's refusals (no residual), on the packs of either
 // piece count -- the image does not depend on the stride.  Raw and ReLU epilogues are instantiated; leaky ReLU is refused.
-template <int PIECES>
+// FMT = kFp16 (include/skd_infer2h.h): on the two-plane fp16 image of skd_conv3x3_split2h_pack_weights.
+template <int PIECES, int FMT = kBf16>
 static int run3_s2(int B, int H, int W, int Cin, int Cout, const float *x, const void *wpack, float *out, const float *conv_bias,
                    const float *mean, const float *var, const float *weight, const float *bias, float eps, int activation,
                    float slope, int geometry, skd_stream_t stream) {
@@ -623,11 +635,11 @@ static int run3_s2(int B, int H, int W, int Cin, int Cout, const float *x, const
   const uint4 *bp = static_cast<const uint4 *>(wpack);
   switch (activation) {
     case SKD_ACT_NONE:
-      return launch3g<kTN, SKD_ACT_NONE, false, PIECES, false, 2>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps, slope, M,
-                                                                  H, W, Cin, Cout, 1, geometry, st);
+      return launch3g<kTN, SKD_ACT_NONE, false, PIECES, false, 2, false, FMT>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps,
+                                                                              slope, M, H, W, Cin, Cout, 1, geometry, st);
     case SKD_ACT_RELU:
-      return launch3g<kTN, SKD_ACT_RELU, false, PIECES, false, 2>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps, slope, M,
-                                                                  H, W, Cin, Cout, 1, geometry, st);
+      return launch3g<kTN, SKD_ACT_RELU, false, PIECES, false, 2, false, FMT>(x, bp, out, nullptr, conv_bias, mean, var, weight, bias, eps,
+                                                                              slope, M, H, W, Cin, Cout, 1, geometry, st);
     default: return 0;
   }
 }
@@ -712,6 +724,37 @@ int skd_conv3x3_split2h_nhwc(int B, int H, int W, int Cin, int Cout, int dilatio
                              float eps, int activation, float slope, int geometry, skd_stream_t stream) {
   return run3<kTN, 2, kFp16>(B, H, W, Cin, Cout, dilation, x, wpack, out, nullptr, conv_bias, mean, var, weight, bias, eps, activation,
                              slope, geometry, 3, stream);
+}
+
+// include/skd_infer2h.h: the residual-epilogue, 64-column and stride-2 forms on two fp16 pieces (the student's inference form).
+int skd_conv3x3_split2h_res_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                                 const float *residual, const float *conv_bias, const float *mean, const float *var,
+                                 const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
+                                 skd_stream_t stream) {
+  return run3<kTN, 2, kFp16>(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps, activation,
+                             slope, geometry, 3, stream);
+}
+
+int64_t skd_conv3x3_narrow2h_pack_bytes(int Cin, int Cout) { return pack_bytes3<kNarrowTN, 2>(Cin, Cout); }
+
+int skd_conv3x3_narrow2h_pack_weights(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                      int64_t stride_x, void *pack, int64_t pack_bytes, skd_stream_t stream) {
+  return pack_pair3<kNarrowTN, 2, kFp16>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack, pack_bytes, nullptr, 0, stream);
+}
+
+int skd_conv3x3_narrow2h_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                              const float *residual, const float *conv_bias, const float *mean, const float *var,
+                              const float *weight, const float *bias, float eps, int activation, float slope, int geometry,
+                              skd_stream_t stream) {
+  return run3<kNarrowTN, 2, kFp16>(B, H, W, Cin, Cout, dilation, x, wpack, out, residual, conv_bias, mean, var, weight, bias, eps,
+                                   activation, slope, geometry, 1, stream);
+}
+
+int skd_conv3x3_split2h_s2_nhwc(int B, int H, int W, int Cin, int Cout, const float *x, const void *wpack, float *out,
+                                const float *conv_bias, const float *mean, const float *var, const float *weight, const float *bias,
+                                float eps, int activation, float slope, int geometry, skd_stream_t stream) {
+  return run3_s2<2, kFp16>(B, H, W, Cin, Cout, x, wpack, out, conv_bias, mean, var, weight, bias, eps, activation, slope, geometry,
+                           stream);
 }
 
 // include/skd_narrow.h: the 64-column form.

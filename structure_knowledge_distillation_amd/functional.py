@@ -255,10 +255,11 @@ def _cached(owner, attr, key, build, hold=None):
 def drop_conv3x3_packs(owner):
     """Forget the weight packs conv3x3_pack_weights (both piece counts, both piece formats) / conv3x3_train_packs / conv3x3_narrow_pack_weights /
     conv3x3_split_train's narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under
-    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train"; the two-plane training pair of include/skd_train2.h too)."""
+    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train"; the two-plane training pair of include/skd_train2.h and the narrow
+    fp16 image of include/skd_infer2h.h too)."""
     slot = owner if isinstance(owner, dict) else vars(owner)
     for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", _TRAIN2_PACK_ATTR, "pack3x3", "pack3x3_2",
-                 "pack3x3_2h", "pack3x3_train") + _NARROW_PACK_ATTRS:
+                 "pack3x3_2h", "pack3x3_train", _NARROW2H_PACK_ATTR) + _NARROW_PACK_ATTRS:
         slot.pop(attr, None)
 
 
@@ -1095,17 +1096,37 @@ _SPLIT2H_ENTRY, _PACK2H_ATTR = _SPLIT2H_ENTRIES[_SPLIT2_ENTRY], "_skd_conv3x3_pa
 _NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
 _NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
 _NARROW_PACK_ATTRS = ("_skd_conv3x3_narrow_pack", "_skd_conv3x3_train_pack_wide", "_skd_conv3x3_train_pack_narrow")
+# include/skd_infer2h.h: the residual-epilogue, 64-column and stride-2 forms on two fp16 pieces, the narrow form's pack entries
+# and its cache slot (its own, beside the three-piece one: neither image is ever served for the other)
+_RES2H_ENTRY, _NARROW2H_ENTRY, _S2H_ENTRY = "skd_conv3x3_split2h_res_nhwc", "skd_conv3x3_narrow2h_nhwc", "skd_conv3x3_split2h_s2_nhwc"
+_NARROW2H_PACK, _NARROW2H_BYTES = "skd_conv3x3_narrow2h_pack_weights", "skd_conv3x3_narrow2h_pack_bytes"
+_NARROW2H_PACK_ATTR = "_skd_conv3x3_narrow_pack2h"
+_INFER2H_ENTRIES = (_RES2H_ENTRY, _NARROW2H_BYTES, _NARROW2H_PACK, _NARROW2H_ENTRY, _S2H_ENTRY)
+# the size query of the weight image each convolution entry reads (skd_conv3x3_split_pack_bytes for the entries not named)
+_PACK_BYTES_OF = {_NARROW_ENTRY: "skd_conv3x3_narrow_pack_bytes", _NARROW2H_ENTRY: _NARROW2H_BYTES, _SPLIT2_ENTRY: _PACK2_BYTES,
+                  _SPLIT2H_ENTRY: _SPLIT2H_ENTRIES[_PACK2_BYTES], _RES2H_ENTRY: _SPLIT2H_ENTRIES[_PACK2_BYTES]}
+
+
+def _need_infer2h_entry(*names):
+    for name in names:
+        if not _lib.has_entry(name):
+            header = "skd_infer2h.h" if name in _lib.ABI["skd_infer2h.h"] else "skd_split2h.h"
+            raise NotImplementedError("the active back-end does not provide %s (include/%s)" % (name, header))
+
+
+def infer2h_supported():
+    """True when the back-end has the five entries of include/skd_infer2h.h and the three of skd_split2h.h they build on (the
+    tests' C double has none of them)."""
+    return all(_lib.has_entry(n) for n in _INFER2H_ENTRIES + tuple(_SPLIT2H_ENTRIES[k] for k in (_PACK2_BYTES, _PACK2_ENTRY, _SPLIT2_ENTRY)))
 
 
 def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0, residual=None):
     """The one launcher of the split-core 3x3 forms: act(bn_running(conv3x3(x) + conv_bias) [+ residual]) by ``entry`` --
-    skd_conv3x3_split_nhwc, its two-piece twin skd_conv3x3_split2_nhwc, or skd_conv3x3_split_res_nhwc / skd_conv3x3_narrow_nhwc, which take the ``residual`` pointer (None
-    included)."""
+    skd_conv3x3_split_nhwc, its two-piece twins skd_conv3x3_split2_nhwc / skd_conv3x3_split2h_nhwc, or skd_conv3x3_split_res_nhwc /
+    skd_conv3x3_narrow_nhwc and their fp16 twins of include/skd_infer2h.h, which take the ``residual`` pointer (None included)."""
     lib = _lib.get()
     b, cin, h, w = x.shape
-    pack_bytes = (lib.skd_conv3x3_narrow_pack_bytes if entry == _NARROW_ENTRY
-                  else getattr(lib, _PACK2_BYTES) if entry == _SPLIT2_ENTRY
-                  else getattr(lib, _SPLIT2H_ENTRIES[_PACK2_BYTES]) if entry == _SPLIT2H_ENTRY else lib.skd_conv3x3_split_pack_bytes)
+    pack_bytes = getattr(lib, _PACK_BYTES_OF.get(entry, "skd_conv3x3_split_pack_bytes"))
     if pack.numel() != pack_bytes(cin, cout):
         raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
     mean = var = gamma = beta = None
@@ -1115,7 +1136,7 @@ def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, act
     _lib.require_device(x, pack, residual, conv_bias, mean, var, gamma, beta)
     # not a view (_new_cl's is one, with the same strides): the in-place ABN behind dsn[0] writes into a custom Function's output
     out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    res = (_lib.ptr(residual),) if entry in (_RES_ENTRY, _NARROW_ENTRY) else ()
+    res = (_lib.ptr(residual),) if entry in (_RES_ENTRY, _NARROW_ENTRY, _RES2H_ENTRY, _NARROW2H_ENTRY) else ()
     _lib.check(getattr(lib, entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(), *res,
                                    _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
                                    _ACT[activation], slope, int(geometry), _lib.stream_of(x)), entry)
@@ -1212,6 +1233,20 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
                            _residual_cl(x, cout, residual))
 
 
+def conv3x3_split_res_eval_fp16(x, pack, cout, dilation, residual, bn, activation, conv_bias=None, geometry=0):
+    """``conv3x3_split_res_eval`` on two FP16 pieces per operand with the scaled residual (include/skd_infer2h.h), with
+    ``pack = conv3x3_pack_weights_fp16(...)`` (the cache of conv3x3_split_eval_fp16): the same arguments, the residual added in
+    fp32 behind the normalisation and never split; ``residual=None`` is conv3x3_split_eval_fp16 bit for bit.  The numerics of
+    the convolution are those of include/skd_split2h.h (tests/split2h_ref.py); an input beyond +-65504 gives non-finite outputs.
+    An op of its own, not a keyword: tests/golden/routing_census.json records every public conv3x3_* call with its defaults.
+    Never downgraded: a back-end without the entry raises NotImplementedError."""
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError("conv3x3_split_res_eval_fp16 is inference-only")
+    _need_infer2h_entry(_RES2H_ENTRY, _SPLIT2H_ENTRIES[_PACK2_BYTES])
+    return _conv3x3_launch(_RES2H_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
+                           _residual_cl(x, cout, residual))
+
+
 def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None, pieces=3):
     """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc, or
     -- ``pieces`` = 2, ``pack`` a two-plane image -- of skd_conv3x3_split2_nhwc."""
@@ -1285,6 +1320,31 @@ def conv3x3_narrow_eval(x, pack, cout, dilation, residual=None, conv_bias=None, 
                            _residual_cl(x, cout, residual))
 
 
+def conv3x3_narrow_pack_weights_fp16(conv, weight=None, owner=None):
+    """``conv3x3_narrow_pack_weights`` for ``conv3x3_narrow_eval_fp16``: the two fp16 planes (p0 and the scaled p1) of the weight
+    per column tile of 64 output channels (4 bytes per weight), written by skd_conv3x3_narrow2h_pack_weights
+    (include/skd_infer2h.h) and cached on ``owner`` under the same ``(data_ptr, _version)`` rule in a slot of its own, beside the
+    three-piece one.  A back-end without the entries raises NotImplementedError."""
+    w = conv.weight if weight is None else weight
+    if torch.is_grad_enabled() and w.requires_grad:
+        raise RuntimeError("conv3x3_narrow_pack_weights_fp16 is for frozen (no-grad) convolutions")
+    _need_infer2h_entry(_NARROW2H_PACK, _NARROW2H_BYTES)
+    return _conv3x3_packs(w, conv if owner is None else owner, _NARROW2H_PACK_ATTR, _NARROW2H_PACK,
+                          "conv3x3_narrow_pack_weights_fp16", (True,), _NARROW2H_BYTES)[0]
+
+
+def conv3x3_narrow_eval_fp16(x, pack, cout, dilation, residual=None, conv_bias=None, bn=None, activation="none", geometry=0):
+    """``conv3x3_narrow_eval`` on two FP16 pieces per operand with the scaled residual (include/skd_infer2h.h), with
+    ``pack = conv3x3_narrow_pack_weights_fp16(...)``: the same arguments; at a Cout both forms take it gives the bits of
+    conv3x3_split_eval_fp16 / conv3x3_split_res_eval_fp16.  Never downgraded: a back-end without the entry raises
+    NotImplementedError."""
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError("conv3x3_narrow_eval_fp16 is inference-only")
+    _need_infer2h_entry(_NARROW2H_ENTRY, _NARROW2H_BYTES)
+    return _conv3x3_launch(_NARROW2H_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
+                           _residual_cl(x, cout, residual))
+
+
 # include/skd_stride2.h: the stride-2 frozen forward of the 128-column family (csrc/conv3x3.hip with STRIDE = 2)
 _S2_ENTRY = "skd_conv3x3_split_s2_nhwc"
 _S2_ENTRIES = ("skd_conv3x3_split_s2_supported", _S2_ENTRY)
@@ -1298,26 +1358,33 @@ def conv3x3_s2_supported(x, conv):
     return _conv3x3_module_ok(x, conv, grad=False, entries=_S2_ENTRIES, query="skd_conv3x3_split_s2_supported", host_ok=True)
 
 
-def conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", pieces=3):
+def _conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", pieces=3, piece_format="bf16"):
     """act(bn_running(conv3x3(x, stride 2, padding 1) + conv_bias)) in one launch of csrc/conv3x3.hip's stride-2 form
     (include/skd_stride2.h; inference only; conv3x3_s2_supported says when), returned as a plain channels-last (B, cout, Ho, Wo) allocation, Ho = (H - 1) // 2 + 1.
     ``pack = conv3x3_pack_weights(conv, pieces=pieces)``: the image does not depend on the stride, so it is the cache of the
     stride-1 form under the one rule of _version_key.  Only the row map differs from conv3x3_split_eval: the result is that
     op's output at the even pixels bit for bit (tests/test_conv3x3_stride2_gpu.py), and its numerics are that op's for either
-    piece count.  ``activation``: 'none' or 'relu'.  A back-end without the entry raises; the call is never downgraded."""
+    piece count.  ``activation``: 'none' or 'relu'.  A back-end without the entry raises; the call is never downgraded.
+    ``conv3x3_s2_eval_fp16`` is the form of include/skd_infer2h.h with ``pack = conv3x3_pack_weights_fp16(conv)``: two fp16
+    pieces, scaled residual, conv3x3_split_eval_fp16's output at the even pixels bit for bit."""
     pieces = _check_pieces(pieces)
+    fp16 = _check_piece_format(pieces, piece_format) == "fp16"
+    entry = _S2H_ENTRY if fp16 else _S2_ENTRY
     if activation not in ("none", "relu"):
         raise ValueError("conv3x3_s2_eval: activation must be 'none' or 'relu', not %r" % (activation,))
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_s2_eval is inference-only")
-    if not _lib.has_entry(_S2_ENTRY):
+    if fp16:
+        _need_infer2h_entry(_S2H_ENTRY, _SPLIT2H_ENTRIES[_PACK2_BYTES])
+    elif not _lib.has_entry(_S2_ENTRY):
         raise NotImplementedError("this back-end has no %s (include/skd_stride2.h)" % _S2_ENTRY)
     lib = _lib.get()
     b, cin, h, w = x.shape
-    if pieces == 2:
+    if pieces == 2 and not fp16:
         _need_split2_entry(_PACK2_BYTES)
-    if pack.numel() != (getattr(lib, _PACK2_BYTES) if pieces == 2 else lib.skd_conv3x3_split_pack_bytes)(cin, cout):
-        raise ValueError("%s: the pack is not the %d-piece image of a (%d, %d, 3, 3) weight" % (_S2_ENTRY, pieces, cout, cin))
+    bytes_entry = _SPLIT2H_ENTRIES[_PACK2_BYTES] if fp16 else _PACK2_BYTES if pieces == 2 else "skd_conv3x3_split_pack_bytes"
+    if pack.numel() != getattr(lib, bytes_entry)(cin, cout):
+        raise ValueError("%s: the pack is not the %d-piece image of a (%d, %d, 3, 3) weight" % (entry, pieces, cout, cin))
     mean = var = gamma = beta = None
     eps, slope = 0.0, 0.01
     if bn is not None:
@@ -1325,10 +1392,23 @@ def conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", p
     _lib.require_device(x, pack, conv_bias, mean, var, gamma, beta)
     out = torch.empty((b, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
                       memory_format=torch.channels_last)
-    _lib.check(getattr(lib, _S2_ENTRY)(b, h, w, cin, cout, x.data_ptr(), pack.data_ptr(), out.data_ptr(), _lib.ptr(conv_bias),
-                                       _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, _ACT[activation], slope,
-                                       pieces, 0, _lib.stream_of(x)), _S2_ENTRY)
+    _lib.check(getattr(lib, entry)(b, h, w, cin, cout, x.data_ptr(), pack.data_ptr(), out.data_ptr(), _lib.ptr(conv_bias),
+                                   _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, _ACT[activation], slope,
+                                   *(() if fp16 else (pieces,)), 0, _lib.stream_of(x)), entry)      # the fp16 twin takes no piece count
     return out
+
+
+def conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", pieces=3):
+    return _conv3x3_s2_eval(x, pack, cout, conv_bias, bn, activation, pieces)
+
+
+def conv3x3_s2_eval_fp16(x, pack, cout, conv_bias=None, bn=None, activation="none"):
+    """``conv3x3_s2_eval`` on two FP16 pieces per operand with the scaled residual (include/skd_infer2h.h), with
+    ``pack = conv3x3_pack_weights_fp16(conv)``; never downgraded (a back-end without the entry raises NotImplementedError)."""
+    return _conv3x3_s2_eval(x, pack, cout, conv_bias, bn, activation, 2, "fp16")
+
+
+conv3x3_s2_eval.__doc__ = _conv3x3_s2_eval.__doc__
 
 
 def conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups):

@@ -180,8 +180,18 @@ class NetModel():
             setattr(self, name, _switch(args, name, env) and all(getattr(self, n) for n in needs))
         # args.fused_eval: the student's eval-mode / no-grad forwards (validation between epochs, evaluate_main) take the fused
         # BasicBlock form of pspnet_combine.fuse_for_inference; training forwards are what they were.  Off by default.
+        # args.infer_piece_format (None: SKD_INFER_PIECE_FORMAT, default "bf16"; outside SWITCHES, like teacher_piece_format):
+        # "fp16" = that form on two FP16 pieces with a scaled residual (fuse_for_inference(piece_format="fp16"),
+        # include/skd_infer2h.h) -- three products at the three-piece accuracy.  Effective only together with fused_eval: without it
+        # nothing is routed.
+        self.infer_piece_format = _infer_piece_format(getattr(args, "infer_piece_format", None))
         if getattr(args, "fused_eval", False):
-            fuse_for_inference(student, narrow=self.split_narrow, stride2=self.split_stride2)
+            fuse_for_inference(student, narrow=self.split_narrow, stride2=self.split_stride2,
+                               **(dict(piece_format="fp16") if self.infer_piece_format == "fp16" else {}))
+        elif self.infer_piece_format == "fp16":
+            import warnings
+            warnings.warn("infer_piece_format / SKD_INFER_PIECE_FORMAT = 'fp16' takes effect only together with fused_eval: nothing "
+                          "is routed and the student's forwards are what they were", RuntimeWarning, stacklevel=2)
         # args.student_pieces (None: SKD_STUDENT_PIECES, default "3"; outside SWITCHES, like teacher_pieces): 2 = the student's 13 wide
         # training convolutions on two bf16 pieces per operand and three products (route_training_convs(pieces=2),
         # include/skd_train2.h) -- an ACCURACY trade, effective only together with split_train: without it nothing is routed.
@@ -942,6 +952,17 @@ def _teacher_piece_format(value, pieces):
     return value
 
 
+def _infer_piece_format(value):
+    """``value`` (None: the environment's SKD_INFER_PIECE_FORMAT, default "bf16") as "bf16" or "fp16"; anything else is a
+    ValueError."""
+    if value is None:
+        value = os.environ.get("SKD_INFER_PIECE_FORMAT", "bf16")
+    value = str(value).strip()
+    if value not in ("bf16", "fp16"):
+        raise ValueError("infer_piece_format / SKD_INFER_PIECE_FORMAT must be 'bf16' or 'fp16', not %r" % (value,))
+    return value
+
+
 def _teacher_planes(value):
     """``value`` as a bool; None: whether the environment's SKD_TEACHER_PLANES is "1" (default "0")."""
     return os.environ.get("SKD_TEACHER_PLANES", "0") == "1" if value is None else bool(value)
@@ -962,7 +983,7 @@ def default_args(**overrides):
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
         split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None, teacher_planes=None,
-        teacher_piece_format=None, student_pieces=None)
+        teacher_piece_format=None, student_pieces=None, infer_piece_format=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     for name, env, _ in SWITCHES:      # None: the environment switch
@@ -971,5 +992,6 @@ def default_args(**overrides):
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     a.teacher_piece_format = _teacher_piece_format(a.teacher_piece_format, a.teacher_pieces)      # "fp16": two fp16 pieces (skd_split2h.h)
     a.student_pieces = _student_pieces(a.student_pieces)      # 2: the student's wide training convolutions on two pieces; default 3
+    a.infer_piece_format = _infer_piece_format(a.infer_piece_format)      # "fp16": the fused inference form on two fp16 pieces (skd_infer2h.h)
     a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include/skd_planes.h)
     return a

@@ -176,6 +176,19 @@ STRIDE2_ROUTING_EXCLUDED = frozenset()
 # instead of 4), the reduce GEMM with the planes epilogue 2.5 - 9.7 % longer than its fp32 twin, the pairs 1.9 - 6.2 % longer at
 # spreads of at most 1.2 % -- so all four pairs of the teacher are listed, and the opt-in routes nothing until a form measures ahead.
 PLANES_ROUTING_EXCLUDED = frozenset({(512, 256, 2), (1024, 256, 2), (1024, 512, 4), (2048, 512, 4)})
+# The student's inference form on two FP16 pieces with a scaled residual (fuse_for_inference(piece_format="fp16"); a further opt-in
+# on top of the fused inference form, include/skd_infer2h.h): every convolution the flagged student's frozen
+# forward hands to the split core -- whatever ``min_cin``, ``narrow`` and ``stride2`` route -- takes the fp16 twin of its entry:
+# three products instead of six at 22 significant bits per operand, the three-piece accuracy.  A shape that does not measure ahead
+# of its three-piece twin by more than the larger side's spread is listed here as (form, Cin, Cout, dilation), form = "wide",
+# "wide+res", "narrow", "narrow+res" or "s2" ("+res": the residual epilogue, a BasicBlock's conv2), and keeps THREE bf16 pieces,
+# never two (profiles/r34_infer2h_isolated.md has every shape).
+# Measured on the MI355X at the evaluation sizes (129 x 257 for layer2-4, 257 x 513 for the stem, layer1 and the stride-2 input),
+# batch 1 and 2: all fourteen shapes are ahead of three pieces at both batch sizes -- the wide forms 1.44 - 1.60 x with and without
+# the residual, the 64-column forms 1.36 - 1.47 x (64 -> 64 with the residual, the shape most bound by its activation and residual
+# traffic: 1.36 / 1.40 x), stride 2 1.37 - 1.47 x -- at spreads of at most 6.7 %, so the set is empty.  The whole forward at
+# 1024 x 2048: 6.43 -> 4.66 ms; five scales with flip: 99.9 -> 70.2 ms, sets apart (profiles/r34_student_infer.md).
+INFER2H_ROUTING_EXCLUDED = frozenset()
 _TEACHER_EARLY_ENTRIES = ("skd_conv3x3_split_s2_supported", "skd_conv3x3_split_s2_nhwc", "skd_conv3x3_split_supported",
                           "skd_conv3x3_split_nhwc", "skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_nhwc")
 _SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
@@ -399,12 +412,42 @@ def _planes_link(block, x):
     return form == "wide", form
 
 
-def _split_conv(x, conv, form, bn=None, activation="none", residual=None, owner=None):
+def _infer_fp16(module, form, conv, residual=False):
+    """Whether the frozen forward of ``module`` -- a BasicBlock or the ResNet (its stem) that fuse_for_inference(piece_format="fp16")
+    marked -- runs ``conv`` in the ``form`` _frozen_form gave on two FP16 pieces (include/skd_infer2h.h): the mark is set, the
+    back-end has the entries (``SF.infer2h_supported``, looked up at call time) and (form [+ "+res"], Cin, Cout, dilation) is not
+    in INFER2H_ROUTING_EXCLUDED.  Asked only where a form was given, i.e. in eval mode under no grad (or by _prepack)."""
+    if getattr(module, "_skd_infer_piece_format", "bf16") != "fp16" or not SF.infer2h_supported():
+        return False
+    key = form + ("+res" if residual and form != "s2" else "")
+    return (key, conv.in_channels, conv.out_channels, conv.dilation[0]) not in INFER2H_ROUTING_EXCLUDED
+
+
+def _split_conv_fp16(x, conv, form, bn, activation, residual):
+    """_split_conv's launch on two fp16 pieces: the twin op of each form on the twin pack (include/skd_infer2h.h; "wide" without
+    residual: the existing entry of include/skd_split2h.h)."""
+    if form == "narrow":
+        return SF.conv3x3_narrow_eval_fp16(x, SF.conv3x3_narrow_pack_weights_fp16(conv), conv.out_channels, conv.dilation[0], residual,
+                                           conv.bias, bn, activation)
+    pack = SF.conv3x3_pack_weights_fp16(conv)
+    if form == "s2":
+        return SF.conv3x3_s2_eval_fp16(x, pack, conv.out_channels, conv.bias, bn, activation)
+    if residual is not None:
+        return SF.conv3x3_split_res_eval_fp16(x, pack, conv.out_channels, conv.dilation[0], residual, bn, activation, conv.bias)
+    return SF.conv3x3_split_eval_fp16(x, pack, conv.out_channels, conv.dilation[0], conv.bias, bn, activation)
+
+
+def _split_conv(x, conv, form, bn=None, activation="none", residual=None, owner=None, infer=None):
     """act(bn(conv(x)) [+ residual]) as one launch of csrc/conv3x3.hip on ``conv``'s cached pack, in the ``form`` _frozen_form
     gave: "wide"; "narrow", the 64-column form (the same file, include/skd_narrow.h) on its own pack; "s2", the stride-2 form
     (include/skd_stride2.h) on the wide form's pack.  ``owner``: the calling module of a frozen teacher; where set_teacher_pieces
     marked it, "wide" without residual and "s2" run on two pieces (their own pack); the other two keep three.  Marked for fp16
-    pieces, "wide" without residual runs on them and "s2", which has no fp16 form, on three bf16 pieces (_piece_route)."""
+    pieces, "wide" without residual runs on them and "s2", which has no fp16 form for the teacher, on three bf16 pieces (_piece_route).
+    ``infer``: the calling module of a student's inference form (a BasicBlock, or the ResNet for its stem); where
+    fuse_for_inference(piece_format="fp16") marked it, every form runs on two fp16 pieces (_infer_fp16), a mark of its own that
+    ``owner``'s rules never see."""
+    if infer is not None and _infer_fp16(infer, form, conv, residual is not None):
+        return _split_conv_fp16(x, conv, form, bn, activation, residual)
     pieces, fmt = _piece_route(owner, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0], fp16_form=form != "s2")
     if form == "narrow":
         return SF.conv3x3_narrow_eval(x, SF.conv3x3_narrow_pack_weights(conv), conv.out_channels, conv.dilation[0], residual, conv.bias,
@@ -490,7 +533,7 @@ class BasicBlock(nn.Module):
         """relu(bn1(conv1(x))) and relu(bn2(conv2(.)) + residual) as one launch of csrc/conv3x3.hip each (BN + ReLU, and BN +
         residual + ReLU, in the epilogue) where _frozen_form says so."""
         f1 = _frozen_form(self, x, self.conv1)
-        out = _split_conv(x, self.conv1, f1, self.bn1, "relu") if f1 else self.bn1.forward_relu(self.conv1(x))
+        out = _split_conv(x, self.conv1, f1, self.bn1, "relu", infer=self) if f1 else self.bn1.forward_relu(self.conv1(x))
         f2 = _frozen_form(self, out, self.conv2, True)
         if self.downsample is None:
             residual = x
@@ -502,7 +545,7 @@ class BasicBlock(nn.Module):
         else:
             residual = self.downsample(x)
         if f2:
-            return _split_conv(out, self.conv2, f2, self.bn2, "relu", residual)
+            return _split_conv(out, self.conv2, f2, self.bn2, "relu", residual, infer=self)
         return self.bn2.forward_relu(self.conv2(out), residual)
 
     def forward(self, x):
@@ -733,8 +776,11 @@ class ResNet(nn.Module):
                 # two pieces where set_teacher_pieces marked this network; it marks the modules of Bottleneck networks alone, so
                 # a student's never carry ``_skd_teacher_pieces`` and its conv3 keeps three
                 f2 = _frozen_form(self, x, self.conv2)
-                x = _split_conv(x, self.conv2, f2, self.bn2, "relu") if f2 == "narrow" else self.bn2.forward_relu(self.conv2(x))
-                c3 = _split_conv(x, self.conv3, "wide", owner=self) if _frozen_form(self, x, self.conv3) == "wide" else self.conv3(x)
+                # ``infer=self``: both on two fp16 pieces where fuse_for_inference(piece_format="fp16") marked this network
+                x = (_split_conv(x, self.conv2, f2, self.bn2, "relu", infer=self) if f2 == "narrow"
+                     else self.bn2.forward_relu(self.conv2(x)))
+                c3 = (_split_conv(x, self.conv3, "wide", owner=self, infer=self) if _frozen_form(self, x, self.conv3) == "wide"
+                      else self.conv3(x))
             else:
                 x = self.bn2.forward_relu(self.conv2(x))
                 c3 = self.conv3(x)
@@ -796,7 +842,9 @@ def _prepack(module, convs):
             if not (w.is_cuda or _lib.test_backend_active()) or w.dtype != torch.float32:
                 continue
             form = _frozen_form(module, w.new_empty((1, 1, 1, conv.in_channels)).permute(0, 3, 1, 2), conv, residual, packing=True)
-            if form == "narrow":
+            if form and _infer_fp16(module, form, conv, residual):      # fuse_for_inference(piece_format="fp16"): the twin pack alone
+                (SF.conv3x3_narrow_pack_weights_fp16 if form == "narrow" else SF.conv3x3_pack_weights_fp16)(conv)
+            elif form == "narrow":
                 SF.conv3x3_narrow_pack_weights(conv)
             elif form:
                 pieces, fmt = _piece_route(module, "3x3", conv.in_channels, conv.out_channels, conv.dilation[0], fp16_form=form != "s2")
@@ -804,7 +852,7 @@ def _prepack(module, convs):
                 pack(conv, **kw)
 
 
-def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False, stride2=False):
+def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=False, stride2=False, piece_format="bf16"):
     """Flag every BasicBlock of ``model`` (the student) for the fused inference form and return ``model``.
 
     A flagged block in eval mode, with grad disabled, on an fp32 channels-last input runs ``conv1 -> bn1 -> relu`` and
@@ -824,14 +872,34 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
     student layer2.0 (64 -> 128) -- runs ``conv1 -> bn1 -> relu`` as one launch of the stride-2 form of the kernel
     (include/skd_stride2.h) on the wide form's pack -- except the shapes of STRIDE2_ROUTING_EXCLUDED; the default leaves every
     existing call as it is.
+    ``piece_format="fp16"`` (a further opt-in, NOT an accuracy trade: include/skd_infer2h.h): every convolution
+    the flags above hand to the split core runs on two FP16 pieces with the residual scaled by 2^11 -- three products instead of
+    six at the three-piece accuracy -- through the twin op of its form: the wide form with and without the residual, the
+    64-column form (the stem's ``conv2`` too), the stem's ``conv3`` and, with ``stride2``, the stride-2 ``conv1`` -- except the
+    shapes of INFER2H_ROUTING_EXCLUDED, which keep THREE bf16 pieces.  "fp16" means two fp16 pieces, the only fp16 form there
+    is; anything but "bf16" and "fp16" is a ValueError.  The mark (``_skd_infer_piece_format``, on the BasicBlocks and on the
+    ResNet for its stem) is this function's own: set_teacher_pieces and what it routes never see it.  An activation beyond
+    +-65504 gives non-finite outputs (the header's range contract).  On a back-end without the entries it warns once
+    (RuntimeWarning, naming skd_infer2h.h) and the student stays on three pieces.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
     is set and changes nothing."""
+    if piece_format not in ("bf16", "fp16"):
+        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
+    if enable and piece_format == "fp16" and not SF.infer2h_supported():
+        import warnings
+        warnings.warn("fuse_for_inference: this back-end lacks the fp16 two-piece entries (include/skd_infer2h.h); the student "
+                      "stays on three pieces", RuntimeWarning, stacklevel=2)
+        piece_format = "bf16"
     for m in model.modules():
         if not isinstance(m, (BasicBlock, ResNet)):
             continue
         stem = isinstance(m, ResNet)
         convs = ((m.conv2, False), (m.conv3, False)) if stem else ((m.conv1, False), (m.conv2, True))
         m._skd_infer_narrow = bool(narrow and enable)
+        if enable and piece_format == "fp16":
+            m._skd_infer_piece_format = "fp16"
+        else:
+            vars(m).pop("_skd_infer_piece_format", None)
         if not stem:
             m._skd_infer_stride2 = bool(stride2 and enable)
         if not enable:
@@ -920,9 +988,10 @@ def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
     ``pieces=2, piece_format="fp16"`` -- opt-in, NOT an accuracy trade: the same modules are marked and the same call sites take the
     entries of include/skd_split2h.h instead -- two FP16 pieces with the residual scaled by 2^11, the same three products: 22
     significant bits per operand, the three-piece accuracy -- except the shapes of SPLIT2H_ROUTING_EXCLUDED.  The
-    stride-2 form (like the 64-column, residual-epilogue and piece-plane forms) has no fp16 twin: under this mark it runs on THREE
-    bf16 pieces, never on two.  An activation beyond +-65504 gives NaN outputs (the header's range contract).  ``piece_format``
-    without ``pieces=2`` is a ValueError, not a silent three-piece run.
+    stride-2 and 64-column forms are not routed to fp16 pieces for the teacher (their fp16 twins, include/skd_infer2h.h, serve the
+    student's inference form alone; the piece-plane form has none): under this mark they run on THREE bf16 pieces, never on two.
+    An activation beyond +-65504 gives NaN outputs (the header's range contract).  ``piece_format`` without ``pieces=2`` is a
+    ValueError, not a silent three-piece run.
     ``pieces=3`` clears the marks and drops the two-plane packs of both formats.  On a back-end without the entries ``pieces=2``
     warns (RuntimeWarning) and leaves three pieces."""
     if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
