@@ -4,7 +4,8 @@
  * gradient are skd_conv3x3_split2_nhwc (skd_split2.h) in both directions, without batch norm and with SKD_ACT_NONE; the conv
  * bias goes in the epilogue.  A reduced-precision mode for training (networks.pspnet_combine.route_training_convs's ``pieces``),
  * opt-in and off by default: fp32 in, fp32 out, fp32 accumulation, 16 significant bits per operand.  bf16 pieces only -- they keep
- * fp32's exponent, so small gradients need no scaling; there is no fp16 form.  Like the entries of skd_train.h and skd_wgrad.h
+ * fp32's exponent, so small gradients need no scaling; the fp16 form, which finds a power-of-two scale per gradient tensor on the
+ * device and keeps 22 bits, is skd_train2h.h.  Like the entries of skd_train.h and skd_wgrad.h
  * they are outside the frozen core ABI (skd.h): the plain-C oracle implements the core ABI only, so a back-end may lack them (the
  * student then stays on three pieces).  Same conventions as skd.h: int return, 1 = success, 0 = refused with nothing launched;
  * raw DEVICE pointers; NULL = optional tensor absent; outputs pre-sized by the caller; asynchronous on `stream`.

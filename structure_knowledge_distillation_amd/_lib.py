@@ -299,6 +299,19 @@ ABI["skd_infer2h.h"] = {
     "skd_conv3x3_split2h_s2_nhwc": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _I, _P]),
 }
 
+# include/skd_train2h.h (csrc/scale_word.hip, csrc/conv3x3.hip's SCALED form, csrc/conv3x3_wgrad.hip with FMT = kFp16): the training
+# student's wide 3x3 convolutions on two FP16 pieces per operand with a power-of-two scale per gradient tensor, found on the
+# device -- twins of skd_train2.h / skd_split2h.h plus the scale word.  A back-end without them leaves the student on three bf16
+# pieces (route_training_convs(piece_format="fp16") warns once; the fp16 training ops themselves raise NotImplementedError).
+ABI["skd_train2h.h"] = {
+    "skd_fp16_scale_word_workspace_bytes": (_L, [_L]),
+    "skd_fp16_scale_word": (_I, [_L, _P, _P, _L, _P, _P]),
+    "skd_conv3x3_split2h_pack_pair": (_I, [_I, _I, _P, _L, _L, _L, _L, _P, _L, _P, _L, _P]),
+    "skd_conv3x3_split2h_scaled_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "skd_conv3x3_split2h_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "skd_conv3x3_split2h_wgrad_nhwc": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _L, _L, _L, _P, _L, _P, _I, _P]),
+}
+
 SIGNATURES = ABI["skd.h"]    # the core ABI: what the plain-C double of oracle/ is typed from
 
 _lib = None

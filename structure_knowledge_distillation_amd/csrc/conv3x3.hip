@@ -50,6 +50,7 @@
 #include "skd_stride2.h"
 #include "skd_train.h"
 #include "skd_train2.h"
+#include "skd_train2h.h"
 
 namespace skd {
 namespace {
@@ -146,8 +147,9 @@ __device__ __forceinline__ void stage_load3_a(Staging3<TM, TN, PIECES, true> &s,
   }
 }
 
-template <int TM, int TN, int PIECES, bool PLANES, int FMT = kBf16>
-__device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLANES> &s, uint4 *stage, int srow) {
+// SCALED (include/skd_train2h.h): the fp32 quad is multiplied by `scale`, a power of two, in front of the split.
+template <int TM, int TN, int PIECES, bool PLANES, int FMT = kBf16, bool SCALED = false>
+__device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLANES> &s, uint4 *stage, int srow, float scale = 1.f) {
   uint2 *sa = reinterpret_cast<uint2 *>(stage) + srow;
 #pragma unroll
   for (int h = 0; h < TM / kRPP; ++h) {
@@ -156,6 +158,8 @@ __device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLAN
       dst[0] = s.a0[h];
       dst[2 * kPlaneChunks] = s.a1[h];
       dst[4 * kPlaneChunks] = s.a2[h];
+    } else if constexpr (SCALED) {
+      split_store<PIECES, FMT>(scaled(s.a[h], scale), sa + 2 * kRPP * h);
     } else {
       split_store<PIECES, FMT>(s.a[h], sa + 2 * kRPP * h);
     }
@@ -172,7 +176,7 @@ __device__ __forceinline__ void stage_store3(const Staging3<TM, TN, PIECES, PLAN
 // What k_loop (conv_split_dev.hpp) needs of a tile of this kernel.  k_loop calls load for kt = 0, 1, 2, ... in order, so the
 // cursor is simply stepped behind every one: it runs as far ahead of the MFMAs as the loads do and crosses a tap boundary
 // wherever that falls.  (Behind the last tile it stands at tap 9, which nothing reads.)
-template <int TM, int TN, int PIECES = 3, bool PLANES = false, int FMT = kBf16>
+template <int TM, int TN, int PIECES = 3, bool PLANES = false, int FMT = kBf16, bool SCALED = false>
 struct Tile3 {
   typedef Staging3<TM, TN, PIECES, PLANES> Stg;
   static constexpr int WM = wave_blocks_m(TM, TN);
@@ -182,6 +186,7 @@ struct Tile3 {
   TapCursor cur;
   int64_t abase[TM / kRPP];
   unsigned mask[TM / kRPP];
+  float scale;                        // SCALED: the power of two of the activation operand (scale_of); otherwise unused
   f32x16 (&low)[WM][2], (&acc)[WM][2];
   __device__ __forceinline__ void load(Stg &s, int kt) {
     stage_load3_a<TM, TN, PIECES>(s, X, cur, abase, mask, Cin);
@@ -193,7 +198,7 @@ struct Tile3 {
       cur.shift = tap_shift(cur.tap, W, dil, Cin);
     }
   }
-  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES, PLANES, FMT>(s, stage, srow); }
+  __device__ __forceinline__ void store(const Stg &s, uint4 *stage, int) const { stage_store3<TM, TN, PIECES, PLANES, FMT, SCALED>(s, stage, srow, scale); }
   __device__ __forceinline__ void mma(const uint4 *stage) const { tile_mma<TM, TN, false, PIECES, FMT>(stage, low, acc); }
 };
 
@@ -254,8 +259,11 @@ __device__ __forceinline__ void block_stats(const f32x16 &acc, float *__restrict
 // (B, Ho, Wo) output, H and W stay the input's, and the rows' addresses and masks come from s2_row_map; STRIDE = 1 is the code
 // without it.  PLANES (include/skd_planes.h): X is the piece planes of the (M, Cin) input map; the rows' addresses are byte
 // offsets of that layout and the staging set holds piece quads (stage_load3_a, stage_store3); masks, tap cursor, K loop, product order
-// and epilogue are the code without it.
-template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
+// and epilogue are the code without it.  SCALED (include/skd_train2h.h; the data gradient on two fp16 pieces): the workgroup reads
+// the scale word of X once, the staging multiplies X's quads by s in front of the split and the epilogue multiplies the joined
+// sets by 1 / s in front of everything else; SCALED = false is the code without it.
+template <int TM, int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16,
+          bool SCALED = false>
 __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const uint4 *__restrict__ Bp, float *__restrict__ Y,
                                              const float *__restrict__ R, float *__restrict__ stats,
                                              const float *__restrict__ cbias, const float *__restrict__ mean,
@@ -263,6 +271,8 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
                                              const float *__restrict__ bias, float eps, float slope, int64_t M, int H, int W,
                                              int Cin, int N, int dil, int64_t m0, int tn, uint4 *lds) {
   constexpr int WM = wave_blocks_m(TM, TN), kRA = TM / kRPP;
+  float scale = 1.f, unscale = 1.f;
+  if constexpr (SCALED) scale_of(__float_as_uint(*R), scale, unscale);      // R: the scale word's address (the kernel's note)
   f32x16 acc[WM][2], low[WM][2];      // a0 b0 | the five (PIECES = 2: two) smaller products (tile_mma): added in the epilogue
 #pragma unroll
   for (int i = 0; i < WM; ++i)
@@ -302,7 +312,7 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
     abase[h] = PLANES ? planes_offset(M, Cin, mm, gkq, 0) : mm * Cin + gkq;
   }
   const uint4 *bsrc = Bp + (int64_t)tn * nk * tile_chunks(TN, PIECES) + gt;
-  Tile3<TM, TN, PIECES, PLANES, FMT> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, low, acc};
+  Tile3<TM, TN, PIECES, PLANES, FMT, SCALED> tile = {X, bsrc, srow, W, dil, Cin, {0, 0, tap_shift(0, W, dil, Cin)}, {}, {}, scale, low, acc};
 #pragma unroll
   for (int h = 0; h < kRA; ++h) {
     tile.abase[h] = abase[h];
@@ -324,6 +334,10 @@ __device__ __forceinline__ void conv3x3_tile(const float *__restrict__ X, const 
 #pragma unroll
     for (int bi = 0; bi < WM; ++bi) {
       join_sets<FMT>(acc[bi][bj], low[bi][bj]);
+      if constexpr (SCALED) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[bi][bj][q] *= unscale;
+      }
       if (cbias != nullptr) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[bi][bj][q] += cb;
@@ -354,7 +368,11 @@ constexpr int conv3x3_wgs(int TN, bool TALL) { return TALL && TN == kTN ? 2 : kM
 // (include/skd_infer2h.h: the student's inference form); two bf16 pieces have the wide forms without residual alone.  The 64-column
 // two-piece form takes 28 KB of LDS: a stage is 512 chunks of A and 256 of B -- one copy per thread -- the second stage
 // stage_chunks(2) = 1024 chunks behind the first.
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
+// SCALED (include/skd_train2h.h): the raw 128-column stride-1 fp16 form alone, both tile heights.  It has no residual, and the scale
+// word of X (one 32-bit word on the device) arrives in the residual pointer's place, so the kernel's argument list is one for every
+// instantiation and the old ones are what they were.
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16,
+          bool SCALED = false>
 __global__ __launch_bounds__(kThreads, conv3x3_wgs(TN, TALL))
 __attribute__((amdgpu_waves_per_eu(conv3x3_wgs(TN, TALL), conv3x3_wgs(TN, TALL))))
 void conv3x3_split_kernel(
@@ -368,6 +386,8 @@ void conv3x3_split_kernel(
   static_assert(STRIDE == 1 || (STRIDE == 2 && TN == kTN && !HAS_RES && !STATS), "stride 2: the 128-column frozen forward alone");
   static_assert(!PLANES || (TN == kTN && PIECES == 3 && !HAS_RES && !STATS && STRIDE == 1), "piece planes in: the wide stride-1 frozen forward alone");
   static_assert(FMT == kBf16 || (PIECES == 2 && !STATS && !PLANES), "fp16 pieces: two of them, the frozen forward families alone (include/skd_infer2h.h)");
+  static_assert(!SCALED || (FMT == kFp16 && PIECES == 2 && TN == kTN && ACT == SKD_ACT_NONE && !HAS_RES && !STATS && STRIDE == 1 && !PLANES),
+                "a scaled operand: the raw wide stride-1 form on two fp16 pieces alone (include/skd_train2h.h)");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int pl = j / tiles_n, tn = j - pl * tiles_n;
@@ -375,11 +395,11 @@ void conv3x3_split_kernel(
   if (TALL && (TN < kTN || tm < p_full)) {
     const int64_t m0 = tm * kTM;
     if (m0 >= M) return;
-    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT, SCALED>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   } else if constexpr (TN == kTN) {
     const int64_t m0 = (int64_t)p_full * kTM + (tm - p_full) * (kTM / 2);
     if (m0 >= M) return;
-    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
+    conv3x3_tile<kTM / 2, TN, ACT, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT, SCALED>(X, Bp, Y, R, stats, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, m0, tn, lds);
   }
 }
 
@@ -428,15 +448,16 @@ __global__ __launch_bounds__(2 * TN) void conv3x3_pack_pair_kernel(
   for (int p = 0; p < PIECES; ++p) pack[(tile * PIECES + p) * (2 * TN) + chunk] = make_uint4(lo[p].x, lo[p].y, hi[p].x, hi[p].y);
 }
 
-template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
+template <int TN, int ACT, bool TALL, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16,
+          bool SCALED = false>
 static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                    const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
-                   int geometry, hipStream_t st, float *stats = nullptr) {
+                   int geometry, hipStream_t st, float *stats = nullptr, const uint32_t *word = nullptr) {
   static PerDeviceFlag ready;          // per instantiation AND per device
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT, SCALED>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv3x3_lds(TN, PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
@@ -452,8 +473,9 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
   const int64_t panels = p_full < tiles_m ? p_full + cdiv(M - p_full * kTM, kTM / 2) : tiles_m;
   const int64_t grid = cdiv(panels, 8) * 8 * tiles_n;
   if (grid > 2147483647) return 0;
-  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
-      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full, R, stats);
+  conv3x3_split_kernel<TN, ACT, TALL, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT, SCALED><<<dim3((unsigned)grid), dim3(kThreads), conv3x3_lds(TN, PIECES), st>>>(
+      X, Bp, Y, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, tiles_n, (int)p_full,
+      SCALED ? reinterpret_cast<const float *>(word) : R, stats);
   return ok();
 }
 
@@ -463,18 +485,19 @@ static int launch3(const float *X, const uint4 *Bp, float *Y, const float *R, co
 // ahead of the 64-row tiles and 10-19 % ahead of 1 (all tiles 128 rows: its partial last round leaves CUs idle); below one full
 // round the 64-row tiles win (128 -> 128 at 65 x 65: 85 against 95 us).  1 is kept for measurements only.
 // TN = 64 has the one geometry, 1 (skd_narrow.h: 0 and 1 are accepted and mean it).
-template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16>
+template <int TN, int ACT, bool HAS_RES, int PIECES = 3, bool STATS = false, int STRIDE = 1, bool PLANES = false, int FMT = kBf16,
+          bool SCALED = false>
 static int launch3g(const float *X, const uint4 *Bp, float *Y, const float *R, const float *cbias, const float *mean, const float *var,
                     const float *weight, const float *bias, float eps, float slope, int64_t M, int H, int W, int Cin, int N, int dil,
-                    int geometry, hipStream_t st, float *stats = nullptr) {
+                    int geometry, hipStream_t st, float *stats = nullptr, const uint32_t *word = nullptr) {
   if constexpr (TN < kTN) {
-    static_assert(STRIDE == 1 && !PLANES, "the 64-column form: stride 1 on an fp32 map");
+    static_assert(STRIDE == 1 && !PLANES && !SCALED, "the 64-column form: stride 1 on an unscaled fp32 map");
     return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, 1, false, FMT>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, 1, st, stats);
   } else {
     if (geometry == 0) geometry = cdiv(M, kTM) * (N / kTN) > 2 * (int64_t)cu_count(st) ? 3 : 2;
     if (geometry == 1 || geometry == 3)
-      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
-    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats);
+      return launch3<TN, ACT, true, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT, SCALED>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats, word);
+    return launch3<TN, ACT, false, HAS_RES, PIECES, STATS, STRIDE, PLANES, FMT, SCALED>(X, Bp, Y, R, cbias, mean, var, weight, bias, eps, slope, M, H, W, Cin, N, dil, geometry, st, stats, word);
   }
 }
 
@@ -540,12 +563,12 @@ static int run3(int B, int H, int W, int Cin, int Cout, int dilation, const floa
     if constexpr (PIECES == 3)                                                                                                \
       return (residual != nullptr ? launch3g<TN, ACT, true> : launch3g<TN, ACT, false>)(                                     \
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st,    \
-          nullptr);                                                                                                           \
+          nullptr, nullptr);                                                                                                  \
     else if constexpr (FMT == kFp16) /* include/skd_infer2h.h: the fp16 form has the residual epilogue */                     \
       return (residual != nullptr ? launch3g<TN, ACT, true, PIECES, false, 1, false, FMT>                                     \
                                   : launch3g<TN, ACT, false, PIECES, false, 1, false, FMT>)(                                  \
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st,    \
-          nullptr);                                                                                                           \
+          nullptr, nullptr);                                                                                                  \
     else                                                                                                                      \
       return residual != nullptr ? 0 : launch3g<TN, ACT, false, PIECES, false, 1, false, FMT>(                                \
           x, bp, out, residual, conv_bias, mean, var, weight, bias, eps, slope, M, H, W, Cin, Cout, dilation, geometry, st)
@@ -582,6 +605,20 @@ static int run3_planes(int B, int H, int W, int Cin, int Cout, int dilation, con
     default: return 0;
   }
 #undef SKD_CONV3X3_PLANES_CASE
+}
+
+// include/skd_train2h.h: the raw convolution on two fp16 pieces whose activation operand is scaled by its word -- run3's refusals
+// (no residual, no epilogue terms), and a NULL or misaligned word.
+static int run3_scaled(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack, float *out,
+                       const uint32_t *word, int geometry, skd_stream_t stream) {
+  if (!supported3<kTN>(Cin, Cout, 1, dilation, dilation, 1) || B < 1 || H < 1 || W < 1) return 0;
+  if (!x || !wpack || !out || !word || geometry < 0 || geometry > 3) return 0;
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wpack)) & 15) || (reinterpret_cast<uintptr_t>(word) & 3)) return 0;
+  if ((int64_t)H * W > 2147483647 || dilation > (1 << 24)) return 0;
+  const int64_t M = (int64_t)B * H * W;
+  return launch3g<kTN, SKD_ACT_NONE, false, 2, false, 1, false, kFp16, true>(x, static_cast<const uint4 *>(wpack), out, nullptr, nullptr,
+                                                                             nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, M, H, W, Cin,
+                                                                             Cout, dilation, geometry, as_stream(stream), nullptr, word);
 }
 
 // include/skd_bnstats.h: floats of the statistics workspace of an (M, Cout) output -- one (mean, M2) per 32-row block and
@@ -755,6 +792,18 @@ int skd_conv3x3_split2h_s2_nhwc(int B, int H, int W, int Cin, int Cout, const fl
                                 float eps, int activation, float slope, int geometry, skd_stream_t stream) {
   return run3_s2<2, kFp16>(B, H, W, Cin, Cout, x, wpack, out, conv_bias, mean, var, weight, bias, eps, activation, slope, geometry,
                            stream);
+}
+
+// include/skd_train2h.h: both fp16 two-plane images of a trained weight in one launch, and the data gradient on a scaled g.
+int skd_conv3x3_split2h_pack_pair(int Cin, int Cout, const float *w, int64_t stride_n, int64_t stride_c, int64_t stride_y,
+                                  int64_t stride_x, void *pack_fwd, int64_t fwd_bytes, void *pack_bwd, int64_t bwd_bytes,
+                                  skd_stream_t stream) {
+  return pack_pair3<kTN, 2, kFp16>(Cin, Cout, w, stride_n, stride_c, stride_y, stride_x, pack_fwd, fwd_bytes, pack_bwd, bwd_bytes, stream);
+}
+
+int skd_conv3x3_split2h_scaled_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const void *wpack,
+                                    float *out, const uint32_t *word, int geometry, skd_stream_t stream) {
+  return run3_scaled(B, H, W, Cin, Cout, dilation, x, wpack, out, word, geometry, stream);
 }
 
 // include/skd_narrow.h: the 64-column form.

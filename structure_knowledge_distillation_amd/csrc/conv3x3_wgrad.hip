@@ -68,6 +68,7 @@
 #include "skd_narrow_wgrad.h"
 #include "skd_shortcut.h"
 #include "skd_train2.h"
+#include "skd_train2h.h"
 #include "skd_wgrad.h"
 
 #ifndef SKD_WGRAD_GRID_ORDER
@@ -99,7 +100,7 @@ struct StagingW {
   float4 v[4];                                         // pixels 4 q .. 4 q + 3, channels 4 r .. 4 r + 3
 };
 
-template <bool NARROW, int TAPS = 9, int PIECES = 3>
+template <bool NARROW, int TAPS = 9, int PIECES = 3, int FMT = kBf16>
 struct TileW {
   typedef StagingW Stg;
   static constexpr int WM = NARROW ? 1 : 2;
@@ -115,6 +116,7 @@ struct TileW {
   int s;                              // channel permutation of this lane
   int slot[4];                        // 8-byte LDS slot of the j-th stored row, the operand's offset included
   int in_hw, in_row, in_step;         // TAPS == 1: pixels of an image of x, and the pixel steps of one output row and column
+  float scale;                        // FMT == kFp16: g's rows times s (scale_of), x's rows times 1; otherwise unused
   f32x16 (&low)[WM][2], (&acc)[WM][2];
 
   __device__ __forceinline__ void load(Stg &st, int kt) const {
@@ -185,12 +187,13 @@ struct TileW {
       const float4 row = make_float4(p[0][j], p[1][j], p[2][j], p[3][j]);
       // NARROW: g's 64-row image has its pieces 2 * 128 slots apart; a wave-uniform branch keeps both distances immediates
       if (NARROW && !is_x) split_store(row, base + slot[j], 2 * 2 * kUnit);
+      else if constexpr (FMT == kFp16) split_store<PIECES, FMT>(scaled(row, scale), base + slot[j]);
       else split_store<PIECES>(row, base + slot[j]);
     }
   }
   __device__ __forceinline__ void mma(const uint4 *stage) const {
     if constexpr (NARROW) tile_mma<kTM, kUnit, true>(stage, low, acc);
-    else tile_mma<kTM, kTN, false, PIECES>(stage, low, acc);
+    else tile_mma<kTM, kTN, false, PIECES, FMT>(stage, low, acc);
   }
 };
 
@@ -202,13 +205,18 @@ struct TileW {
 // are kept per K-tile -- a0 b1 and a1 b0 into `low`, a0 b0 into `acc`, the two-set rule as it is.  The LDS ring shrinks to
 // conv_lds(2) = 32 KB; the 128 accumulator registers stay, so the two workgroups per CU stay too (three would leave 168
 // registers a lane for 128 accumulators, two staging sets and the fragments: profiles/r33_kernel_resources.md).
-template <bool NARROW, int TAPS = 9, int PIECES = 3>
+// FMT = kFp16 (skd_train2h.h; that PIECES = 2 form alone): two fp16 pieces with the scaled residual.  g's rows are multiplied by
+// s = scale_of(*word) in front of the split (word == nullptr: s = 1), x's rows are not; the slice's block is
+// fma(low, 2^-11, acc) (1 / s).  LDS ring, accumulators, staging sets and the two workgroups per CU are the bf16 twin's
+// (profiles/r35_kernel_resources.md).
+template <bool NARROW, int TAPS = 9, int PIECES = 3, int FMT = kBf16>
 __global__ __launch_bounds__(kThreads, Form<NARROW>::per_cu)
 __attribute__((amdgpu_waves_per_eu(Form<NARROW>::per_cu, Form<NARROW>::per_cu)))
 void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__ G, float *__restrict__ part, int P, int H, int W,
                           int Cin, int Cout, int dil, int nk, int tiles_per_slice, int slices, unsigned rcp_hw, unsigned rcp_w,
-                          int total, int Hin, int Win) {
+                          int total, int Hin, int Win, const uint32_t *__restrict__ word) {
   static_assert(TAPS == 9 || TAPS == 1, "the 3x3 convolution, or its centre tap alone");
+  static_assert(FMT == kBf16 || (FMT == kFp16 && PIECES == 2), "fp16 pieces: the two-piece form alone");
   static_assert(PIECES == 3 || (PIECES == 2 && !NARROW && TAPS == 9), "two pieces: the wide nine-tap form alone");
   extern __shared__ __attribute__((aligned(16))) uint4 lds[];
   constexpr int WM = NARROW ? 1 : 2;
@@ -247,7 +255,7 @@ void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__
                         is_x ? ((int64_t)(ty - 1) * W + (tx - 1)) * dil : 0,
                         is_x ? Cin : Cout, has_rows ? P : 0, H, W, H * W, rcp_hw, rcp_w,
                         is_x ? (ty - 1) * dil : 0, is_x ? (tx - 1) * dil : 0,
-                        kt0 * kBK + 4 * q, is_x, stages, s, {}, Hin * Win, dil * Win, dil, low, acc};
+                        kt0 * kBK + 4 * q, is_x, stages, s, {}, Hin * Win, dil * Win, dil, 1.f, low, acc};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int row = 4 * r + (j ^ s), kh = q >> 1;
@@ -287,11 +295,15 @@ void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__
     const int s = (r >> 1) & 3;
     const int C = is_x ? Cin : Cout;
     const float *src = (is_x ? X + tc * kTN : G + tn * kTM) + 4 * r;
-    TileW<false, TAPS, PIECES> tile = {src,
+    float scale = 1.f, unscale = 1.f;
+    if constexpr (FMT == kFp16) {
+      if (word != nullptr) scale_of(*word, scale, unscale);
+    }
+    TileW<false, TAPS, PIECES, FMT> tile = {src,
                          is_x ? ((int64_t)(ty - 1) * W + (tx - 1)) * dil : 0,
                          C, P, H, W, H * W, rcp_hw, rcp_w,
                          is_x ? (ty - 1) * dil : 0, is_x ? (tx - 1) * dil : 0,
-                         kt0 * kBK + 4 * q, is_x, true, s, {}, Hin * Win, dil * Win, dil, low, acc};
+                         kt0 * kBK + 4 * q, is_x, true, s, {}, Hin * Win, dil * Win, dil, is_x ? 1.f : scale, low, acc};
 #pragma unroll
     for (int j = 0; j < 4; ++j) tile.slot[j] = (is_x ? 2 * operand_chunks(PIECES) : 0) + plane_slot(4 * r + (j ^ s), 4 * q);
     k_loop<kWgDepth, PIECES>(tile, nks, lds);
@@ -304,8 +316,14 @@ void conv3x3_wgrad_kernel(const float *__restrict__ X, const float *__restrict__
       const int col = tap * Cin + tc * kTN + wj + bj * 32 + (lane & 31);
 #pragma unroll
       for (int bi = 0; bi < 2; ++bi) {
+        if constexpr (FMT == kFp16) {      // the one join of the fp16 sets (conv_split_dev.hpp), then the scale of g taken out
+          join_sets<kFp16>(acc[bi][bj], low[bi][bj]);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[bi][bj][e] += low[bi][bj][e];
+          for (int e = 0; e < 16; ++e) acc[bi][bj][e] *= unscale;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[bi][bj][e] += low[bi][bj][e];
+        }
         store_block<SKD_ACT_NONE, false, true, false>(acc[bi][bj], nullptr, slab, (int64_t)tn * kTM + wi + bi * 32, col, Cout, TAPS * Cin,
                                                       0.f, 1.f, 1.f, 0.f, 0.f);
       }
@@ -441,10 +459,12 @@ int plan_of(int B, int H, int W, int Cin, int Cout, int slices, int cus, int64_t
 }
 
 // TAPS == 1: `dilation` is 1, x has H x W pixels an image and g (H - 1) / stride + 1 by (W - 1) / stride + 1 (plan_of).
-template <bool NARROW, int TAPS = 9, int PIECES = 3>
+template <bool NARROW, int TAPS = 9, int PIECES = 3, int FMT = kBf16>
 int launch(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const float *g, float *dw, int64_t sn, int64_t sc,
-           int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes, int slices, skd_stream_t stream, int stride = 1) {
+           int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes, int slices, skd_stream_t stream, int stride = 1,
+           const uint32_t *word = nullptr) {
   if (!x || !g || !dw || !workspace || B < 1 || H < 1 || W < 1 || stride < 1) return 0;
+  if (reinterpret_cast<uintptr_t>(word) & 3) return 0;
   if (dilation < 1 || dilation > kMaxDilation || !supported<NARROW>(Cin, Cout, 1, dilation, dilation, 1)) return 0;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(workspace)) & 15) return 0;
   if (sn < 0 || sc < 0 || sy < 0 || sx < 0) return 0;
@@ -466,15 +486,15 @@ int launch(int B, int H, int W, int Cin, int Cout, int dilation, const float *x,
   bool *rdy = ready.get();
   if (rdy == nullptr) return 0;
   if (!*rdy) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel<NARROW, TAPS, PIECES>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_wgrad_kernel<NARROW, TAPS, PIECES, FMT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)conv_lds(PIECES)) != hipSuccess) return 0;
     *rdy = true;
   }
   hipStream_t st = as_stream(stream);
   float *part = static_cast<float *>(workspace);
-  conv3x3_wgrad_kernel<NARROW, TAPS, PIECES><<<dim3((unsigned)grid), dim3(kThreads), conv_lds(PIECES), st>>>(
+  conv3x3_wgrad_kernel<NARROW, TAPS, PIECES, FMT><<<dim3((unsigned)grid), dim3(kThreads), conv_lds(PIECES), st>>>(
       x, g, part, (int)P, Ho, Wo, Cin, Cout, TAPS == 1 ? stride : dilation, (int)nk, (int)per_slice, (int)used,
-      reciprocal32((unsigned)(Ho * Wo)), reciprocal32((unsigned)Wo), (int)total, H, W);
+      reciprocal32((unsigned)(Ho * Wo)), reciprocal32((unsigned)Wo), (int)total, H, W, word);
   if (!ok()) return 0;
   const bool vec = sc == 1 && (sn | sy | sx) % 4 == 0 && (reinterpret_cast<uintptr_t>(dw) & 15) == 0;
   const dim3 rg((unsigned)rgrid), rb(kThreads);
@@ -533,6 +553,18 @@ int skd_conv3x3_split2_wgrad_nhwc(int B, int H, int W, int Cin, int Cout, int di
                                   int64_t sn, int64_t sc, int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes,
                                   int slices, skd_stream_t stream) {
   return launch<false, 9, 2>(B, H, W, Cin, Cout, dilation, x, g, dw, sn, sc, sy, sx, workspace, workspace_bytes, slices, stream);
+}
+
+// Two FP16 pieces per operand and the scale word of g (skd_train2h.h): the same predicate, plan, workspace and reduce launch.
+int skd_conv3x3_split2h_wgrad_plan(int B, int H, int W, int Cin, int Cout, int slices, int cus, int64_t *plan) {
+  return plan_of<false>(B, H, W, Cin, Cout, slices, cus, plan);
+}
+
+int skd_conv3x3_split2h_wgrad_nhwc(int B, int H, int W, int Cin, int Cout, int dilation, const float *x, const float *g, float *dw,
+                                   int64_t sn, int64_t sc, int64_t sy, int64_t sx, void *workspace, int64_t workspace_bytes,
+                                   const uint32_t *word, int slices, skd_stream_t stream) {
+  return launch<false, 9, 2, kFp16>(B, H, W, Cin, Cout, dilation, x, g, dw, sn, sc, sy, sx, workspace, workspace_bytes, slices, stream, 1,
+                                    word);
 }
 
 // The 1x1 convolution of stride 1 or 2 (skd_shortcut.h): the one-tap form of the kernel, the 128 x 128 tiles where both channel

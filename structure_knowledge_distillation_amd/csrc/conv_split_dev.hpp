@@ -90,6 +90,21 @@ __device__ __forceinline__ void split4_f16(float4 v, uint2 &p0, uint2 &p1) {
   p1.x = pack_f16((v.x - a[0]) * kResidualScale, (v.y - a[1]) * kResidualScale);
   p1.y = pack_f16((v.z - b[0]) * kResidualScale, (v.w - b[1]) * kResidualScale);
 }
+// The SCALE of a gradient tensor's fp16 split (include/skd_train2h.h): `word` is the largest bits & 0x7fffffff of the tensor
+// (csrc/scale_word.hip).  s = 2^k puts a finite amax >= 2^-112 into [2^14, 2^15), k = clamp(14 - e, -126, 126) with e the
+// word's unbiased exponent (-127 for an fp32 subnormal); s and inv = 2^-k are normal fp32, so both multiplications are exact
+// while nothing leaves the normal range.  A zero or non-finite word gives s = inv = 1: an infinity or a NaN is split as it is.
+__host__ __device__ inline void scale_of(uint32_t word, float &s, float &inv) {
+  int k = 0;
+  if (word != 0u && word < 0x7f800000u) {
+    k = 14 - ((int)(word >> 23) - 127);
+    k = k < -126 ? -126 : (k > 126 ? 126 : k);
+  }
+  const uint32_t sb = (uint32_t)(127 + k) << 23, ib = (uint32_t)(127 - k) << 23;
+  s = __builtin_bit_cast(float, sb);
+  inv = __builtin_bit_cast(float, ib);
+}
+__device__ __forceinline__ float4 scaled(float4 v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
 // ... written to the thread's 8-byte slot `dst` of the PIECES planes of one operand's LDS image
 template <int PIECES = 3, int FMT = kBf16>
 __device__ __forceinline__ void split_store(float4 v, uint2 *dst) {

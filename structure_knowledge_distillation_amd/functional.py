@@ -255,10 +255,10 @@ def _cached(owner, attr, key, build, hold=None):
 def drop_conv3x3_packs(owner):
     """Forget the weight packs conv3x3_pack_weights (both piece counts, both piece formats) / conv3x3_train_packs / conv3x3_narrow_pack_weights /
     conv3x3_split_train's narrow form cached on ``owner`` (a module, or a PSPModule's ``_fold_cache`` dict, whose packs sit under
-    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train"; the two-plane training pair of include/skd_train2.h and the narrow
-    fp16 image of include/skd_infer2h.h too)."""
+    "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train"; the two-plane training pairs of include/skd_train2.h and
+    skd_train2h.h and the narrow fp16 image of include/skd_infer2h.h too)."""
     slot = owner if isinstance(owner, dict) else vars(owner)
-    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", _TRAIN2_PACK_ATTR, "pack3x3", "pack3x3_2",
+    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", _TRAIN2_PACK_ATTR, _TRAIN2H_PACK_ATTR, "pack3x3", "pack3x3_2",
                  "pack3x3_2h", "pack3x3_train", _NARROW2H_PACK_ATTR) + _NARROW_PACK_ATTRS:
         slot.pop(attr, None)
 
@@ -464,7 +464,7 @@ def ppm_fold_supported(feats, sizes):
 
 
 def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False, pieces=3,
-                         piece_format="bf16"):
+                         piece_format="bf16", train_fp16=False):
     """conv3x3(cat([upsample(p) for p in priors] + [feats], 1), weight, padding=1) (pspnet_combine.py:104-111) without
     the concatenated tensor and without convolving the priors' channels: the feature-map slice of the weight goes through
     the convolution, the priors through a (B s^2) x Cm x 9 Cout GEMM each and the fold kernel (csrc/ppm.hip).
@@ -477,7 +477,9 @@ def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, spli
     `pieces` = 2: with `split3x3`, the frozen feature-map convolution on the two-piece core (conv3x3_split_eval's ``pieces``), its
     pack under a key of its own in `cache`; with `split_train`, the training form on two bf16 pieces (conv3x3_split_train2,
     include/skd_train2.h), its pack pair in a slot of its own; the fold's matrix products are what they were.
-    `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include/skd_split2h.h), its pack under a third key."""
+    `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include/skd_split2h.h), its pack under a third key.
+    `ppm_fold_bottleneck_train_fp16`: with `split_train`, the training form on two fp16 pieces (conv3x3_split_train_fp16,
+    include/skd_train2h.h), its pack pair in a slot of its own; a frozen call is ppm_fold_bottleneck's."""
     _check_piece_format(_check_pieces(pieces), piece_format)
     import torch.nn.functional as F
     cm = priors[0].shape[1]
@@ -497,6 +499,8 @@ def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, spli
     if train:
         extra = dict(wgrad=True) if split_wgrad else {}
         train_op = conv3x3_split_train2 if pieces == 2 and piece_format == "bf16" else conv3x3_split_train
+        if train_fp16:
+            train_op = conv3x3_split_train_fp16
         base = train_op(feats, weight[:, n_prior:], 1, None, cache.setdefault("pack3x3_train", {}), **extra)
     elif split3x3 and cache is not None and _conv3x3_ok(feats, weight[:, n_prior:], 1, 1, 1, 1, **_FROZEN):
         if pieces == 2:
@@ -523,6 +527,12 @@ def ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, split
 def ppm_fold_bottleneck_fp16(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False):
     """``ppm_fold_bottleneck`` with the frozen feature-map convolution on two FP16 pieces (``conv3x3_split_eval_fp16``)."""
     return _ppm_fold_bottleneck(priors, feats, weight, cache, split3x3, split_train, split_wgrad, 2, "fp16")
+
+
+def ppm_fold_bottleneck_train_fp16(priors, feats, weight, cache=None, split3x3=False, split_train=False, split_wgrad=False):
+    """``ppm_fold_bottleneck`` whose TRAINING form runs the feature-map convolution on two FP16 pieces with a scaled gradient
+    (``conv3x3_split_train_fp16``, include/skd_train2h.h); without ``split_train`` it is ``ppm_fold_bottleneck``."""
+    return _ppm_fold_bottleneck(priors, feats, weight, cache, split3x3, split_train, split_wgrad, 3, "bf16", train_fp16=True)
 
 
 ppm_fold_bottleneck.__doc__ = _ppm_fold_bottleneck.__doc__
@@ -1086,6 +1096,59 @@ def conv3x3_train_packs2(weight, owner=None):
 conv3x3_train_packs.__doc__ = _conv3x3_train_packs.__doc__
 
 
+# include/skd_train2h.h: the training student's wide convolutions on two FP16 pieces with a power-of-two scale per gradient tensor
+# -- the scale word, the fp16 pack pair, the scaled data gradient, the weight gradient's plan and launch -- and the slot the fp16
+# pair is cached in (its own again)
+_TRAIN2H_WORD_BYTES, _TRAIN2H_WORD = "skd_fp16_scale_word_workspace_bytes", "skd_fp16_scale_word"
+_TRAIN2H_PACK_PAIR, _TRAIN2H_SCALED = "skd_conv3x3_split2h_pack_pair", "skd_conv3x3_split2h_scaled_nhwc"
+_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD = "skd_conv3x3_split2h_wgrad_plan", "skd_conv3x3_split2h_wgrad_nhwc"
+_TRAIN2H_PACK_ATTR = "_skd_conv3x3_train_pack2h"
+_TRAIN2H_FWD, _TRAIN2H_PACK_BYTES = "skd_conv3x3_split2h_nhwc", "skd_conv3x3_split2h_pack_bytes"      # include/skd_split2h.h
+_TRAIN2H_ENTRIES = (_TRAIN2H_WORD_BYTES, _TRAIN2H_WORD, _TRAIN2H_PACK_PAIR, _TRAIN2H_SCALED, _TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD,
+                    _TRAIN2H_FWD, _TRAIN2H_PACK_BYTES)
+
+
+def _need_train2h_entry(*names):
+    for name in names:
+        if not _lib.has_entry(name):
+            header = "skd_train2h.h" if name in _lib.ABI["skd_train2h.h"] else "skd_split2h.h"
+            raise NotImplementedError("the active back-end does not provide %s (include/%s)" % (name, header))
+
+
+def train2h_supported():
+    """True when the back-end has the six entries of include/skd_train2h.h and the two of skd_split2h.h they build on (the tests'
+    C double has none of them)."""
+    return all(_lib.has_entry(n) for n in _TRAIN2H_ENTRIES)
+
+
+def fp16_scale_word(g):
+    """The scale word of the dense fp32 tensor ``g`` (include/skd_train2h.h): a one-element int32 device tensor holding
+    ``max(bits(g) & 0x7fffffff)``, from which the fp16 training kernels derive the power of two that puts ``g``'s largest magnitude
+    into [2^14, 2^15).  At most two launches on ``g``'s stream, no host synchronisation, the same word on every call; an infinity
+    or a NaN in ``g`` makes it >= 0x7f800000 (scale 1: a non-finite gradient stays loud)."""
+    _need_train2h_entry(_TRAIN2H_WORD_BYTES, _TRAIN2H_WORD)
+    _lib.require_device(g)
+    if g.dtype != torch.float32 or g.numel() < 1 or not _non_overlapping_and_dense(g) or g.data_ptr() % 16:
+        raise ValueError("fp16_scale_word: a dense, 16-byte aligned fp32 tensor of at least one element expected")
+    lib = _lib.get()
+    n = int(g.numel())
+    nbytes = int(lib.skd_fp16_scale_word_workspace_bytes(n))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=g.device)
+    word = torch.empty((1,), dtype=torch.int32, device=g.device)
+    _lib.check(lib.skd_fp16_scale_word(n, g.data_ptr(), ws.data_ptr(), nbytes, word.data_ptr(), _lib.stream_of(g)), _TRAIN2H_WORD)
+    return word
+
+
+def conv3x3_train_packs_fp16(weight, owner=None):
+    """``conv3x3_train_packs`` for ``conv3x3_split_train_fp16``: the two-plane FP16 images of include/skd_train2h.h
+    (skd_conv3x3_split2h_pack_pair, 4 bytes per weight: p0 and the scaled p1 of skd_split2h.h) for the forward and for the data
+    gradient, one launch, cached per ``(data_ptr, _version)`` in a slot of its own beside the bf16 pairs.  A back-end without
+    the entry raises NotImplementedError."""
+    _need_train2h_entry(_TRAIN2H_PACK_PAIR, _TRAIN2H_PACK_BYTES)
+    return _conv3x3_packs(weight, owner, _TRAIN2H_PACK_ATTR, _TRAIN2H_PACK_PAIR, "conv3x3_train_packs_fp16", (True, True),
+                          _TRAIN2H_PACK_BYTES)
+
+
 _ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
 _RES_ENTRY = "skd_conv3x3_split_res_nhwc"
 # include/skd_split2.h: the two-piece form of the frozen 128-column convolution, its pack entry, its size query, its cache slot
@@ -1471,9 +1534,10 @@ def _non_overlapping_and_dense(t):
     return True
 
 
-def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilation, slices):
+def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilation, slices, word=()):
     """The body conv3x3_split_wgrad and conv3x3_narrow_wgrad share: the checks, the plan call, the workspace, the layout of ``dw``
-    and the launch entry, on the pair of entries ``plan_entry`` / ``run_entry`` (skd_wgrad.h or skd_narrow_wgrad.h)."""
+    and the launch entry, on the pair of entries ``plan_entry`` / ``run_entry`` (skd_wgrad.h or skd_narrow_wgrad.h).  ``word``:
+    ``(pointer,)`` for the entry of skd_train2h.h, which takes the scale word of ``g`` in front of the slice count."""
     _lib.require_device(x, g)
     lib = _lib.get()
     b, cin, h, w = (int(v) for v in x.shape)
@@ -1491,7 +1555,7 @@ def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilati
     else:
         dw = torch.empty(tuple(weight_like.shape), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     _lib.check(getattr(lib, run_entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), g.data_ptr(), dw.data_ptr(),
-                                       *(int(v) for v in dw.stride()), ws.data_ptr(), int(plan[2]), int(plan[0]),
+                                       *(int(v) for v in dw.stride()), ws.data_ptr(), int(plan[2]), *word, int(plan[0]),
                                        _lib.stream_of(x)), run_entry)
     return dw
 
@@ -1526,6 +1590,38 @@ def conv3x3_split_wgrad2(x, g, weight_like, dilation, slices=0):
 conv3x3_split_wgrad.__doc__ = _conv3x3_split_wgrad.__doc__
 
 
+def _check_word(word, like):
+    if word is not None and (word.dtype != torch.int32 or word.numel() != 1 or word.device != like.device):
+        raise ValueError("word: the one-element int32 tensor of fp16_scale_word on the gradient's device expected")
+    return word
+
+
+def conv3x3_split_wgrad_fp16(x, g, weight_like, dilation, slices=0, word=None):
+    """``conv3x3_split_wgrad`` on two FP16 pieces per operand and three products (include/skd_train2h.h): ``g``'s rows are
+    multiplied by the power of two of ``word`` (``fp16_scale_word(g)``) in front of the split, the result by its reciprocal;
+    ``x`` is not scaled and keeps skd_split2h.h's loud contract (|x| > 65504 gives NaN).  ``word=None``: scale 1 -- gradients
+    below fp16's range are then lost, so a caller passes the word.  The same plan, workspace, slice sum and result layout; 22
+    significant bits per operand.  A back-end without the entries raises NotImplementedError."""
+    _need_train2h_entry(_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD)
+    _lib.require_device(_check_word(word, g))
+    return _conv3x3_wgrad_launch("conv3x3_split_wgrad_fp16", _TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD, x, g, weight_like, dilation, slices,
+                                 (_lib.ptr(word),))
+
+
+def _conv3x3_scaled_launch(g, pack, cout, dilation, word):
+    """conv3x3(g) on the fp16 image ``pack`` with ``g`` scaled by its ``word`` (skd_conv3x3_split2h_scaled_nhwc): the data gradient
+    of include/skd_train2h.h, one launch, raw."""
+    lib = _lib.get()
+    b, cin, h, w = g.shape
+    if pack.numel() != lib.skd_conv3x3_split2h_pack_bytes(cin, cout):
+        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (_TRAIN2H_SCALED, cout, cin))
+    _lib.require_device(g, pack, _check_word(word, g))
+    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
+    _lib.check(lib.skd_conv3x3_split2h_scaled_nhwc(b, h, w, cin, cout, int(dilation), g.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                                   word.data_ptr(), 0, _lib.stream_of(g)), _TRAIN2H_SCALED)
+    return out
+
+
 _NARROW_WGRAD_ENTRIES = ("skd_conv3x3_narrow_wgrad_supported", "skd_conv3x3_narrow_wgrad_plan", "skd_conv3x3_narrow_wgrad_nhwc")
 
 
@@ -1557,7 +1653,9 @@ class _Conv3x3SplitTrain(Function):
     (conv3x3_split_train's ``stats``) makes the forward return ``(y, partials)`` -- the same ``y`` and the statistics records of
     include/skd_bnstats.h, marked non-differentiable; the backward is the same.  A fifth (2, from conv3x3_split_train2) is the
     piece count of the wide form's products: the packs are two-plane images, forward and data gradient run
-    skd_conv3x3_split2_nhwc and ``wgrad`` is conv3x3_split_wgrad2's (include/skd_train2.h)."""
+    skd_conv3x3_split2_nhwc and ``wgrad`` is conv3x3_split_wgrad2's (include/skd_train2.h).  "fp16" in its place (from
+    conv3x3_split_train_fp16; include/skd_train2h.h): the packs are the fp16 pair, the forward runs skd_conv3x3_split2h_nhwc, and the
+    backward computes the scale word of ``g`` ONCE and hands it to the scaled data gradient and to conv3x3_split_wgrad_fp16."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, *wgrad):
@@ -1569,6 +1667,9 @@ class _Conv3x3SplitTrain(Function):
         # (forward?, backward?) on the narrow entry: the third optional argument (conv3x3_split_train's ``narrow``)
         fwd_narrow, ctx.bwd_narrow = wgrad[1] if len(wgrad) > 1 else (False, False)
         ctx.two = two = dict(pieces=2) if len(wgrad) > 3 and wgrad[3] == 2 else {}      # the keyword only where it says 2
+        ctx.fp16 = len(wgrad) > 3 and wgrad[3] == "fp16"
+        if ctx.fp16:
+            return _conv3x3_launch(_TRAIN2H_FWD, x, pack_fwd, int(weight.shape[0]), dilation, bias)
         if len(wgrad) > 2 and wgrad[2]:
             y, partials = _conv3x3_stats_launch(fwd_narrow, x, pack_fwd, int(weight.shape[0]), dilation, bias)
             ctx.mark_non_differentiable(partials)
@@ -1586,14 +1687,24 @@ class _Conv3x3SplitTrain(Function):
         if g.data_ptr() % 16:
             g = g.clone(memory_format=torch.channels_last)
         dx = dw = db = None
+        # (the entries the branch below launches: the fp16 form does not depend on skd_wgrad.h)
+        wgrad_entries = ((_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD) if ctx.fp16 else _NARROW_WGRAD_ENTRIES if ctx.narrow_wgrad
+                         else _WGRAD_ENTRIES)
+        split_w = ctx.wgrad and ctx.needs_input_grad[1] and all(_lib.has_entry(n) for n in wgrad_entries)
+        # fp16 pieces: ONE scale word of g for both gradient products
+        word = fp16_scale_word(g) if ctx.fp16 and (ctx.needs_input_grad[0] or split_w) else None
         if ctx.needs_input_grad[0]:
-            if ctx.bwd_narrow:
+            if ctx.fp16:
+                dx = _conv3x3_scaled_launch(g, ctx.pack_bwd, int(weight.shape[1]), d, word)
+            elif ctx.bwd_narrow:
                 dx = _conv3x3_narrow_launch(g, ctx.pack_bwd, int(weight.shape[1]), d)
             else:
                 dx = _conv3x3_split_launch(g, ctx.pack_bwd, int(weight.shape[1]), d, **ctx.two)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.wgrad and need_w and all(_lib.has_entry(n) for n in (_NARROW_WGRAD_ENTRIES if ctx.narrow_wgrad else _WGRAD_ENTRIES)):
-            if ctx.narrow_wgrad:
+        if split_w:
+            if ctx.fp16:
+                dw = conv3x3_split_wgrad_fp16(x, g, weight, d, word=word)
+            elif ctx.narrow_wgrad:
                 dw = conv3x3_narrow_wgrad(x, g, weight, d)
             else:
                 dw = (conv3x3_split_wgrad2 if ctx.two else conv3x3_split_wgrad)(x, g, weight, d)
@@ -1663,6 +1774,27 @@ def conv3x3_split_train2(x, weight, dilation, bias=None, owner=None, *, wgrad=Fa
 
 
 conv3x3_split_train.__doc__ = _conv3x3_split_train.__doc__
+
+
+def conv3x3_split_train_fp16(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False,
+                             stats=False):
+    """``conv3x3_split_train`` with the WIDE form on two FP16 pieces per operand, a scaled residual and three products
+    (include/skd_train2h.h; opt-in): 22 significant bits per operand -- the three-piece accuracy at the two-piece product count.
+    The forward is skd_conv3x3_split2h_nhwc on the fp16 forward pack (conv3x3_train_packs_fp16, cached apart from the bf16
+    pairs); ``x`` and the weight are NOT scaled, so it keeps skd_split2h.h's loud contract: |x| or |w| above 65504 gives NaN.  The
+    backward computes the scale word of the output gradient once (fp16_scale_word) and hands it to the scaled data gradient and,
+    with ``wgrad``, to conv3x3_split_wgrad_fp16: gradients far below fp16's range lose nothing, a non-finite gradient stays
+    non-finite.  A direction ``narrow`` puts on the 64-column form and a call with ``stats`` have no fp16 form: they keep three
+    bf16 pieces, as under conv3x3_split_train2.  The library's weight gradient (``wgrad=False``) and the bias gradient are what
+    they were.  A back-end without the entries raises NotImplementedError."""
+    _need_train2h_entry(_TRAIN2H_PACK_PAIR, _TRAIN2H_PACK_BYTES, _TRAIN2H_FWD, _TRAIN2H_WORD_BYTES, _TRAIN2H_WORD, _TRAIN2H_SCALED,
+                        *((_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD) if wgrad else ()))
+    # (a 64-channel side, decided from the shape as _conv3x3_narrow_train_packs decides it, in front of any pack launch)
+    if stats or (narrow and (int(weight.shape[0]) % 128 != 0 or int(weight.shape[1]) % 128 != 0)):
+        return _conv3x3_split_train(x, weight, dilation, bias, owner, wgrad=wgrad, narrow=narrow, narrow_wgrad=narrow_wgrad,
+                                    stats=stats)
+    pack_fwd, pack_bwd = conv3x3_train_packs_fp16(weight, owner)
+    return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), False, "fp16")
 
 
 # ---- the training student's 1x1 down-sample (shortcut) convolutions on the split core (include/skd_shortcut.h) ----

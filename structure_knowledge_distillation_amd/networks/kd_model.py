@@ -195,15 +195,22 @@ class NetModel():
         # args.student_pieces (None: SKD_STUDENT_PIECES, default "3"; outside SWITCHES, like teacher_pieces): 2 = the student's 13 wide
         # training convolutions on two bf16 pieces per operand and three products (route_training_convs(pieces=2),
         # include/skd_train2.h) -- an ACCURACY trade, effective only together with split_train: without it nothing is routed.
+        # args.student_piece_format (None: SKD_STUDENT_PIECE_FORMAT, default "bf16"): "fp16" with student_pieces = 2 = two FP16 pieces
+        # with a power-of-two scale per gradient tensor (route_training_convs(pieces=2, piece_format="fp16"), include/skd_train2h.h)
+        # -- NOT an accuracy trade; without student_pieces = 2 it is a ValueError, without split_train the one warning below.
         self.student_pieces = _student_pieces(getattr(args, "student_pieces", None))
+        self.student_piece_format = _student_piece_format(getattr(args, "student_piece_format", None), self.student_pieces)
         if self.student_pieces == 2 and not self.split_train:
             import warnings
-            warnings.warn("student_pieces / SKD_STUDENT_PIECES = 2 takes effect only together with split_train / SKD_SPLIT_TRAIN: "
+            what = ("student_pieces / SKD_STUDENT_PIECES = 2" if self.student_piece_format == "bf16" else
+                    "student_pieces / SKD_STUDENT_PIECES = 2 with student_piece_format / SKD_STUDENT_PIECE_FORMAT = 'fp16'")
+            warnings.warn(what + " takes effect only together with split_train / SKD_SPLIT_TRAIN: "
                           "nothing is routed and the student's convolutions are what they were", RuntimeWarning, stacklevel=2)
         if self.split_train:
             route_training_convs(student, wgrad=self.split_wgrad, narrow=self.split_narrow, narrow_wgrad=self.split_narrow_wgrad,
                                  shortcut=self.split_shortcut, bnstats=self.split_bnstats,
-                                 **(dict(pieces=2) if self.student_pieces == 2 else {}))
+                                 **(dict(pieces=2) if self.student_pieces == 2 else {}),
+                                 **(dict(piece_format="fp16") if self.student_piece_format == "fp16" else {}))
 
         teacher = Res_pspnet(Bottleneck, [3, 4, 23, 3], num_classes=args.classes_num)
         load_T_model(teacher, getattr(args, "T_ckpt_path", None))
@@ -952,6 +959,19 @@ def _teacher_piece_format(value, pieces):
     return value
 
 
+def _student_piece_format(value, pieces):
+    """``value`` (None: the environment's SKD_STUDENT_PIECE_FORMAT, default "bf16") as "bf16" or "fp16"; anything else, and "fp16"
+    with ``pieces`` other than 2, is a ValueError."""
+    if value is None:
+        value = os.environ.get("SKD_STUDENT_PIECE_FORMAT", "bf16")
+    value = str(value).strip()
+    if value not in ("bf16", "fp16"):
+        raise ValueError("student_piece_format / SKD_STUDENT_PIECE_FORMAT must be 'bf16' or 'fp16', not %r" % (value,))
+    if value == "fp16" and pieces != 2:
+        raise ValueError("student_piece_format 'fp16' requires student_pieces / SKD_STUDENT_PIECES = 2, not %r" % (pieces,))
+    return value
+
+
 def _infer_piece_format(value):
     """``value`` (None: the environment's SKD_INFER_PIECE_FORMAT, default "bf16") as "bf16" or "fp16"; anything else is a
     ValueError."""
@@ -983,7 +1003,7 @@ def default_args(**overrides):
         ohem=False, ohem_thresh=0.7, ohem_keep=100000, fused_eval=False, split_train=None,
         split_wgrad=None, split_narrow=None, split_narrow_wgrad=None, split_shortcut=None, teacher_pieces=None,
         split_bnstats=None, teacher_early=None, split_stride2=None, split_pairwise=None, teacher_planes=None,
-        teacher_piece_format=None, student_pieces=None, infer_piece_format=None)
+        teacher_piece_format=None, student_pieces=None, infer_piece_format=None, student_piece_format=None)
     for k, v in overrides.items():
         setattr(a, k, v)
     for name, env, _ in SWITCHES:      # None: the environment switch
@@ -992,6 +1012,7 @@ def default_args(**overrides):
     a.teacher_pieces = _teacher_pieces(a.teacher_pieces)      # 2: the frozen teacher on two pieces (an accuracy trade); default 3
     a.teacher_piece_format = _teacher_piece_format(a.teacher_piece_format, a.teacher_pieces)      # "fp16": two fp16 pieces (skd_split2h.h)
     a.student_pieces = _student_pieces(a.student_pieces)      # 2: the student's wide training convolutions on two pieces; default 3
+    a.student_piece_format = _student_piece_format(a.student_piece_format, a.student_pieces)      # "fp16": two fp16 pieces, scaled gradients (skd_train2h.h)
     a.infer_piece_format = _infer_piece_format(a.infer_piece_format)      # "fp16": the fused inference form on two fp16 pieces (skd_infer2h.h)
     a.teacher_planes = _teacher_planes(a.teacher_planes)      # the teacher's conv1 -> conv2 link as bf16 piece planes (include/skd_planes.h)
     return a

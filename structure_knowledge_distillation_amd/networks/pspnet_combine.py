@@ -96,6 +96,12 @@ WGRAD_ROUTING_EXCLUDED = frozenset()
 STUDENT_PIECES_ROUTING_EXCLUDED = frozenset()
 _TRAIN2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_pair",
                    "skd_conv3x3_split2_wgrad_plan", "skd_conv3x3_split2_wgrad_nhwc")
+# The same 13 convolutions on two FP16 pieces per operand with a power-of-two scale per gradient tensor
+# (route_training_convs(pieces=2, piece_format="fp16"); NOT an accuracy trade: include/skd_train2h.h): forward on
+# skd_conv3x3_split2h_nhwc, data gradient and -- with ``wgrad`` -- weight gradient on the scaled entries.  A shape that does not
+# measure ahead of its three-piece twin by more than the spread is listed here as (Cin, Cout, dilation) and keeps THREE pieces,
+# never two bf16 ones (profiles/r35_student_fp16_isolated.md).
+STUDENT_FP16_ROUTING_EXCLUDED = frozenset()
 # The 64-channel convolutions (fuse_for_inference(narrow=True), route_training_convs(narrow=True); a further opt-in on top of either):
 # the stem's conv2 (64 -> 64) and layer1's four convolutions (128 -> 64, then three 64 -> 64) on the 64-column form of the kernel
 # (csrc/conv3x3.hip with 64-column tiles), the stem's conv3 (64 -> 128) on the wide kernel in the forward and on the narrow one for its data
@@ -301,6 +307,14 @@ def _student_pieces(module, cin, cout, dilation):
     return 3
 
 
+def _student_fp16(module, cin, cout, dilation):
+    """Whether a WIDE convolution the flagged ``module`` routes runs on two fp16 pieces: route_training_convs(pieces=2,
+    piece_format="fp16") marked it (``_skd_train_piece_format``, a mark of its own beside ``_skd_train_pieces``), the back-end has
+    the entries of include/skd_train2h.h and the shape is outside STUDENT_FP16_ROUTING_EXCLUDED.  Otherwise three pieces."""
+    return (getattr(module, "_skd_train_piece_format", "bf16") == "fp16" and (cin, cout, dilation) not in STUDENT_FP16_ROUTING_EXCLUDED
+            and SF.train2h_supported())
+
+
 def _train_form(module, x, conv, bn=None):
     """``(form, wgrad, stats)``: how the flagged ``module`` (route_training_convs) in training mode runs ``conv(x)``.
     ``form``: "wide" -- SF.conv3x3_split_train: at least ``_skd_train_min_cin`` input channels, outside TRAIN_ROUTING_EXCLUDED
@@ -341,7 +355,9 @@ def _train_conv(module, conv, x, bn=None):
     narrow = form == "narrow"
     # two pieces: the wide form without statistics alone (the twin op only where the count is 2: every other call is what it was)
     two = not narrow and not stats and _student_pieces(module, conv.in_channels, conv.out_channels, conv.dilation[0]) == 2
-    out = (SF.conv3x3_split_train2 if two else SF.conv3x3_split_train)(
+    # two fp16 pieces: the same forms, under the mark of its own (a module never carries both marks)
+    fp16 = not narrow and not stats and _student_fp16(module, conv.in_channels, conv.out_channels, conv.dilation[0])
+    out = (SF.conv3x3_split_train_fp16 if fp16 else SF.conv3x3_split_train2 if two else SF.conv3x3_split_train)(
         x, conv.weight, conv.dilation[0], conv.bias, owner=conv, wgrad=wgrad and not narrow, narrow=narrow,
         narrow_wgrad=wgrad and narrow, stats=stats)
     return out if stats else (out, None)
@@ -684,6 +700,9 @@ class PSPModule(nn.Module):
                 pieces, fmt = ((_student_pieces(self, feats.shape[1], conv.out_channels, 1), "bf16") if self.training
                                else _piece_route(self, "3x3", feats.shape[1], conv.out_channels, 1))
                 fold, kw = _piece_op("ppm_fold_bottleneck", pieces, fmt)
+                if self.training and _student_fp16(self, feats.shape[1], conv.out_channels, 1):
+                    # the trained feature half on two fp16 pieces (route_training_convs(piece_format="fp16"))
+                    fold, kw = SF.ppm_fold_bottleneck_train_fp16, {}
                 out = fold(priors, feats, conv.weight, self._fold_cache,
                            split3x3=CONV3X3_SPLIT and not self.training and feats.shape[1] >= CONV3X3_SPLIT_MIN_CIN,
                            split_train=(min_cin is not None and self.training and feats.shape[1] >= min_cin
@@ -1029,7 +1048,7 @@ def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
 
 
 def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=False, narrow=False, narrow_wgrad=False,
-                         shortcut=False, bnstats=False, pieces=3):
+                         shortcut=False, bnstats=False, pieces=3, piece_format="bf16"):
     """Flag ``model`` (the student) for the training form of its 3x3 convolutions and return ``model``.
 
     A flagged module in training mode, with grad enabled, on an fp32 channels-last device input runs ``BasicBlock.conv1`` /
@@ -1068,10 +1087,31 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     pieces, or the library, whatever ``pieces`` says: the 64-column forms of ``narrow`` and their weight gradients; the 1x1
     shortcut convolutions of ``shortcut``; a convolution that writes statistics (``bnstats``); every stride-2 convolution.  On a
     back-end without the entries the student stays on three pieces.  Anything but the integers 2 and 3 is a ValueError.
+    ``pieces=2, piece_format="fp16"`` -- opt-in, NOT an accuracy trade (include/skd_train2h.h): the same 13
+    convolutions on two FP16 pieces per operand with the residual scaled by 2^11 and three products, 22 significant bits per
+    operand (SF.conv3x3_split_train_fp16, SF.ppm_fold_bottleneck_train_fp16).  The forward runs skd_conv3x3_split2h_nhwc; the
+    backward finds a power-of-two scale of the output gradient on the device (SF.fp16_scale_word, once per convolution) and hands
+    it to the scaled data gradient and, with ``wgrad``, to SF.conv3x3_split_wgrad_fp16, so gradients far below fp16's range lose
+    nothing.  ``x`` and the weights are not scaled: an activation or a weight beyond +-65504 gives NaN (skd_split2h.h's loud
+    contract).  The shapes of STUDENT_FP16_ROUTING_EXCLUDED keep THREE pieces, never two bf16 ones, and so does everything
+    ``pieces=2`` leaves on three.  The mark (``_skd_train_piece_format``) is its own; a module never carries it together with
+    ``_skd_train_pieces``.  "fp16" with ``pieces=3`` and anything but "bf16" / "fp16" are ValueErrors; on a back-end without
+    the entries it warns once (RuntimeWarning, naming skd_train2h.h) and the student stays on three pieces.  The default "bf16"
+    changes nothing.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
     if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
         raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
+    if piece_format not in ("bf16", "fp16"):
+        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
+    if piece_format == "fp16" and pieces != 2:
+        raise ValueError("piece_format='fp16' requires pieces=2 (include/skd_train2h.h), not pieces=%r" % (pieces,))
+    fp16 = bool(enable) and piece_format == "fp16"
+    if fp16 and not SF.train2h_supported():
+        import warnings
+        warnings.warn("route_training_convs: this back-end lacks the fp16 training entries (include/skd_train2h.h); the student "
+                      "stays on three pieces", RuntimeWarning, stacklevel=2)
+        fp16, pieces = False, 3
     for m in model.modules():
         if not isinstance(m, (BasicBlock, ResNet, PSPModule)):
             continue
@@ -1079,10 +1119,14 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
         m._skd_train_wgrad = bool(wgrad and enable)
         m._skd_train_narrow = bool(narrow and enable)
         m._skd_train_narrow_wgrad = bool(narrow_wgrad and enable)
-        if enable and pieces == 2:
+        if enable and pieces == 2 and not fp16:
             m._skd_train_pieces = 2
         else:
             vars(m).pop("_skd_train_pieces", None)
+        if fp16:
+            m._skd_train_piece_format = "fp16"
+        else:
+            vars(m).pop("_skd_train_piece_format", None)
         if isinstance(m, BasicBlock):
             m._skd_train_shortcut = bool(shortcut and enable)
             m._skd_train_bnstats = bool(bnstats and enable)
