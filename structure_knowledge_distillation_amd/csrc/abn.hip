@@ -625,13 +625,12 @@ static bool same_phase(const void *a, const void *b) {
   return ((reinterpret_cast<uintptr_t>(a) ^ reinterpret_cast<uintptr_t>(b)) & 15) == 0;
 }
 
-template <bool WRITE_Y>
 static void launch_apply(int act, const Plan &pl, hipStream_t st, const float *x, const float *mean,
                          const float *var, const float *weight, const float *bias, float *y, float *z,
                          float eps, float slope, int N, int C, int S, int reverse) {
   const dim3 grid((unsigned)pl.items), block(kThreads);
   dispatch_act_or_none<SKD_ACT_LEAKY_RELU, SKD_ACT_ELU, SKD_ACT_RELU>(act, [&](auto a) {
-    abn_apply_kernel<decltype(a)::value, WRITE_Y><<<grid, block, 0, st>>>(x, mean, var, weight, bias, y, z, eps, slope, N, C, S, pl, reverse);
+    abn_apply_kernel<decltype(a)::value, false><<<grid, block, 0, st>>>(x, mean, var, weight, bias, y, z, eps, slope, N, C, S, pl, reverse);
   });
 }
 
@@ -698,7 +697,7 @@ int skd_abn_apply(int N, int C, int S, float *x, const float *mean, const float 
                   skd_stream_t stream) {
   if (!valid_dims(N, C, S) || !x || !mean || !var) return 0;
   const Plan pl = make_plan(N, C, S);
-  launch_apply<false>(activation, pl, as_stream(stream), x, mean, var, weight, bias, x, x, eps, slope, N, C, S, 0);
+  launch_apply(activation, pl, as_stream(stream), x, mean, var, weight, bias, x, x, eps, slope, N, C, S, 0);
   return ok();
 }
 
@@ -719,7 +718,7 @@ int skd_abn_forward_train(int N, int C, int S, float *x, const float *weight, co
   const Plan pl = make_plan(N, C, S);
   hipStream_t st = as_stream(stream);
   launch_stats_nchw(pl, st, N, C, S, x, workspace, mean, var, running_mean, running_var, momentum, (double)N * (double)S);
-  launch_apply<false>(activation, pl, st, x, mean, var, weight, bias, x, x, eps, slope, N, C, S, 1);
+  launch_apply(activation, pl, st, x, mean, var, weight, bias, x, x, eps, slope, N, C, S, 1);
   return ok();
 }
 
@@ -782,7 +781,7 @@ static int launch_apply_to(int N, int C, int S, const float *x, const float *res
                            int activation, float slope, hipStream_t st, int reverse) {
   const Plan pl = make_plan(N, C, S);
   if (residual == nullptr) {
-    launch_apply<false>(activation, pl, st, x, mean, var, weight, bias, out, out, eps, slope, N, C, S, reverse);
+    launch_apply(activation, pl, st, x, mean, var, weight, bias, out, out, eps, slope, N, C, S, reverse);
     return ok();
   }
   return launch_apply_residual(activation, pl, st, x, residual, mean, var, weight, bias, out, eps, slope, N, C, S);
@@ -857,9 +856,10 @@ int skd_bn_forward(int N, int C, int S, const float *x, const float *mean, const
   if (!same_phase(x, y) || !same_phase(x, z)) return 0;
   const Plan pl = make_plan(N, C, S);
   if (y == z)
-    launch_apply<false>(SKD_ACT_NONE, pl, as_stream(stream), x, mean, var, weight, bias, y, z, eps, 0.f, N, C, S, 0);
-  else
-    launch_apply<true>(SKD_ACT_NONE, pl, as_stream(stream), x, mean, var, weight, bias, y, z, eps, 0.f, N, C, S, 0);
+    launch_apply(SKD_ACT_NONE, pl, as_stream(stream), x, mean, var, weight, bias, y, z, eps, 0.f, N, C, S, 0);
+  else   // (the only caller that writes y apart from z, and it has no activation: launched directly, so that no other <ACT, true> exists)
+    abn_apply_kernel<SKD_ACT_NONE, true><<<dim3((unsigned)pl.items), dim3(kThreads), 0, as_stream(stream)>>>(x, mean, var, weight, bias, y, z, eps, 0.f, N,
+                                                                                                          C, S, pl, 0);
   return ok();
 }
 

@@ -473,12 +473,18 @@ static int launch_fwd_fused(int act, int64_t rows, int C, const float *x, const 
   if (f.nr <= 5) SKD_FWD_FUSED(ACT_, 5);       \
   else if (f.nr <= 9) SKD_FWD_FUSED(ACT_, 9);  \
   else SKD_FWD_FUSED(ACT_, 17)
+  // (`if constexpr`: a residual comes with ReLU only, and a run-time `!HAS_RES &&` still instantiated the six <NONE / LEAKY, true>
+  // kernels, twelve with the synchronised ones, that no entry can launch)
   if (act == SKD_ACT_RELU) {
     SKD_FWD_FUSED_NR(SKD_ACT_RELU);
-  } else if (!HAS_RES && act == SKD_ACT_LEAKY_RELU) {
-    SKD_FWD_FUSED_NR(SKD_ACT_LEAKY_RELU);
-  } else if (!HAS_RES && act == SKD_ACT_NONE) {
-    SKD_FWD_FUSED_NR(SKD_ACT_NONE);
+  } else if constexpr (!HAS_RES) {
+    if (act == SKD_ACT_LEAKY_RELU) {
+      SKD_FWD_FUSED_NR(SKD_ACT_LEAKY_RELU);
+    } else if (act == SKD_ACT_NONE) {
+      SKD_FWD_FUSED_NR(SKD_ACT_NONE);
+    } else {
+      return -1;
+    }
   } else {
     return -1;
   }

@@ -36,7 +36,10 @@ CASES = [
     ("longk-256-512-13x11-s1", 2, 256, 512, 13, 11, 1),        # K = 256; four column tiles
     ("rounds-128-64-161x161-s1", 4, 128, 64, 161, 161, 1),     # 811 row tiles: more than one round of a 256-CU device
 ]
-CASE = {c[0]: c for c in CASES}
+# integers only (exact against float64, no parent figure needed): the stride-2 data gradient with Cin a multiple of 128, i.e.
+# conv1x1_train_kernel<128, kMapY> (csrc/conv1x1_train.hip:165-172) -- every stride-2 case above has Cin = 64, the 64-column form
+EXACT_ONLY = [("dgrad-wide-128-128-13x11-s2", 2, 128, 128, 13, 11, 2)]
+CASE = {c[0]: c for c in CASES + EXACT_ONLY}
 SMALL = [c[0] for c in CASES[:-1]]
 PRODUCTS = ("fwd", "dgrad", "wgrad")
 
@@ -193,7 +196,7 @@ def test_product_vs_float64(hip, name, product):
 
 # ---- 2. integers are exact ------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", SMALL)
+@pytest.mark.parametrize("name", SMALL + [c[0] for c in EXACT_ONLY])
 def test_integers_bit_exact_and_adjoint(hip, name):
     s = CASE[name][6]
     x, wt, g = int_inputs(name)

@@ -174,13 +174,17 @@ def test_bits_of_the_wide_kernel(hip, cout, epi):
 
 
 def test_residual_is_one_fp32_add_behind_the_bn_expression(hip):
-    """With a residual r: the bits of relu(z + r) in fp32, z the same launch's ``activation = none`` output without it."""
+    """With a residual r: the bits of relu(z + r) in fp32, z the same launch's ``activation = none`` output without it; and with
+    leaky ReLU behind the same sum, the bits of its fp32 expression (slope 0.01, the value ``launch`` passes)."""
     name = "n-ragged-13x11-d2-bn-res-relu"
     x, wt, p = case_inputs(name)
     z = run_narrow(hip, x, wt, dict(p, res=None, act="none"), 2)
     got = run_narrow(hip, x, wt, p, 2)
     want = torch.relu(z + p["res"])
     assert torch.equal(got, want) and not torch.equal(got, torch.relu(z))
+    v = z + p["res"]
+    leaky = run_narrow(hip, x, wt, dict(p, act="leaky_relu"), 2)
+    assert torch.equal(leaky, torch.where(v < 0, v * torch.tensor(0.01), v)) and bool((v < 0).any())
 
 
 # ---- 3. integers, geometries, weight layout ---------------------------------------------------------------------------------

@@ -258,7 +258,7 @@ def test_consumer_gives_the_bits_of_the_fp32_entry(hip, shape, d, cin, cout):
     A.check()
     assert by_host.numel() == nb and torch.equal(by_host.cpu(), by_kernel.cpu())
     want, out = A.out("want", (m, cout), row=cout), A.out("out", (m, cout), row=cout)
-    for v, eps, act in ((none, 0.0, "none"), (vec, 1e-5, "relu")):
+    for v, eps, act in ((none, 0.0, "none"), (vec, 1e-5, "relu"), (vec, 1e-5, "leaky_relu")):      # (leaky: the <128, 1, *, PLANES> forms)
         for geometry in range(4):
             want.fill_(float("nan"))
             assert hip.skd_conv3x3_split_nhwc(*conv_args(b, h, w, cin, cout, dx, pk, want, v, eps, act, d, geometry, False)) == 1

@@ -132,6 +132,17 @@ CASES1 = [
     ("reduce-K2048-N512", 2048, 512, T1.RAGGED_M, False, False, 3, dict(nt=1, ct=1, pm=2, half=False, padded=True)),
     ("down-K1024-N2048-hh", 1024, 2048, HH, False, False, 0, dict(nt=1, ct=2, pm=4, half=True)),      # NT super-tile + half-height
     ("reduce-K256-N128-hh", 256, 128, HH, False, False, 3, dict(nt=0, ct=1, pm=1, half=True)),        # half-height, panel-major
+    # the epilogue / prologue combinations of the two-piece kernel that the rows above do not instantiate (the recipes of the
+    # three-piece tests under their own names, hence their measured parent figures): panel-major at K = 64 ...
+    ("ragged-K64-N256-pro-res-none", 64, 256, T1.RAGGED_M, True, True, 0, None),
+    ("ragged-K64-N256-nopro-res-none", 64, 256, T1.RAGGED_M, False, True, 0, None),
+    ("ragged-K64-N256-nopro-res-relu", 64, 256, T1.RAGGED_M, False, True, 3, None),
+    ("ragged-K64-N256-pro-nores-relu", 64, 256, T1.RAGGED_M, True, False, 3, None),
+    # ... and in column chunks (NT) at K = 512, N = 2048
+    ("ragged-K512-N2048-pro-nores-none", 512, 2048, T1.RAGGED_M, True, False, 0, dict(nt=1, ct=4, pm=8, half=False)),
+    ("ragged-K512-N2048-nopro-res-none", 512, 2048, T1.RAGGED_M, False, True, 0, dict(nt=1, ct=4, pm=8, half=False)),
+    ("ragged-K512-N2048-pro-res-none", 512, 2048, T1.RAGGED_M, True, True, 0, dict(nt=1, ct=4, pm=8, half=False)),
+    ("ragged-K512-N2048-nopro-res-relu", 512, 2048, T1.RAGGED_M, False, True, 3, dict(nt=1, ct=4, pm=8, half=False)),
 ]
 
 
@@ -267,7 +278,7 @@ def test_pack_is_the_first_two_planes(hip, cin, cout):
 
 
 def test_geometries_and_repeats_give_the_same_bits(hip):
-    for name in ("many-tiles-226x226-d1", "ragged-13x11-d2"):
+    for name in ("many-tiles-226x226-d1", "ragged-13x11-d2", "ragged-13x11-d2-bn-relu"):      # (the last: the tall tile with the ReLU epilogue)
         x, wt, p = T3.case_inputs(name)
         d = T3.CASE[name][6]
         base, pk = run3(hip, x, wt, p, d)

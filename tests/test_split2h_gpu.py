@@ -173,6 +173,10 @@ def check_exact(cls, got, x2d, w2d, what, bf16=None):
 
 
 CASES1 = list(itertools.product((130, 257), (16, 48, 272), (128, 256), (False, True)))
+# K = 272 runs through the prologue entry; at M = 2113, N = 2048 the launch is cut in column chunks: the NT forms of the two-piece kernel
+CASES1 += [(2113, 272, 2048, False), (2113, 272, 2048, True)]
+# ... and without the prologue: column chunks depend on K and N alone (128 * K * 4 bytes a column tile against 2^20), K = 144 gives 14 of 16
+CASES1 += [(130, 144, 2048, True)]
 
 
 @pytest.mark.parametrize("m,k,n,res", CASES1, ids=["M%d-K%d-N%d%s" % (m, k, n, "-res" if r else "") for m, k, n, r in CASES1])
@@ -345,7 +349,8 @@ def test_guard_bands_around_every_operand(hip):
                                             ACT["leaky_relu"], 0.01, geometry, None)
         outs.append(y)
     for mm, k, n, pro, res in ((257, 48, 256, False, True), (130, 272, 128, True, True), (257, 16, 128, False, False),
-                               (130, 272, 256, True, False)):
+                               (130, 272, 256, True, False),
+                               (130, 272, 2048, True, False), (130, 144, 2048, False, True)):      # N = 2048: in column chunks (the NT forms with ReLU)
         x1 = A.inp("x1", torch.randn(mm, k, generator=g))
         w1 = A.inp("w1", torch.randn(n, k, generator=g) * 0.05)
         r1 = A.inp("r1", torch.randn(mm, n, generator=g)) if res else None

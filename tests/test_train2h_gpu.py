@@ -83,7 +83,7 @@ def pack_pair(hip, A, w, fmt="fp16", fwd=True, bwd=True):
     return pf, pb
 
 
-def conv(hip, x, w, d, mode, backward=False, word_value=None):
+def conv(hip, x, w, d, mode, backward=False, word_value=None, geometry=0):
     """conv3x3 of the channels-last CPU map ``x`` with the CPU weight ``w`` (Cout, Cin, 3, 3) -- ``backward``: with its flipped,
     transposed image, the data gradient of a g = x -- through one entry: "scaled" (skd_conv3x3_split2h_scaled_nhwc with the device
     word of x, or the given word value), "unscaled" (skd_conv3x3_split2h_nhwc), "three" (skd_conv3x3_split_nhwc)."""
@@ -100,10 +100,10 @@ def conv(hip, x, w, d, mode, backward=False, word_value=None):
             word, _ = scale_word(hip, A, xa)
         else:
             word = A.inp("word", torch.tensor([word_value], dtype=torch.int64).to(torch.int32))
-        assert hip.skd_conv3x3_split2h_scaled_nhwc(b, h, ww, cin, cout, d, P(xa), P(pack), P(out), P(word), 0, None) == 1
+        assert hip.skd_conv3x3_split2h_scaled_nhwc(b, h, ww, cin, cout, d, P(xa), P(pack), P(out), P(word), geometry, None) == 1
     else:
         entry = hip.skd_conv3x3_split2h_nhwc if mode == "unscaled" else hip.skd_conv3x3_split_nhwc
-        assert entry(b, h, ww, cin, cout, d, P(xa), P(pack), P(out), None, None, None, None, None, 0.0, 0, 0.01, 0, None) == 1
+        assert entry(b, h, ww, cin, cout, d, P(xa), P(pack), P(out), None, None, None, None, None, 0.0, 0, 0.01, geometry, None) == 1
     A.check()
     return out.cpu().permute(0, 3, 1, 2)
 
@@ -310,6 +310,8 @@ def test_scale_invariance_on_the_device(hip, chans):
     x, w, g, _, _ = float_case(cin, cout, 2, 1.0)
     base_dx = conv(hip, g, w, 2, "scaled", backward=True)
     base_dw = {s: wgrad(hip, x, g, 2, s, "scaled") for s in T.WGRAD_SLICES}
+    for geometry in (1, 2, 3):                             # every forced tile height of the scaled entry (1 and 3: the tall tile) gives those bits
+        assert BC.same_bits(conv(hip, g, w, 2, "scaled", backward=True, geometry=geometry), base_dx), "data gradient, geometry %d" % geometry
     for j in (-40, -20, 20):
         up = 2.0 ** j
         assert BC.same_bits(conv(hip, cl(g * up), w, 2, "scaled", backward=True), base_dx * up), "data gradient, 2^%d" % j
