@@ -18,6 +18,7 @@ All are first-order only (``once_differentiable``), like the reference's native 
 derivatives of the discriminator's stock convolutions; the spectral-norm node is traversed once,
 by the final ``d_loss.backward()``.
 """
+import collections
 import ctypes
 
 import torch
@@ -31,6 +32,22 @@ def _f32c(t, what):
     if t.dtype != torch.float32:
         raise TypeError("%s: fp32 tensors only (got %s)" % (what, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
+
+
+_HEADER_OF = {name: header for header, table in _lib.ABI.items() for name in table}      # entry -> the header that declares it
+
+
+def _has(*names):
+    """Whether the active back-end provides every entry of ``names``."""
+    return all(_lib.has_entry(n) for n in names)
+
+
+def _need(*names):
+    """The one refusal of an op whose back-end lacks an extension entry: NotImplementedError naming the first entry of ``names``
+    that is missing and the header of include/ that declares it.  An op lists its entries in the order it uses them."""
+    for name in names:
+        if not _lib.has_entry(name):
+            raise NotImplementedError("the active back-end does not provide %s (include/%s)" % (name, _HEADER_OF[name]))
 
 
 class _PixelWise(Function):
@@ -105,11 +122,6 @@ def cross_entropy_dsn(logits_main, logits_dsn, target, ignore_index=255, aux_wei
     return _CrossEntropyDSN.apply(logits_main, logits_dsn, target, ignore_index, aux_weight)
 
 
-def _need_ohem_entry(name):
-    if not _lib.has_entry(name):
-        raise NotImplementedError("the active back-end does not provide %s (include/skd_ohem.h)" % name)
-
-
 def _ohem_inputs(logits_main, logits_dsn, target, factor, what):
     _lib.require_device(logits_main, logits_dsn, target)
     lm = _f32c(logits_main, what)
@@ -148,8 +160,7 @@ def _ohem_threshold(lib, lm, tg, ignore_index, thresh, min_kept, factor, ws, pre
 class _CrossEntropyOhemDSN(Function):
     @staticmethod
     def forward(ctx, logits_main, logits_dsn, target, ignore_index, thresh, min_kept, factor, aux_weight):
-        for name in ("skd_ce_ohem_workspace_floats", "skd_ohem_threshold", "skd_ce_ohem_dsn_forward"):
-            _need_ohem_entry(name)
+        _need("skd_ce_ohem_workspace_floats", "skd_ohem_threshold", "skd_ce_ohem_dsn_forward")
         lm, ld, tg, factor = _ohem_inputs(logits_main, logits_dsn, target, factor, "ce_ohem_dsn")
         if int(min_kept) < 0:
             raise ValueError("ce_ohem_dsn: min_kept >= 0 expected (got %d)" % int(min_kept))
@@ -193,8 +204,7 @@ def ohem_threshold(logits_main, target, ignore_index=255, thresh=0.7, min_kept=1
     """The OHEM threshold alone (OhemCrossEntropy2d.find_threshold on the up-sampled logits' softmax), without autograd:
     (threshold fp32 [], num_valid int32 []) device tensors, and with ``want_keys`` the (B, Hd, Wd) down-sampled label
     probabilities the selection ran on (-1 where the down-sampled label is ignored)."""
-    for name in ("skd_ce_ohem_workspace_floats", "skd_ohem_threshold"):
-        _need_ohem_entry(name)
+    _need("skd_ce_ohem_workspace_floats", "skd_ohem_threshold")
     lm, _, tg, factor = _ohem_inputs(logits_main.detach(), None, target, factor, "ohem_threshold")
     b, c, h, w = lm.shape
     H, W = tg.shape[1], tg.shape[2]
@@ -258,8 +268,7 @@ def drop_conv3x3_packs(owner):
     "pack3x3" / "pack3x3_2" / "pack3x3_2h" / "pack3x3_train"; the two-plane training pairs of include/skd_train2.h and
     skd_train2h.h and the narrow fp16 image of include/skd_infer2h.h too)."""
     slot = owner if isinstance(owner, dict) else vars(owner)
-    for attr in ("_skd_conv3x3_pack", _PACK2_ATTR, _PACK2H_ATTR, "_skd_conv3x3_train_pack", _TRAIN2_PACK_ATTR, _TRAIN2H_PACK_ATTR, "pack3x3", "pack3x3_2",
-                 "pack3x3_2h", "pack3x3_train", _NARROW2H_PACK_ATTR) + _NARROW_PACK_ATTRS:
+    for attr in _conv3x3_slots() + ("pack3x3", "pack3x3_2", "pack3x3_2h", "pack3x3_train"):
         slot.pop(attr, None)
 
 
@@ -480,7 +489,7 @@ def _ppm_fold_bottleneck(priors, feats, weight, cache=None, split3x3=False, spli
     `ppm_fold_bottleneck_fp16`: that convolution on two fp16 pieces (include/skd_split2h.h), its pack under a third key.
     `ppm_fold_bottleneck_train_fp16`: with `split_train`, the training form on two fp16 pieces (conv3x3_split_train_fp16,
     include/skd_train2h.h), its pack pair in a slot of its own; a frozen call is ppm_fold_bottleneck's."""
-    _check_piece_format(_check_pieces(pieces), piece_format)
+    check_pieces(pieces, piece_format)
     import torch.nn.functional as F
     cm = priors[0].shape[1]
     n_prior = len(priors) * cm
@@ -718,60 +727,38 @@ def abn_pack_eval_params(bn):
     return _cached(bn, "_skd_eval_pack", _version_key((bn.running_mean, bn.running_var, bn.weight, bn.bias), float(bn.eps)), build)[0]
 
 
-def _check_pieces(pieces):
-    """``pieces``: 3 (the six products of the three-piece split) or 2 (include/skd_split2.h: three products of two pieces)."""
-    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
-        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
-    return pieces
-
-
-def _need_split2_entry(name):
-    if not _lib.has_entry(name):
-        raise NotImplementedError("the active back-end does not provide %s (include/skd_split2.h)" % name)
-
-
-# include/skd_split2h.h: the two-piece form on FP16 pieces with the scaled residual, entry for entry the twin of skd_split2.h
-_SPLIT2H_ENTRIES = {"skd_conv3x3_split2_pack_bytes": "skd_conv3x3_split2h_pack_bytes",
-                    "skd_conv3x3_split2_pack_weights": "skd_conv3x3_split2h_pack_weights",
-                    "skd_conv3x3_split2_nhwc": "skd_conv3x3_split2h_nhwc",
-                    "skd_conv1x1_abn2_nhwc": "skd_conv1x1_abn2h_nhwc",
-                    "skd_conv1x1_abn2_pro_nhwc": "skd_conv1x1_abn2h_pro_nhwc"}
-
-
-def _check_piece_format(pieces, piece_format):
-    """``piece_format``: "bf16" (every form so far) or "fp16" (include/skd_split2h.h), which exists for ``pieces`` = 2 alone."""
+def check_piece_format(piece_format):
+    """``piece_format``: "bf16" (every form but these) or "fp16" (include/skd_split2h.h and its kin); ValueError otherwise."""
     if piece_format not in ("bf16", "fp16"):
         raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
-    if piece_format == "fp16" and pieces != 2:
-        raise ValueError("piece_format='fp16' requires pieces=2 (include/skd_split2h.h), not pieces=%r" % (pieces,))
     return piece_format
 
 
-def _split2_entry(name, piece_format):
-    """The two-piece entry ``name`` of include/skd_split2.h in ``piece_format``; NotImplementedError on a back-end without it."""
-    if piece_format == "fp16":
-        name = _SPLIT2H_ENTRIES[name]
-        if not _lib.has_entry(name):
-            raise NotImplementedError("the active back-end does not provide %s (include/skd_split2h.h)" % name)
-        return name
-    _need_split2_entry(name)
-    return name
+def check_pieces(pieces, piece_format="bf16"):
+    """The one validator of a ``(pieces, piece_format)`` pair, here and in networks.pspnet_combine: ``pieces`` is 3 (the six
+    products of the three-piece split) or 2 (three products of two pieces), ``piece_format`` "bf16" or "fp16", and fp16 pieces exist
+    for ``pieces`` = 2 alone.  Returns the pair; ValueError otherwise."""
+    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
+        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
+    if check_piece_format(piece_format) == "fp16" and pieces != 2:
+        raise ValueError("piece_format='fp16' requires pieces=2, not pieces=%r" % (pieces,))
+    return pieces, piece_format
 
+
+# (plain GEMM entry, entry with the ``pro`` prologue) of the fused 1x1 + eval-ABN GEMM per (pieces, piece_format): include/skd.h,
+# skd_split2.h, skd_split2h.h
+_CONV1X1_ABN = {(3, "bf16"): ("skd_conv1x1_abn_nhwc", "skd_conv1x1_abn_pro_nhwc"),
+                (2, "bf16"): ("skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn2_pro_nhwc"),
+                (2, "fp16"): ("skd_conv1x1_abn2h_nhwc", "skd_conv1x1_abn2h_pro_nhwc")}
 
 # include/skd_planes.h: piece planes -- an activation map as the three bf16 pieces the split core's consumer reads
-_PLANES_PRODUCER, _PLANES_CONSUMER = "skd_conv1x1_abn_planes_nhwc", "skd_conv3x3_split_planes_nhwc"
-_PLANES_ENTRIES = ("skd_planes_supported", "skd_planes_bytes", "skd_planes_offset", "skd_planes_split_nhwc", "skd_planes_join_nhwc",
-                   _PLANES_PRODUCER, _PLANES_CONSUMER)
+_PLANES_PRODUCER = "skd_conv1x1_abn_planes_nhwc"
+_PLANES_ENTRIES = tuple(_lib.ABI["skd_planes.h"])
 
 
 def planes_supported():
     """True when the active back-end has the seven entries of include/skd_planes.h (the tests' plain-C double has none)."""
-    return all(_lib.has_entry(n) for n in _PLANES_ENTRIES)
-
-
-def _need_planes():
-    if not planes_supported():
-        raise NotImplementedError("the active back-end does not provide the entries of include/skd_planes.h")
+    return _has(*_PLANES_ENTRIES)
 
 
 class Planes:
@@ -796,7 +783,7 @@ class Planes:
 
 def planes_bytes(m, c):
     """skd_planes_bytes(m, c): the allocation size of the planes of an (m, c) map; ValueError for sizes the kernels refuse."""
-    _need_planes()
+    _need(*_PLANES_ENTRIES)
     n = ctypes.c_int64(0)
     if not _lib.get().skd_planes_bytes(int(m), int(c), ctypes.cast(ctypes.byref(n), ctypes.c_void_p)):
         raise ValueError("piece planes: unsupported map of %d rows x %d channels (channels: a multiple of 16)" % (m, c))
@@ -813,7 +800,7 @@ def _new_planes(ref, b, h, w, c):
 def planes_split(x):
     """The piece planes of the fp32 channels-last map ``x`` (B, C, H, W), by the stand-alone kernel skd_planes_split_nhwc: for a
     map no producer wrote."""
-    _need_planes()
+    _need(*_PLANES_ENTRIES)
     _lib.require_device(x)
     if not _fp32_cl_map(x):
         raise ValueError("planes_split: an fp32 channels-last map is required")
@@ -825,7 +812,7 @@ def planes_split(x):
 
 def planes_join(planes):
     """The fp32 channels-last map (B, C, H, W) whose pieces ``planes`` holds, (p0 + p1) + p2: a debugging and test aid."""
-    _need_planes()
+    _need(*_PLANES_ENTRIES)
     b, h, w, c = planes.shape
     out = _new_cl(planes.data, b, c, h, w)
     _lib.check(_lib.get().skd_planes_join_nhwc(planes.M, c, planes.data.data_ptr(), out.data_ptr(), _lib.stream_of(planes.data)),
@@ -841,7 +828,7 @@ def conv1x1_abn_planes_eval(x, conv_weight, running_mean, running_var, weight, b
     call.)  Inference only; a back-end without the entries raises."""
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
         raise RuntimeError("conv1x1_abn_planes_eval is inference-only")
-    _need_planes()
+    _need(*_PLANES_ENTRIES)
     _lib.require_device(x, conv_weight, running_mean, running_var, weight, bias)
     b, k, h, w = x.shape
     n = conv_weight.shape[0]
@@ -874,8 +861,7 @@ def _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, e
     tests/split2h_ref.py is its model; an input beyond +-65504 gives NaN) -- an op of its own, not a keyword of this one, whose
     bound arguments are recorded call by call in tests/golden/routing_census.json.  ``conv1x1_abn_planes_eval`` is the same GEMM with its result written as bf16 piece planes
     (include/skd_planes.h)."""
-    pieces = _check_pieces(pieces)
-    piece_format = _check_piece_format(pieces, piece_format)
+    plain_entry, pro_entry = _CONV1X1_ABN[check_pieces(pieces, piece_format)]
     if torch.is_grad_enabled() and (x.requires_grad or conv_weight.requires_grad):
         raise RuntimeError("conv1x1_abn_eval is inference-only")
     _lib.require_device(x, conv_weight, running_mean, running_var, weight, bias, residual)
@@ -894,20 +880,16 @@ def _conv1x1_abn_eval(x, conv_weight, running_mean, running_var, weight, bias, e
         _lib.require_device(pro)
         if pro.dtype != torch.float32 or tuple(pro.shape) != (4, k) or not pro.is_contiguous():
             raise ValueError("pro must be the (4, Cin) fp32 pack of abn_pack_eval_params")
-        entry = "skd_conv1x1_abn_pro_nhwc" if pieces == 3 else "skd_conv1x1_abn2_pro_nhwc"
-        if pieces == 2:
-            entry = _split2_entry(entry, piece_format)
-        _lib.check(getattr(_lib.get(), entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
-                                              running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight),
-                                              _lib.ptr(bias), float(eps), pro.data_ptr(), act, float(slope),
-                                              _lib.stream_of(x)), entry)
+        _need(pro_entry)
+        _lib.check(getattr(_lib.get(), pro_entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
+                                                  running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight),
+                                                  _lib.ptr(bias), float(eps), pro.data_ptr(), act, float(slope),
+                                                  _lib.stream_of(x)), pro_entry)
         return out
-    entry = "skd_conv1x1_abn_nhwc" if pieces == 3 else "skd_conv1x1_abn2_nhwc"
-    if pieces == 2:
-        entry = _split2_entry(entry, piece_format)
-    _lib.check(getattr(_lib.get(), entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
-                                          running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
-                                          float(eps), act, float(slope), _lib.stream_of(x)), entry)
+    _need(plain_entry)
+    _lib.check(getattr(_lib.get(), plain_entry)(b * h * w, k, n, x.data_ptr(), wt.data_ptr(), _lib.ptr(residual), out.data_ptr(),
+                                                running_mean.data_ptr(), running_var.data_ptr(), _lib.ptr(weight), _lib.ptr(bias),
+                                                float(eps), act, float(slope), _lib.stream_of(x)), plain_entry)
     return out
 
 
@@ -934,6 +916,91 @@ def conv2d_square_geometry(conv):
     return None if s[0] != s[1] or p[0] != p[1] or d[0] != d[1] else (s[0], p[0], d[0])
 
 
+# ---- the forms of the split-core 3x3 kernel family (csrc/conv3x3.hip, csrc/conv3x3_wgrad.hip) ----
+# One row per (column width, pieces, piece format) that exists.  A row names every C entry, size query, cache slot and public
+# weight-gradient op of its form; None where the form has none -- which is how "statistics and the 64-column directions keep three
+# bf16 pieces" or "two bf16 pieces have no residual epilogue" is said.  Every entry name of the family is written here and nowhere
+# else; the ops below take a row and launch what it names.  ``wgrad_op`` is a NAME, looked up on this module when called: tests
+# and the routing census wrap the public ops.
+_Form = collections.namedtuple("_Form", (
+    "headers",          # the headers of include/ that declare the row's entries, the convolution entry's first
+    "query",            # geometry query of the frozen forward
+    "conv",             # the convolution entry: act(bn(conv3x3(x) + bias))
+    "res_arg",          # whether ``conv`` itself takes the residual pointer
+    "res",              # the entry with the residual epilogue, where it is a separate one
+    "planes",           # ``conv`` reading piece planes (include/skd_planes.h): dilation and geometry behind the epilogue
+    "s2_query", "s2",   # the stride-2 forward (no dilation argument) and its geometry query
+    "s2_pieces",        # whether ``s2`` takes the piece count (it then serves both bf16 piece counts)
+    "stats",            # the training forward that also writes the batch-norm statistics records
+    "scaled",           # the data gradient that takes the scale word of fp16_scale_word
+    "train_query",      # geometry query of forward + data gradient in training
+    "pack",             # writes the frozen weight image
+    "pack_pair",        # writes the forward image and / or the data gradient's in one launch
+    "bytes",            # size query of either image
+    "wgrad_query", "wgrad", "wgrad_op",      # the weight gradient: geometry query, (plan entry, launch entry), the public op's name
+    "pack_slot",        # cache slot of the frozen image
+    "train_slot",       # cache slot of the training pair
+    "packs_op",         # name of the public op that makes (and caches) the training pair
+    "mixed_slot",       # cache slot of this form's half of a pair whose other direction is on the other column width
+), defaults=(None,) * 22)
+
+_WIDE3 = _Form(
+    headers=("skd_eval.h", "skd_infer.h", "skd_planes.h", "skd_stride2.h", "skd_bnstats.h", "skd_train.h", "skd_wgrad.h"),
+    query="skd_conv3x3_split_supported", conv="skd_conv3x3_split_nhwc", res_arg=False, res="skd_conv3x3_split_res_nhwc",
+    planes="skd_conv3x3_split_planes_nhwc", s2_query="skd_conv3x3_split_s2_supported", s2="skd_conv3x3_split_s2_nhwc",
+    s2_pieces=True, stats="skd_conv3x3_split_stats_nhwc", train_query="skd_conv3x3_split_train_supported",
+    pack="skd_conv3x3_split_pack_weights", pack_pair="skd_conv3x3_split_pack_pair", bytes="skd_conv3x3_split_pack_bytes",
+    wgrad_query="skd_conv3x3_split_wgrad_supported", wgrad=("skd_conv3x3_split_wgrad_plan", "skd_conv3x3_split_wgrad_nhwc"),
+    wgrad_op="conv3x3_split_wgrad", pack_slot="_skd_conv3x3_pack", train_slot="_skd_conv3x3_train_pack",
+    packs_op="conv3x3_train_packs",     mixed_slot="_skd_conv3x3_train_pack_wide")
+# two bf16 pieces.  The geometry queries are the three-piece form's (the predicates ask _WIDE3), and so are the stride-2 entry, which
+# takes the piece count, and the weight gradient's query; no residual epilogue, no piece planes, no statistics.
+_WIDE2 = _Form(
+    headers=("skd_split2.h", "skd_stride2.h", "skd_train2.h", "skd_wgrad.h"),
+    conv="skd_conv3x3_split2_nhwc", res_arg=False, s2=_WIDE3.s2, s2_pieces=True, pack="skd_conv3x3_split2_pack_weights",
+    pack_pair="skd_conv3x3_split2_pack_pair", bytes="skd_conv3x3_split2_pack_bytes", wgrad_query=_WIDE3.wgrad_query,
+    wgrad=("skd_conv3x3_split2_wgrad_plan", "skd_conv3x3_split2_wgrad_nhwc"), wgrad_op="conv3x3_split_wgrad2",
+    pack_slot="_skd_conv3x3_pack2", train_slot="_skd_conv3x3_train_pack2", packs_op="conv3x3_train_packs2")
+# two fp16 pieces: a stride-2 entry of its own, without a piece count; a data gradient of its own, which takes the scale word; the
+# weight gradient has no query of its own and does not depend on skd_wgrad.h
+_WIDE2H = _Form(
+    headers=("skd_split2h.h", "skd_infer2h.h", "skd_train2h.h"),
+    conv="skd_conv3x3_split2h_nhwc", res_arg=False, res="skd_conv3x3_split2h_res_nhwc", s2="skd_conv3x3_split2h_s2_nhwc",
+    s2_pieces=False, scaled="skd_conv3x3_split2h_scaled_nhwc", pack="skd_conv3x3_split2h_pack_weights",
+    pack_pair="skd_conv3x3_split2h_pack_pair", bytes="skd_conv3x3_split2h_pack_bytes",
+    wgrad=("skd_conv3x3_split2h_wgrad_plan", "skd_conv3x3_split2h_wgrad_nhwc"), wgrad_op="conv3x3_split_wgrad_fp16",
+    pack_slot="_skd_conv3x3_pack2h", train_slot="_skd_conv3x3_train_pack2h", packs_op="conv3x3_train_packs_fp16")
+# the 64-column form: its one convolution entry takes the residual pointer, its pack-pair entry writes the frozen image too
+_NARROW3 = _Form(
+    headers=("skd_narrow.h", "skd_bnstats.h", "skd_narrow_wgrad.h"),
+    query="skd_conv3x3_narrow_supported", conv="skd_conv3x3_narrow_nhwc", res_arg=True, stats="skd_conv3x3_narrow_stats_nhwc",
+    pack_pair="skd_conv3x3_narrow_pack_pair", bytes="skd_conv3x3_narrow_pack_bytes",
+    wgrad_query="skd_conv3x3_narrow_wgrad_supported", wgrad=("skd_conv3x3_narrow_wgrad_plan", "skd_conv3x3_narrow_wgrad_nhwc"),
+    wgrad_op="conv3x3_narrow_wgrad", pack_slot="_skd_conv3x3_narrow_pack", train_slot="_skd_conv3x3_train_pack_narrow")
+_NARROW2H = _Form(
+    headers=("skd_infer2h.h",),
+    conv="skd_conv3x3_narrow2h_nhwc", res_arg=True, pack="skd_conv3x3_narrow2h_pack_weights",
+    bytes="skd_conv3x3_narrow2h_pack_bytes", pack_slot="_skd_conv3x3_narrow_pack2h")
+_FORMS = (_WIDE3, _WIDE2, _WIDE2H, _NARROW3, _NARROW2H)
+_WIDE = {(3, "bf16"): _WIDE3, (2, "bf16"): _WIDE2, (2, "fp16"): _WIDE2H}      # check_pieces' answer -> the wide form
+# the slots of the table under the names tests read them by
+_TRAIN2_PACK_ATTR, _TRAIN2H_PACK_ATTR = _WIDE2.train_slot, _WIDE2H.train_slot
+_NARROW_PACK_ATTRS = (_NARROW3.pack_slot, _WIDE3.mixed_slot, _NARROW3.train_slot)
+# what _Conv3x3SplitTrain runs: the rows of the forward and of the data gradient, the row whose weight-gradient op is asked for
+# (None: the library's), whether the forward also writes the statistics records
+_TrainForms = collections.namedtuple("_TrainForms", "fwd bwd wgrad stats")
+
+
+def _conv3x3_slots():
+    """Every cache slot a form names: what drop_conv3x3_packs forgets on a module."""
+    return tuple(s for form in _FORMS for s in (form.pack_slot, form.train_slot, form.mixed_slot) if s is not None)
+
+
+def _res_entry(form):
+    """The entry of ``form`` that takes the residual pointer: its convolution entry itself, or the separate one (None: none)."""
+    return form.conv if form.res_arg else form.res
+
+
 def _conv3x3_ok(x, weight, stride, padding, dilation, groups, grad, entries, query, host_ok):
     """The one predicate of the split-core 3x3 forms: grad is ``grad``, the back-end has every entry of ``entries``, ``x`` is an
     fp32 channels-last 16-byte-aligned device map (``host_ok``: a host one passes under a test double), ``weight`` a
@@ -957,8 +1024,12 @@ def _conv3x3_module_ok(x, conv, **form):
 
 # The frozen form refuses host tensors even under a test double: under the recording and computing doubles that is what keeps the
 # student's dsn[0] and PSP half on F.conv2d.
-_FROZEN = dict(grad=False, entries=("skd_conv3x3_split_nhwc",), query="skd_conv3x3_split_supported", host_ok=False)
-_TRAIN_ENTRIES = ("skd_conv3x3_split_train_supported", "skd_conv3x3_split_pack_pair", "skd_conv3x3_split_nhwc")
+_FROZEN = dict(grad=False, entries=(_WIDE3.conv,), query=_WIDE3.query, host_ok=False)
+_TRAIN_ENTRIES = (_WIDE3.train_query, _WIDE3.pack_pair, _WIDE3.conv)
+_NARROW_ENTRIES = (_NARROW3.query, _NARROW3.bytes, _NARROW3.pack_pair, _NARROW3.conv)
+_S2_ENTRIES = (_WIDE3.s2_query, _WIDE3.s2)
+_WGRAD_ENTRIES = (_WIDE3.wgrad_query,) + _WIDE3.wgrad
+_NARROW_WGRAD_ENTRIES = (_NARROW3.wgrad_query,) + _NARROW3.wgrad
 
 
 def conv3x3_split_supported(x, conv):
@@ -974,9 +1045,8 @@ def conv3x3_infer_supported(x, conv, residual=False):
     ``skd_conv3x3_split_res_nhwc`` (include/skd_infer.h) with ``residual``, ``skd_conv3x3_split_nhwc`` without.  A back-end
     without it (the tests' C double) answers False and the block runs the sequence it ran before.  Host tensors pass only
     under a test double, as in conv1x1_abn_supported."""
-    entry = "skd_conv3x3_split_res_nhwc" if residual else "skd_conv3x3_split_nhwc"
-    return _conv3x3_module_ok(x, conv, grad=False, entries=(entry, "skd_conv3x3_split_supported"),
-                              query="skd_conv3x3_split_supported", host_ok=True)
+    entry = _WIDE3.res if residual else _WIDE3.conv
+    return _conv3x3_module_ok(x, conv, grad=False, entries=(entry, _WIDE3.query), query=_WIDE3.query, host_ok=True)
 
 
 def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
@@ -987,10 +1057,10 @@ def conv3x3_train_supported(x, weight, stride, padding, dilation, groups):
     ungrouped, Cin and Cout multiples of 128.  ``weight`` may be any strided view.  Host tensors pass only under a test double,
     as in conv3x3_infer_supported."""
     return _conv3x3_ok(x, weight, stride, padding, dilation, groups, grad=True, entries=_TRAIN_ENTRIES,
-                       query="skd_conv3x3_split_train_supported", host_ok=True)
+                       query=_WIDE3.train_query, host_ok=True)
 
 
-def _conv3x3_packs(w, owner, attr, entry, what, images, bytes_entry="skd_conv3x3_split_pack_bytes"):
+def _conv3x3_packs(w, owner, attr, entry, what, images, bytes_entry):
     """The image(s) of the (Cout, Cin, 3, 3) weight ``w`` that csrc/conv3x3.hip streams into LDS, written by one launch of
     ``entry`` and cached on ``owner`` as ``(key, *packs, storage)`` with ``key = (data_ptr, _version, shape, stride)``.
     ``images`` has one flag per (pointer, bytes) pair that ``entry`` takes, forward image first: ``(True,)`` for
@@ -1025,17 +1095,13 @@ def _conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3, piece_format=
     ``conv3x3_split_eval(..., pieces=2)``; cached under the same rule in a slot of its own, so both packs of one module coexist.
     ``conv3x3_pack_weights_fp16``: the two fp16 planes of include/skd_split2h.h (p0 and the scaled p1, 4 bytes per weight
     again), in a third slot beside the other two."""
-    pieces = _check_pieces(pieces)
-    piece_format = _check_piece_format(pieces, piece_format)
+    form = _WIDE[check_pieces(pieces, piece_format)]
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_pack_weights is for frozen (no-grad) convolutions")
-    if pieces == 2:
-        pack_entry, bytes_entry = (_split2_entry(name, piece_format) for name in (_PACK2_ENTRY, _PACK2_BYTES))
-        return _conv3x3_packs(w, conv if owner is None else owner, _PACK2H_ATTR if piece_format == "fp16" else _PACK2_ATTR, pack_entry,
-                              "conv3x3_pack_weights", (True,), bytes_entry)[0]
-    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_pack", "skd_conv3x3_split_pack_weights",
-                          "conv3x3_pack_weights", (True,))[0]
+    _need(form.pack, form.bytes)
+    return _conv3x3_packs(w, conv if owner is None else owner, form.pack_slot, form.pack, "conv3x3_pack_weights", (True,),
+                          form.bytes)[0]
 
 
 def conv3x3_pack_weights(conv, weight=None, owner=None, pieces=3):
@@ -1051,20 +1117,14 @@ def conv3x3_pack_weights_fp16(conv, weight=None, owner=None):
 conv3x3_pack_weights.__doc__ = _conv3x3_pack_weights.__doc__
 
 
-# include/skd_train2.h: the two-piece forms of the training student's wide convolutions -- the pack pair, the weight gradient's
-# plan and launch -- and the slot the two-plane pair is cached in (its own: switching the piece count never serves the other image)
-_TRAIN2_PACK_PAIR, _TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD = ("skd_conv3x3_split2_pack_pair", "skd_conv3x3_split2_wgrad_plan",
-                                                        "skd_conv3x3_split2_wgrad_nhwc")
-_TRAIN2_PACK_ATTR = "_skd_conv3x3_train_pack2"
+def _conv3x3_train_packs(form, weight, owner, what="conv3x3_train_packs"):
+    """The ``(pack_fwd, pack_bwd)`` of ``form``: one launch of its pack-pair entry, cached in its training slot (each form its own:
+    switching the piece count or format never serves another form's image)."""
+    _need(form.pack_pair, form.bytes)
+    return _conv3x3_packs(weight, owner, form.train_slot, form.pack_pair, what, (True, True), form.bytes)
 
 
-def _need_train2_entry(name):
-    if not _lib.has_entry(name):
-        raise NotImplementedError("the active back-end does not provide %s (include/%s)"
-                                  % (name, "skd_train2.h" if name in _lib.ABI["skd_train2.h"] else "skd_split2.h"))
-
-
-def _conv3x3_train_packs(weight, owner=None, pieces=3):
+def conv3x3_train_packs(weight, owner=None):
     """``(pack_fwd, pack_bwd)`` of a trained (Cout, Cin, 3, 3) weight: the image csrc/conv3x3.hip streams for the forward
     convolution and the image of the flipped, transposed weight for its data gradient, written by ONE launch of
     skd_conv3x3_split_pack_pair under no_grad.  Cached on ``owner`` (a dict or any object that takes attributes; None: no cache)
@@ -1076,49 +1136,34 @@ def _conv3x3_train_packs(weight, owner=None, pieces=3):
     counts coexist on one owner and neither is ever served for the other.  A back-end without the entry raises
     NotImplementedError.  (A twin, not a ``pieces`` argument: tests/golden/routing_census.json records every call of the public
     conv3x3_* ops with its defaults filled in, so their signatures stay what they are -- as for the ``_fp16`` twins.)"""
-    if _check_pieces(pieces) == 2:
-        for name in (_TRAIN2_PACK_PAIR, _PACK2_BYTES):
-            _need_train2_entry(name)
-        return _conv3x3_packs(weight, owner, _TRAIN2_PACK_ATTR, _TRAIN2_PACK_PAIR, "conv3x3_train_packs", (True, True), _PACK2_BYTES)
-    return _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack", "skd_conv3x3_split_pack_pair", "conv3x3_train_packs",
-                          (True, True))
-
-
-def conv3x3_train_packs(weight, owner=None):
-    return _conv3x3_train_packs(weight, owner, 3)
+    return _conv3x3_train_packs(_WIDE3, weight, owner)
 
 
 def conv3x3_train_packs2(weight, owner=None):
     """``conv3x3_train_packs`` for ``conv3x3_split_train2``: the two-plane pair of include/skd_train2.h, in a slot of its own."""
-    return _conv3x3_train_packs(weight, owner, 2)
+    return _conv3x3_train_packs(_WIDE2, weight, owner)
 
 
-conv3x3_train_packs.__doc__ = _conv3x3_train_packs.__doc__
+# the two entries of include/skd_train2h.h that belong to no form: the scale word of a gradient tensor
+_SCALE_WORD = ("skd_fp16_scale_word_workspace_bytes", "skd_fp16_scale_word")
 
 
-# include/skd_train2h.h: the training student's wide convolutions on two FP16 pieces with a power-of-two scale per gradient tensor
-# -- the scale word, the fp16 pack pair, the scaled data gradient, the weight gradient's plan and launch -- and the slot the fp16
-# pair is cached in (its own again)
-_TRAIN2H_WORD_BYTES, _TRAIN2H_WORD = "skd_fp16_scale_word_workspace_bytes", "skd_fp16_scale_word"
-_TRAIN2H_PACK_PAIR, _TRAIN2H_SCALED = "skd_conv3x3_split2h_pack_pair", "skd_conv3x3_split2h_scaled_nhwc"
-_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD = "skd_conv3x3_split2h_wgrad_plan", "skd_conv3x3_split2h_wgrad_nhwc"
-_TRAIN2H_PACK_ATTR = "_skd_conv3x3_train_pack2h"
-_TRAIN2H_FWD, _TRAIN2H_PACK_BYTES = "skd_conv3x3_split2h_nhwc", "skd_conv3x3_split2h_pack_bytes"      # include/skd_split2h.h
-_TRAIN2H_ENTRIES = (_TRAIN2H_WORD_BYTES, _TRAIN2H_WORD, _TRAIN2H_PACK_PAIR, _TRAIN2H_SCALED, _TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD,
-                    _TRAIN2H_FWD, _TRAIN2H_PACK_BYTES)
+def split2_supported(piece_format="bf16"):
+    """True when the back-end has the five entries of the frozen two-piece forms in ``piece_format``: include/skd_split2.h for
+    "bf16", skd_split2h.h for "fp16" -- the 3x3 convolution, its pack entry and size query, and the two 1x1 GEMMs (the tests' C
+    double has none of them)."""
+    return _has(*_lib.ABI[_WIDE[2, check_piece_format(piece_format)].headers[0]])
 
 
-def _need_train2h_entry(*names):
-    for name in names:
-        if not _lib.has_entry(name):
-            header = "skd_train2h.h" if name in _lib.ABI["skd_train2h.h"] else "skd_split2h.h"
-            raise NotImplementedError("the active back-end does not provide %s (include/%s)" % (name, header))
+def train2_supported():
+    """True when the back-end has the three entries of include/skd_train2.h and the two of skd_split2.h they build on."""
+    return _has(*_lib.ABI["skd_train2.h"], _WIDE2.bytes, _WIDE2.conv)
 
 
 def train2h_supported():
     """True when the back-end has the six entries of include/skd_train2h.h and the two of skd_split2h.h they build on (the tests'
     C double has none of them)."""
-    return all(_lib.has_entry(n) for n in _TRAIN2H_ENTRIES)
+    return _has(*_lib.ABI["skd_train2h.h"], _WIDE2H.conv, _WIDE2H.bytes)
 
 
 def fp16_scale_word(g):
@@ -1126,7 +1171,7 @@ def fp16_scale_word(g):
     ``max(bits(g) & 0x7fffffff)``, from which the fp16 training kernels derive the power of two that puts ``g``'s largest magnitude
     into [2^14, 2^15).  At most two launches on ``g``'s stream, no host synchronisation, the same word on every call; an infinity
     or a NaN in ``g`` makes it >= 0x7f800000 (scale 1: a non-finite gradient stays loud)."""
-    _need_train2h_entry(_TRAIN2H_WORD_BYTES, _TRAIN2H_WORD)
+    _need(*_SCALE_WORD)
     _lib.require_device(g)
     if g.dtype != torch.float32 or g.numel() < 1 or not _non_overlapping_and_dense(g) or g.data_ptr() % 16:
         raise ValueError("fp16_scale_word: a dense, 16-byte aligned fp32 tensor of at least one element expected")
@@ -1135,7 +1180,7 @@ def fp16_scale_word(g):
     nbytes = int(lib.skd_fp16_scale_word_workspace_bytes(n))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=g.device)
     word = torch.empty((1,), dtype=torch.int32, device=g.device)
-    _lib.check(lib.skd_fp16_scale_word(n, g.data_ptr(), ws.data_ptr(), nbytes, word.data_ptr(), _lib.stream_of(g)), _TRAIN2H_WORD)
+    _lib.check(lib.skd_fp16_scale_word(n, g.data_ptr(), ws.data_ptr(), nbytes, word.data_ptr(), _lib.stream_of(g)), _SCALE_WORD[1])
     return word
 
 
@@ -1144,87 +1189,71 @@ def conv3x3_train_packs_fp16(weight, owner=None):
     (skd_conv3x3_split2h_pack_pair, 4 bytes per weight: p0 and the scaled p1 of skd_split2h.h) for the forward and for the data
     gradient, one launch, cached per ``(data_ptr, _version)`` in a slot of its own beside the bf16 pairs.  A back-end without
     the entry raises NotImplementedError."""
-    _need_train2h_entry(_TRAIN2H_PACK_PAIR, _TRAIN2H_PACK_BYTES)
-    return _conv3x3_packs(weight, owner, _TRAIN2H_PACK_ATTR, _TRAIN2H_PACK_PAIR, "conv3x3_train_packs_fp16", (True, True),
-                          _TRAIN2H_PACK_BYTES)
+    return _conv3x3_train_packs(_WIDE2H, weight, owner, "conv3x3_train_packs_fp16")
 
 
 _ACT = {"none": 0, "leaky_relu": 1, "relu": 3}      # SKD_ACT_* of include/skd.h
-_RES_ENTRY = "skd_conv3x3_split_res_nhwc"
-# include/skd_split2.h: the two-piece form of the frozen 128-column convolution, its pack entry, its size query, its cache slot
-_SPLIT2_ENTRY, _PACK2_ENTRY, _PACK2_BYTES = "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_pack_bytes"
-_PACK2_ATTR = "_skd_conv3x3_pack2"
-_SPLIT2H_ENTRY, _PACK2H_ATTR = _SPLIT2H_ENTRIES[_SPLIT2_ENTRY], "_skd_conv3x3_pack2h"      # include/skd_split2h.h: fp16 pieces
-# include/skd_narrow.h: the 64-column form of csrc/conv3x3.hip.  Its one convolution entry takes the residual pointer.
-_NARROW_ENTRY, _NARROW_PACK_PAIR = "skd_conv3x3_narrow_nhwc", "skd_conv3x3_narrow_pack_pair"
-_NARROW_ENTRIES = ("skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_pack_bytes", _NARROW_PACK_PAIR, _NARROW_ENTRY)
-_NARROW_PACK_ATTRS = ("_skd_conv3x3_narrow_pack", "_skd_conv3x3_train_pack_wide", "_skd_conv3x3_train_pack_narrow")
-# include/skd_infer2h.h: the residual-epilogue, 64-column and stride-2 forms on two fp16 pieces, the narrow form's pack entries
-# and its cache slot (its own, beside the three-piece one: neither image is ever served for the other)
-_RES2H_ENTRY, _NARROW2H_ENTRY, _S2H_ENTRY = "skd_conv3x3_split2h_res_nhwc", "skd_conv3x3_narrow2h_nhwc", "skd_conv3x3_split2h_s2_nhwc"
-_NARROW2H_PACK, _NARROW2H_BYTES = "skd_conv3x3_narrow2h_pack_weights", "skd_conv3x3_narrow2h_pack_bytes"
-_NARROW2H_PACK_ATTR = "_skd_conv3x3_narrow_pack2h"
-_INFER2H_ENTRIES = (_RES2H_ENTRY, _NARROW2H_BYTES, _NARROW2H_PACK, _NARROW2H_ENTRY, _S2H_ENTRY)
-# the size query of the weight image each convolution entry reads (skd_conv3x3_split_pack_bytes for the entries not named)
-_PACK_BYTES_OF = {_NARROW_ENTRY: "skd_conv3x3_narrow_pack_bytes", _NARROW2H_ENTRY: _NARROW2H_BYTES, _SPLIT2_ENTRY: _PACK2_BYTES,
-                  _SPLIT2H_ENTRY: _SPLIT2H_ENTRIES[_PACK2_BYTES], _RES2H_ENTRY: _SPLIT2H_ENTRIES[_PACK2_BYTES]}
-
-
-def _need_infer2h_entry(*names):
-    for name in names:
-        if not _lib.has_entry(name):
-            header = "skd_infer2h.h" if name in _lib.ABI["skd_infer2h.h"] else "skd_split2h.h"
-            raise NotImplementedError("the active back-end does not provide %s (include/%s)" % (name, header))
 
 
 def infer2h_supported():
     """True when the back-end has the five entries of include/skd_infer2h.h and the three of skd_split2h.h they build on (the
     tests' C double has none of them)."""
-    return all(_lib.has_entry(n) for n in _INFER2H_ENTRIES + tuple(_SPLIT2H_ENTRIES[k] for k in (_PACK2_BYTES, _PACK2_ENTRY, _SPLIT2_ENTRY)))
+    return _has(*_lib.ABI["skd_infer2h.h"], _WIDE2H.bytes, _WIDE2H.pack, _WIDE2H.conv)
 
 
-def _conv3x3_launch(entry, x, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0, residual=None):
-    """The one launcher of the split-core 3x3 forms: act(bn_running(conv3x3(x) + conv_bias) [+ residual]) by ``entry`` --
-    skd_conv3x3_split_nhwc, its two-piece twins skd_conv3x3_split2_nhwc / skd_conv3x3_split2h_nhwc, or skd_conv3x3_split_res_nhwc /
-    skd_conv3x3_narrow_nhwc and their fp16 twins of include/skd_infer2h.h, which take the ``residual`` pointer (None included)."""
+def _bn_epilogue(bn):
+    """``(mean, var, gamma, beta, eps, slope)`` of a launch's epilogue: the running statistics and affine parameters of the
+    eval-mode InPlace-ABN module ``bn``, or no normalisation for None."""
+    if bn is None:
+        return None, None, None, None, 0.0, 0.01
+    return bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
+
+
+def _conv3x3_begin(form, entry, src, dims, pack, cout, out_hw, *others):
+    """The host steps every launch of the family starts with: ``pack`` is the image ``form`` reads for a (cout, cin, 3, 3)
+    weight, every tensor is on the device, and the output is allocated -- (b, cout, *out_hw) fp32 channels-last on the device of
+    ``src``, the tensor the entry reads a ``dims = (b, cin, h, w)`` map from.  Returns ``(lib, out)``."""
     lib = _lib.get()
-    b, cin, h, w = x.shape
-    pack_bytes = getattr(lib, _PACK_BYTES_OF.get(entry, "skd_conv3x3_split_pack_bytes"))
-    if pack.numel() != pack_bytes(cin, cout):
+    b, cin = dims[:2]
+    if pack.numel() != getattr(lib, form.bytes)(cin, cout):
         raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
-    mean = var = gamma = beta = None
-    eps, slope = 0.0, 0.01
-    if bn is not None:
-        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
-    _lib.require_device(x, pack, residual, conv_bias, mean, var, gamma, beta)
+    _lib.require_device(src, pack, *others)
     # not a view (_new_cl's is one, with the same strides): the in-place ABN behind dsn[0] writes into a custom Function's output
-    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    res = (_lib.ptr(residual),) if entry in (_RES_ENTRY, _NARROW_ENTRY, _RES2H_ENTRY, _NARROW2H_ENTRY) else ()
+    out = torch.empty((b, cout) + tuple(out_hw), dtype=torch.float32, device=src.device, memory_format=torch.channels_last)
+    return lib, out
+
+
+def _conv3x3_launch(form, entry, x, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0, residual=None):
+    """The one launcher of the split-core 3x3 forms: act(bn_running(conv3x3(x) + conv_bias) [+ residual]) by ``entry``, the
+    convolution entry of ``form`` (a row of the table above) or its residual entry, which takes the ``residual`` pointer (None
+    included)."""
+    b, cin, h, w = x.shape
+    mean, var, gamma, beta, eps, slope = _bn_epilogue(bn)
+    lib, out = _conv3x3_begin(form, entry, x, x.shape, pack, cout, (h, w), residual, conv_bias, mean, var, gamma, beta)
+    res = (_lib.ptr(residual),) if entry == _res_entry(form) else ()
     _lib.check(getattr(lib, entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(), *res,
                                    _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
                                    _ACT[activation], slope, int(geometry), _lib.stream_of(x)), entry)
     return out
 
 
-def _conv3x3_planes_launch(planes, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0):
-    """_conv3x3_launch for skd_conv3x3_split_planes_nhwc (include/skd_planes.h): the input is a ``Planes``; the entry takes
+def _conv3x3_raw_launch(form, x, pack, cout, dilation, conv_bias=None):
+    """conv3x3(x) + conv_bias on ``form``, raw (no normalisation, no activation): what training runs in both directions."""
+    return _conv3x3_launch(form, form.conv, x, pack, cout, dilation, conv_bias)
+
+
+def _conv3x3_planes_launch(form, planes, pack, cout, dilation, conv_bias=None, bn=None, activation="none", geometry=0):
+    """_conv3x3_launch for the piece-plane entry of ``form`` (include/skd_planes.h): the input is a ``Planes``; the entry takes
     dilation and geometry behind the epilogue arguments."""
-    lib = _lib.get()
     b, h, w, cin = planes.shape
-    if pack.numel() != lib.skd_conv3x3_split_pack_bytes(cin, cout):
-        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (_PLANES_CONSUMER, cout, cin))
     if planes.data.numel() != planes_bytes(planes.M, cin) or planes.M != b * h * w:
-        raise ValueError("%s: the planes are not those of a %s map" % (_PLANES_CONSUMER, (planes.shape,)))
-    mean = var = gamma = beta = None
-    eps, slope = 0.0, 0.01
-    if bn is not None:
-        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
-    _lib.require_device(planes.data, pack, conv_bias, mean, var, gamma, beta)
-    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=planes.device, memory_format=torch.channels_last)
-    _lib.check(getattr(lib, _PLANES_CONSUMER)(b, h, w, cin, cout, planes.data.data_ptr(), pack.data_ptr(), out.data_ptr(),
-                                              _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
-                                              _ACT[activation], slope, int(dilation), int(geometry), _lib.stream_of(planes.data)),
-               _PLANES_CONSUMER)
+        raise ValueError("%s: the planes are not those of a %s map" % (form.planes, (planes.shape,)))
+    mean, var, gamma, beta, eps, slope = _bn_epilogue(bn)
+    lib, out = _conv3x3_begin(form, form.planes, planes.data, (b, cin, h, w), pack, cout, (h, w), conv_bias, mean, var, gamma, beta)
+    _lib.check(getattr(lib, form.planes)(b, h, w, cin, cout, planes.data.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                         _lib.ptr(conv_bias), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps,
+                                         _ACT[activation], slope, int(dilation), int(geometry), _lib.stream_of(planes.data)),
+               form.planes)
     return out
 
 
@@ -1254,18 +1283,16 @@ def _conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, acti
     (tests/split2h_ref.py); an input beyond +-65504 gives NaN.
     ``x`` may be a ``Planes`` (include/skd_planes.h; three pieces only): the kernel loads the pieces instead of cutting the
     fp32 map (skd_conv3x3_split_planes_nhwc), and the result is bit for bit that of the call on the fp32 map."""
-    pieces = _check_pieces(pieces)
-    piece_format = _check_piece_format(pieces, piece_format)
+    form = _WIDE[check_pieces(pieces, piece_format)]
     if isinstance(x, Planes):
-        if pieces != 3:
+        if form.planes is None:
             raise ValueError("conv3x3_split_eval: piece planes hold three pieces")
-        _need_planes()
-        return _conv3x3_planes_launch(x, pack, cout, dilation, conv_bias, bn, activation, geometry)
+        _need(*_PLANES_ENTRIES)
+        return _conv3x3_planes_launch(form, x, pack, cout, dilation, conv_bias, bn, activation, geometry)
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_split_eval is inference-only")
-    if pieces == 2:
-        return _conv3x3_launch(_split2_entry(_SPLIT2_ENTRY, piece_format), x, pack, cout, dilation, conv_bias, bn, activation, geometry)
-    return _conv3x3_launch("skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias, bn, activation, geometry)
+    _need(form.conv)
+    return _conv3x3_launch(form, form.conv, x, pack, cout, dilation, conv_bias, bn, activation, geometry)
 
 
 def conv3x3_split_eval(x, pack, cout, dilation=1, conv_bias=None, bn=None, activation="none", geometry=0, pieces=3):
@@ -1281,6 +1308,15 @@ def conv3x3_split_eval_fp16(x, pack, cout, dilation=1, conv_bias=None, bn=None, 
 conv3x3_split_eval.__doc__ = _conv3x3_split_eval.__doc__
 
 
+def _conv3x3_res_eval(form, what, x, pack, cout, dilation, residual, bn, activation, conv_bias, geometry):
+    """The body of the four inference ops with a residual epilogue: the op ``what`` on the residual-taking entry of ``form``."""
+    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
+        raise RuntimeError("%s is inference-only" % what)
+    entry = _res_entry(form)
+    _need(entry, form.bytes)
+    return _conv3x3_launch(form, entry, x, pack, cout, dilation, conv_bias, bn, activation, geometry, _residual_cl(x, cout, residual))
+
+
 def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, conv_bias=None, geometry=0):
     """act(bn_running(conv3x3(x) + conv_bias) + residual) in one launch of csrc/conv3x3.hip (include/skd_infer.h; inference
     only): conv3x3_split_eval with the residual added in the epilogue, behind the normalisation and in front of the activation
@@ -1288,12 +1324,7 @@ def conv3x3_split_res_eval(x, pack, cout, dilation, residual, bn, activation, co
     eval-mode InPlace-ABN module or None, ``residual`` (B, cout, H, W) fp32, read in channels-last memory (copied when it is
     not) and never written; ``residual=None`` is conv3x3_split_eval bit for bit.  The numerics of the convolution are those of
     conv3x3_split_eval; the residual add is one more fp32 rounding."""
-    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
-        raise RuntimeError("conv3x3_split_res_eval is inference-only")
-    if not _lib.has_entry(_RES_ENTRY):
-        raise NotImplementedError("this back-end has no skd_conv3x3_split_res_nhwc (include/skd_infer.h)")
-    return _conv3x3_launch(_RES_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
-                           _residual_cl(x, cout, residual))
+    return _conv3x3_res_eval(_WIDE3, "conv3x3_split_res_eval", x, pack, cout, dilation, residual, bn, activation, conv_bias, geometry)
 
 
 def conv3x3_split_res_eval_fp16(x, pack, cout, dilation, residual, bn, activation, conv_bias=None, geometry=0):
@@ -1303,50 +1334,30 @@ def conv3x3_split_res_eval_fp16(x, pack, cout, dilation, residual, bn, activatio
     the convolution are those of include/skd_split2h.h (tests/split2h_ref.py); an input beyond +-65504 gives non-finite outputs.
     An op of its own, not a keyword: tests/golden/routing_census.json records every public conv3x3_* call with its defaults.
     Never downgraded: a back-end without the entry raises NotImplementedError."""
-    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
-        raise RuntimeError("conv3x3_split_res_eval_fp16 is inference-only")
-    _need_infer2h_entry(_RES2H_ENTRY, _SPLIT2H_ENTRIES[_PACK2_BYTES])
-    return _conv3x3_launch(_RES2H_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
-                           _residual_cl(x, cout, residual))
-
-
-def _conv3x3_split_launch(x, pack, cout, dilation, conv_bias=None, pieces=3):
-    """conv3x3(x) + conv_bias on the split core, raw (no normalisation, no activation): one launch of skd_conv3x3_split_nhwc, or
-    -- ``pieces`` = 2, ``pack`` a two-plane image -- of skd_conv3x3_split2_nhwc."""
-    return _conv3x3_launch(_SPLIT2_ENTRY if pieces == 2 else "skd_conv3x3_split_nhwc", x, pack, cout, dilation, conv_bias)
-
-
-def _conv3x3_narrow_launch(x, pack, cout, dilation, conv_bias=None):
-    """The same on the 64-column form, for a pack of skd_conv3x3_narrow_pack_pair: one launch of skd_conv3x3_narrow_nhwc."""
-    return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias)
+    return _conv3x3_res_eval(_WIDE2H, "conv3x3_split_res_eval_fp16", x, pack, cout, dilation, residual, bn, activation, conv_bias,
+                             geometry)
 
 
 # include/skd_bnstats.h: the training forward that also emits the batch-norm statistics records of its output, and their finalize
-_BNSTATS_ENTRIES = ("skd_conv3x3_bnstats_floats", "skd_conv3x3_split_stats_nhwc", "skd_conv3x3_narrow_stats_nhwc",
-                    "skd_abn_stats_from_partials_nhwc")
+_BNSTATS_ENTRIES = tuple(_lib.ABI["skd_bnstats.h"])
 
 
 def conv3x3_bnstats_supported():
     """True when the back-end has the four entries of include/skd_bnstats.h (the tests' C double does not: conv3x3_split_train is
     then not asked for statistics and the ABN forward behind it runs what it ran before)."""
-    return all(_lib.has_entry(n) for n in _BNSTATS_ENTRIES)
+    return _has(*_BNSTATS_ENTRIES)
 
 
-def _conv3x3_stats_launch(narrow, x, pack, cout, dilation, conv_bias=None):
-    """``(conv3x3(x) + conv_bias, partials)``: _conv3x3_split_launch / _conv3x3_narrow_launch by the entry of include/skd_bnstats.h
-    that writes the same bits and, from its epilogue, one (mean, M2) per 32-row block and channel of the output into ``partials``
+def _conv3x3_stats_launch(form, x, pack, cout, dilation, conv_bias=None):
+    """``(conv3x3(x) + conv_bias, partials)``: the raw _conv3x3_launch of ``form`` by its entry of include/skd_bnstats.h, which
+    writes the same bits and, from its epilogue, one (mean, M2) per 32-row block and channel of the output into ``partials``
     (fp32, skd_conv3x3_bnstats_floats long, every element written)."""
-    lib = _lib.get()
-    entry = "skd_conv3x3_narrow_stats_nhwc" if narrow else "skd_conv3x3_split_stats_nhwc"
     b, cin, h, w = x.shape
-    if pack.numel() != (lib.skd_conv3x3_narrow_pack_bytes if narrow else lib.skd_conv3x3_split_pack_bytes)(cin, cout):
-        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (entry, cout, cin))
-    _lib.require_device(x, pack, conv_bias)
-    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    lib, out = _conv3x3_begin(form, form.stats, x, x.shape, pack, cout, (h, w), conv_bias)
     n = int(lib.skd_conv3x3_bnstats_floats(b * h * w, cout))
     partials = torch.empty((max(n, 1),), dtype=torch.float32, device=x.device)
-    _lib.check(getattr(lib, entry)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
-                                   _lib.ptr(conv_bias), 0, partials.data_ptr(), n, _lib.stream_of(x)), entry)
+    _lib.check(getattr(lib, form.stats)(b, h, w, cin, cout, int(dilation), x.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                        _lib.ptr(conv_bias), 0, partials.data_ptr(), n, _lib.stream_of(x)), form.stats)
     return out, partials
 
 
@@ -1356,7 +1367,7 @@ def conv3x3_narrow_supported(x, conv, residual=False):
     what they ran before), an fp32 channels-last 16-byte-aligned input, a plain 3x3 / stride-1 / padding == dilation / ungrouped
     convolution with Cin a multiple of 16 and Cout of 64.  ``residual``: the one entry takes it, so the answer is the same.
     Host tensors pass only under a test double, as in conv3x3_infer_supported."""
-    return _conv3x3_module_ok(x, conv, grad=False, entries=_NARROW_ENTRIES, query="skd_conv3x3_narrow_supported", host_ok=True)
+    return _conv3x3_module_ok(x, conv, grad=False, entries=_NARROW_ENTRIES, query=_NARROW3.query, host_ok=True)
 
 
 def conv3x3_narrow_pack_weights(conv, weight=None, owner=None):
@@ -1366,8 +1377,8 @@ def conv3x3_narrow_pack_weights(conv, weight=None, owner=None):
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_narrow_pack_weights is for frozen (no-grad) convolutions")
-    return _conv3x3_packs(w, conv if owner is None else owner, "_skd_conv3x3_narrow_pack", _NARROW_PACK_PAIR,
-                          "conv3x3_narrow_pack_weights", (True, False), "skd_conv3x3_narrow_pack_bytes")[0]
+    return _conv3x3_packs(w, conv if owner is None else owner, _NARROW3.pack_slot, _NARROW3.pack_pair,
+                          "conv3x3_narrow_pack_weights", (True, False), _NARROW3.bytes)[0]
 
 
 def conv3x3_narrow_eval(x, pack, cout, dilation, residual=None, conv_bias=None, bn=None, activation="none", geometry=0):
@@ -1375,12 +1386,7 @@ def conv3x3_narrow_eval(x, pack, cout, dilation, residual=None, conv_bias=None, 
     only), with ``pack = conv3x3_narrow_pack_weights(...)``: conv3x3_split_eval / conv3x3_split_res_eval for a Cout that is a
     multiple of 64.  The arithmetic of every output element is that of the 128-column form, in its order: where both take a
     convolution they give the same bits.  ``residual`` (B, cout, H, W) fp32 is read in channels-last memory (copied when it is not) and never written."""
-    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
-        raise RuntimeError("conv3x3_narrow_eval is inference-only")
-    if not _lib.has_entry(_NARROW_ENTRY):
-        raise NotImplementedError("this back-end has no skd_conv3x3_narrow_nhwc (include/skd_narrow.h)")
-    return _conv3x3_launch(_NARROW_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
-                           _residual_cl(x, cout, residual))
+    return _conv3x3_res_eval(_NARROW3, "conv3x3_narrow_eval", x, pack, cout, dilation, residual, bn, activation, conv_bias, geometry)
 
 
 def conv3x3_narrow_pack_weights_fp16(conv, weight=None, owner=None):
@@ -1391,9 +1397,9 @@ def conv3x3_narrow_pack_weights_fp16(conv, weight=None, owner=None):
     w = conv.weight if weight is None else weight
     if torch.is_grad_enabled() and w.requires_grad:
         raise RuntimeError("conv3x3_narrow_pack_weights_fp16 is for frozen (no-grad) convolutions")
-    _need_infer2h_entry(_NARROW2H_PACK, _NARROW2H_BYTES)
-    return _conv3x3_packs(w, conv if owner is None else owner, _NARROW2H_PACK_ATTR, _NARROW2H_PACK,
-                          "conv3x3_narrow_pack_weights_fp16", (True,), _NARROW2H_BYTES)[0]
+    _need(_NARROW2H.pack, _NARROW2H.bytes)
+    return _conv3x3_packs(w, conv if owner is None else owner, _NARROW2H.pack_slot, _NARROW2H.pack,
+                          "conv3x3_narrow_pack_weights_fp16", (True,), _NARROW2H.bytes)[0]
 
 
 def conv3x3_narrow_eval_fp16(x, pack, cout, dilation, residual=None, conv_bias=None, bn=None, activation="none", geometry=0):
@@ -1401,16 +1407,8 @@ def conv3x3_narrow_eval_fp16(x, pack, cout, dilation, residual=None, conv_bias=N
     ``pack = conv3x3_narrow_pack_weights_fp16(...)``: the same arguments; at a Cout both forms take it gives the bits of
     conv3x3_split_eval_fp16 / conv3x3_split_res_eval_fp16.  Never downgraded: a back-end without the entry raises
     NotImplementedError."""
-    if torch.is_grad_enabled() and (x.requires_grad or (residual is not None and residual.requires_grad)):
-        raise RuntimeError("conv3x3_narrow_eval_fp16 is inference-only")
-    _need_infer2h_entry(_NARROW2H_ENTRY, _NARROW2H_BYTES)
-    return _conv3x3_launch(_NARROW2H_ENTRY, x, pack, cout, dilation, conv_bias, bn, activation, geometry,
-                           _residual_cl(x, cout, residual))
-
-
-# include/skd_stride2.h: the stride-2 frozen forward of the 128-column family (csrc/conv3x3.hip with STRIDE = 2)
-_S2_ENTRY = "skd_conv3x3_split_s2_nhwc"
-_S2_ENTRIES = ("skd_conv3x3_split_s2_supported", _S2_ENTRY)
+    return _conv3x3_res_eval(_NARROW2H, "conv3x3_narrow_eval_fp16", x, pack, cout, dilation, residual, bn, activation, conv_bias,
+                             geometry)
 
 
 def conv3x3_s2_supported(x, conv):
@@ -1418,7 +1416,7 @@ def conv3x3_s2_supported(x, conv):
     of a frozen forward: no grad, a back-end that has the entries (the tests' C double does not: callers then run what they ran
     before), an fp32 channels-last 16-byte-aligned input, a plain 3x3 / stride-2 / padding-1 / dilation-1 / ungrouped convolution
     with Cin a multiple of 16 and Cout of 128.  Host tensors pass only under a test double, as in conv3x3_infer_supported."""
-    return _conv3x3_module_ok(x, conv, grad=False, entries=_S2_ENTRIES, query="skd_conv3x3_split_s2_supported", host_ok=True)
+    return _conv3x3_module_ok(x, conv, grad=False, entries=_S2_ENTRIES, query=_WIDE3.s2_query, host_ok=True)
 
 
 def _conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", pieces=3, piece_format="bf16"):
@@ -1430,34 +1428,19 @@ def _conv3x3_s2_eval(x, pack, cout, conv_bias=None, bn=None, activation="none", 
     piece count.  ``activation``: 'none' or 'relu'.  A back-end without the entry raises; the call is never downgraded.
     ``conv3x3_s2_eval_fp16`` is the form of include/skd_infer2h.h with ``pack = conv3x3_pack_weights_fp16(conv)``: two fp16
     pieces, scaled residual, conv3x3_split_eval_fp16's output at the even pixels bit for bit."""
-    pieces = _check_pieces(pieces)
-    fp16 = _check_piece_format(pieces, piece_format) == "fp16"
-    entry = _S2H_ENTRY if fp16 else _S2_ENTRY
+    form = _WIDE[check_pieces(pieces, piece_format)]
     if activation not in ("none", "relu"):
         raise ValueError("conv3x3_s2_eval: activation must be 'none' or 'relu', not %r" % (activation,))
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("conv3x3_s2_eval is inference-only")
-    if fp16:
-        _need_infer2h_entry(_S2H_ENTRY, _SPLIT2H_ENTRIES[_PACK2_BYTES])
-    elif not _lib.has_entry(_S2_ENTRY):
-        raise NotImplementedError("this back-end has no %s (include/skd_stride2.h)" % _S2_ENTRY)
-    lib = _lib.get()
+    _need(form.s2, form.bytes)
     b, cin, h, w = x.shape
-    if pieces == 2 and not fp16:
-        _need_split2_entry(_PACK2_BYTES)
-    bytes_entry = _SPLIT2H_ENTRIES[_PACK2_BYTES] if fp16 else _PACK2_BYTES if pieces == 2 else "skd_conv3x3_split_pack_bytes"
-    if pack.numel() != getattr(lib, bytes_entry)(cin, cout):
-        raise ValueError("%s: the pack is not the %d-piece image of a (%d, %d, 3, 3) weight" % (entry, pieces, cout, cin))
-    mean = var = gamma = beta = None
-    eps, slope = 0.0, 0.01
-    if bn is not None:
-        mean, var, gamma, beta, eps, slope = bn.running_mean, bn.running_var, bn.weight, bn.bias, float(bn.eps), float(bn.slope)
-    _lib.require_device(x, pack, conv_bias, mean, var, gamma, beta)
-    out = torch.empty((b, cout, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device,
-                      memory_format=torch.channels_last)
-    _lib.check(getattr(lib, entry)(b, h, w, cin, cout, x.data_ptr(), pack.data_ptr(), out.data_ptr(), _lib.ptr(conv_bias),
-                                   _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, _ACT[activation], slope,
-                                   *(() if fp16 else (pieces,)), 0, _lib.stream_of(x)), entry)      # the fp16 twin takes no piece count
+    mean, var, gamma, beta, eps, slope = _bn_epilogue(bn)
+    lib, out = _conv3x3_begin(form, form.s2, x, x.shape, pack, cout, ((h - 1) // 2 + 1, (w - 1) // 2 + 1), conv_bias, mean, var,
+                              gamma, beta)
+    _lib.check(getattr(lib, form.s2)(b, h, w, cin, cout, x.data_ptr(), pack.data_ptr(), out.data_ptr(), _lib.ptr(conv_bias),
+                                     _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), eps, _ACT[activation], slope,
+                                     *((pieces,) if form.s2_pieces else ()), 0, _lib.stream_of(x)), form.s2)
     return out
 
 
@@ -1479,29 +1462,28 @@ def conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups)
     conv3x3_train_supported asks, except that each direction need only fit the wide form OR the narrow one -- Cin and Cout
     multiples of 64 -- and the back-end has the entries of include/skd_narrow.h as well."""
     return (_conv3x3_ok(x, weight, stride, padding, dilation, groups, grad=True, entries=_TRAIN_ENTRIES + _NARROW_ENTRIES,
-                        query="skd_conv3x3_narrow_supported", host_ok=True)
-            and bool(_lib.get().skd_conv3x3_narrow_supported(int(weight.shape[0]), int(weight.shape[1]), int(stride), int(padding),
-                                                             int(dilation), int(groups))))
+                        query=_NARROW3.query, host_ok=True)
+            and bool(getattr(_lib.get(), _NARROW3.query)(int(weight.shape[0]), int(weight.shape[1]), int(stride), int(padding),
+                                                         int(dilation), int(groups))))
 
 
 def _conv3x3_narrow_train_packs(weight, owner):
-    """``(pack_fwd, pack_bwd, fwd_narrow, bwd_narrow)`` of a trained weight whose directions are chosen by their N -- Cout for the
-    forward, Cin for the data gradient: the wide image for a multiple of 128, the narrow one otherwise.  One launch per entry
-    that has an image to write, each cached in a slot of its own; both wide is conv3x3_train_packs."""
+    """``(pack_fwd, pack_bwd, fwd_form, bwd_form)`` of a trained weight whose directions are chosen by their N -- Cout for the
+    forward, Cin for the data gradient: _WIDE3 and its image for a multiple of 128, _NARROW3 and its image otherwise.  One launch
+    per entry that has an image to write, each cached in a slot of its own; both wide is conv3x3_train_packs."""
     cout, cin = int(weight.shape[0]), int(weight.shape[1])
     narrow = (cout % 128 != 0, cin % 128 != 0)
+    forms = tuple(_NARROW3 if n else _WIDE3 for n in narrow)
     if not any(narrow):
-        return conv3x3_train_packs(weight, owner) + narrow
+        return conv3x3_train_packs(weight, owner) + forms
     wide = (None, None)
     if not all(narrow):
-        wide = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_wide", "skd_conv3x3_split_pack_pair", "conv3x3_split_train",
-                              (not narrow[0], not narrow[1]))
-    thin = _conv3x3_packs(weight, owner, "_skd_conv3x3_train_pack_narrow", _NARROW_PACK_PAIR, "conv3x3_split_train", narrow,
-                          "skd_conv3x3_narrow_pack_bytes")
-    return tuple(t if n else v for t, v, n in zip(thin, wide, narrow)) + narrow
+        wide = _conv3x3_packs(weight, owner, _WIDE3.mixed_slot, _WIDE3.pack_pair, "conv3x3_split_train",
+                              (not narrow[0], not narrow[1]), _WIDE3.bytes)
+    thin = _conv3x3_packs(weight, owner, _NARROW3.train_slot, _NARROW3.pack_pair, "conv3x3_split_train", narrow, _NARROW3.bytes)
+    return tuple(t if n else v for t, v, n in zip(thin, wide, narrow)) + forms
 
 
-_WGRAD_ENTRIES = ("skd_conv3x3_split_wgrad_supported", "skd_conv3x3_split_wgrad_plan", "skd_conv3x3_split_wgrad_nhwc")
 _device_cus = {}
 
 
@@ -1509,9 +1491,9 @@ def conv3x3_wgrad_supported(x, weight, stride, padding, dilation, groups):
     """True when conv3x3_split_wgrad takes the weight gradient of ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)``:
     a back-end that has the three entries of include/skd_wgrad.h (the tests' C double does not: the gradient then comes from the
     library, as before) and everything conv3x3_train_supported asks."""
-    return (all(_lib.has_entry(n) for n in _WGRAD_ENTRIES) and conv3x3_train_supported(x, weight, stride, padding, dilation, groups)
-            and bool(_lib.get().skd_conv3x3_split_wgrad_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride),
-                                                                  int(padding), int(dilation), int(groups))))
+    return (_has(*_WGRAD_ENTRIES) and conv3x3_train_supported(x, weight, stride, padding, dilation, groups)
+            and bool(getattr(_lib.get(), _WIDE3.wgrad_query)(int(weight.shape[1]), int(weight.shape[0]), int(stride),
+                                                             int(padding), int(dilation), int(groups))))
 
 
 def _cus_of(device):
@@ -1534,10 +1516,12 @@ def _non_overlapping_and_dense(t):
     return True
 
 
-def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilation, slices, word=()):
-    """The body conv3x3_split_wgrad and conv3x3_narrow_wgrad share: the checks, the plan call, the workspace, the layout of ``dw``
-    and the launch entry, on the pair of entries ``plan_entry`` / ``run_entry`` (skd_wgrad.h or skd_narrow_wgrad.h).  ``word``:
-    ``(pointer,)`` for the entry of skd_train2h.h, which takes the scale word of ``g`` in front of the slice count."""
+def _conv3x3_wgrad_launch(form, what, x, g, weight_like, dilation, slices, word=()):
+    """The body the four weight-gradient ops share: the checks, the plan call, the workspace, the layout of ``dw`` and the launch
+    entry, on the plan / launch pair of ``form``; a back-end without the pair raises.  ``word``: ``(pointer,)`` for the form whose
+    entry takes the scale word of ``g`` in front of the slice count (skd_train2h.h)."""
+    plan_entry, run_entry = form.wgrad
+    _need(plan_entry, run_entry)
     _lib.require_device(x, g)
     lib = _lib.get()
     b, cin, h, w = (int(v) for v in x.shape)
@@ -1560,7 +1544,7 @@ def _conv3x3_wgrad_launch(what, plan_entry, run_entry, x, g, weight_like, dilati
     return dw
 
 
-def _conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0, pieces=3):
+def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
     """The weight gradient of the same-size 3x3 convolution ``F.conv2d(x, w, None, 1, dilation, dilation)`` for the output gradient
     ``g``, on the split core (csrc/conv3x3_wgrad.hip: both operands split in the loop, split-K over the pixels into a workspace,
     a second launch that sums the slices in a fixed order -- the same bits on every call).  ``x`` (B, Cin, H, W) and ``g``
@@ -1570,24 +1554,13 @@ def _conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0, pieces=3):
     ``conv3x3_split_wgrad2``: the two-piece form of include/skd_train2.h -- both operands cut into two bf16 pieces, three
     products, the same plan, workspace and slice sum (the numerics of conv3x3_split_eval's ``pieces=2``).  A back-end without
     the entries raises NotImplementedError."""
-    if _check_pieces(pieces) == 2:
-        for name in (_TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD):
-            _need_train2_entry(name)
-        return _conv3x3_wgrad_launch("conv3x3_split_wgrad", _TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD, x, g, weight_like, dilation, slices)
-    return _conv3x3_wgrad_launch("conv3x3_split_wgrad", _WGRAD_ENTRIES[1], _WGRAD_ENTRIES[2], x, g, weight_like, dilation, slices)
-
-
-def conv3x3_split_wgrad(x, g, weight_like, dilation, slices=0):
-    return _conv3x3_split_wgrad(x, g, weight_like, dilation, slices, 3)
+    return _conv3x3_wgrad_launch(_WIDE3, "conv3x3_split_wgrad", x, g, weight_like, dilation, slices)
 
 
 def conv3x3_split_wgrad2(x, g, weight_like, dilation, slices=0):
     """``conv3x3_split_wgrad`` on two bf16 pieces per operand and three products (include/skd_train2.h): the same arguments, the
     same plan and result layout."""
-    return _conv3x3_split_wgrad(x, g, weight_like, dilation, slices, 2)
-
-
-conv3x3_split_wgrad.__doc__ = _conv3x3_split_wgrad.__doc__
+    return _conv3x3_wgrad_launch(_WIDE2, "conv3x3_split_wgrad", x, g, weight_like, dilation, slices)
 
 
 def _check_word(word, like):
@@ -1602,118 +1575,91 @@ def conv3x3_split_wgrad_fp16(x, g, weight_like, dilation, slices=0, word=None):
     ``x`` is not scaled and keeps skd_split2h.h's loud contract (|x| > 65504 gives NaN).  ``word=None``: scale 1 -- gradients
     below fp16's range are then lost, so a caller passes the word.  The same plan, workspace, slice sum and result layout; 22
     significant bits per operand.  A back-end without the entries raises NotImplementedError."""
-    _need_train2h_entry(_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD)
     _lib.require_device(_check_word(word, g))
-    return _conv3x3_wgrad_launch("conv3x3_split_wgrad_fp16", _TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD, x, g, weight_like, dilation, slices,
-                                 (_lib.ptr(word),))
+    return _conv3x3_wgrad_launch(_WIDE2H, "conv3x3_split_wgrad_fp16", x, g, weight_like, dilation, slices, (_lib.ptr(word),))
 
 
-def _conv3x3_scaled_launch(g, pack, cout, dilation, word):
-    """conv3x3(g) on the fp16 image ``pack`` with ``g`` scaled by its ``word`` (skd_conv3x3_split2h_scaled_nhwc): the data gradient
-    of include/skd_train2h.h, one launch, raw."""
-    lib = _lib.get()
+def _conv3x3_scaled_launch(g, pack, cout, dilation, word, form=_WIDE2H):
+    """conv3x3(g) on the image ``pack`` of ``form`` with ``g`` scaled by its ``word``, by the form's scaled entry: the data gradient
+    of include/skd_train2h.h (the one form that has such an entry), one launch, raw."""
     b, cin, h, w = g.shape
-    if pack.numel() != lib.skd_conv3x3_split2h_pack_bytes(cin, cout):
-        raise ValueError("%s: the pack is not that of a (%d, %d, 3, 3) weight" % (_TRAIN2H_SCALED, cout, cin))
-    _lib.require_device(g, pack, _check_word(word, g))
-    out = torch.empty((b, cout, h, w), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
-    _lib.check(lib.skd_conv3x3_split2h_scaled_nhwc(b, h, w, cin, cout, int(dilation), g.data_ptr(), pack.data_ptr(), out.data_ptr(),
-                                                   word.data_ptr(), 0, _lib.stream_of(g)), _TRAIN2H_SCALED)
+    lib, out = _conv3x3_begin(form, form.scaled, g, g.shape, pack, cout, (h, w), _check_word(word, g))
+    _lib.check(getattr(lib, form.scaled)(b, h, w, cin, cout, int(dilation), g.data_ptr(), pack.data_ptr(), out.data_ptr(),
+                                         word.data_ptr(), 0, _lib.stream_of(g)), form.scaled)
     return out
-
-
-_NARROW_WGRAD_ENTRIES = ("skd_conv3x3_narrow_wgrad_supported", "skd_conv3x3_narrow_wgrad_plan", "skd_conv3x3_narrow_wgrad_nhwc")
 
 
 def conv3x3_narrow_wgrad_supported(x, weight, stride, padding, dilation, groups):
     """True when conv3x3_narrow_wgrad takes the weight gradient of ``F.conv2d(x, weight, bias, stride, padding, dilation, groups)``:
     a back-end that has the three entries of include/skd_narrow_wgrad.h (the tests' C double does not: the gradient then comes from
     the library, as before), everything conv3x3_narrow_train_supported asks, and Cin and Cout multiples of 64."""
-    return (all(_lib.has_entry(n) for n in _NARROW_WGRAD_ENTRIES)
+    return (_has(*_NARROW_WGRAD_ENTRIES)
             and conv3x3_narrow_train_supported(x, weight, stride, padding, dilation, groups)
-            and bool(_lib.get().skd_conv3x3_narrow_wgrad_supported(int(weight.shape[1]), int(weight.shape[0]), int(stride),
-                                                                   int(padding), int(dilation), int(groups))))
+            and bool(getattr(_lib.get(), _NARROW3.wgrad_query)(int(weight.shape[1]), int(weight.shape[0]), int(stride),
+                                                               int(padding), int(dilation), int(groups))))
 
 
 def conv3x3_narrow_wgrad(x, g, weight_like, dilation, slices=0):
     """conv3x3_split_wgrad for channel counts that are multiples of 64: the 128 x 64 tile form of the same kernel
     (csrc/conv3x3_wgrad.hip, include/skd_narrow_wgrad.h) -- the same arguments, the same result layout, the same numerics; for a
     shape both take and the same slice count, the same bits."""
-    return _conv3x3_wgrad_launch("conv3x3_narrow_wgrad", _NARROW_WGRAD_ENTRIES[1], _NARROW_WGRAD_ENTRIES[2], x, g, weight_like,
-                                 dilation, slices)
+    return _conv3x3_wgrad_launch(_NARROW3, "conv3x3_narrow_wgrad", x, g, weight_like, dilation, slices)
 
 
 class _Conv3x3SplitTrain(Function):
     """A same-size 3x3 convolution of a network in training, both directions on csrc/conv3x3.hip: the forward on ``pack_fwd``, the
     data gradient -- the same kind of convolution of the output gradient with the flipped, transposed weight -- on the
     ``pack_bwd`` THIS forward was given (kept in ctx: an optimizer step in between changes the cache, not this node).  The
-    weight gradient (and the bias gradient) are the library's, as before -- with ``wgrad`` the weight gradient is
-    conv3x3_split_wgrad's where the back-end has its entries, and the library computes the bias gradient alone; ``"narrow"`` in
-    its place (conv3x3_split_train's ``narrow_wgrad``) asks for conv3x3_narrow_wgrad's in the same way.  A fourth optional argument
-    (conv3x3_split_train's ``stats``) makes the forward return ``(y, partials)`` -- the same ``y`` and the statistics records of
-    include/skd_bnstats.h, marked non-differentiable; the backward is the same.  A fifth (2, from conv3x3_split_train2) is the
-    piece count of the wide form's products: the packs are two-plane images, forward and data gradient run
-    skd_conv3x3_split2_nhwc and ``wgrad`` is conv3x3_split_wgrad2's (include/skd_train2.h).  "fp16" in its place (from
-    conv3x3_split_train_fp16; include/skd_train2h.h): the packs are the fp16 pair, the forward runs skd_conv3x3_split2h_nhwc, and the
-    backward computes the scale word of ``g`` ONCE and hands it to the scaled data gradient and to conv3x3_split_wgrad_fp16."""
+    weight gradient (and the bias gradient) are the library's, as before.  ``cfg`` (a _TrainForms) says the rest: ``cfg.fwd`` and
+    ``cfg.bwd`` are the table rows of the forward and of the data gradient -- chosen per direction by conv3x3_split_train's
+    ``narrow``, two-plane images and two-piece entries from conv3x3_split_train2, the fp16 pair from conv3x3_split_train_fp16,
+    whose row has a scaled data gradient: the backward then computes the scale word of ``g`` ONCE and hands it to that entry and
+    to the weight gradient.  ``cfg.wgrad``: the row whose public weight-gradient op computes ``dw`` where the back-end has that
+    op's entries (the library then computes the bias gradient alone), or None.  ``cfg.stats`` makes the forward return
+    ``(y, partials)`` -- the same ``y`` and the statistics records of include/skd_bnstats.h, marked non-differentiable; the
+    backward is the same."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, *wgrad):
+    def forward(ctx, x, weight, bias, dilation, pack_fwd, pack_bwd, cfg):
         _lib.require_device(x, weight, bias, pack_fwd, pack_bwd)
         ctx.save_for_backward(x, weight)
-        ctx.pack_bwd, ctx.dilation, ctx.has_bias = pack_bwd, int(dilation), bias is not None
-        ctx.wgrad, ctx.n_inputs = bool(wgrad and wgrad[0]), 6 + len(wgrad)
-        ctx.narrow_wgrad = bool(wgrad) and wgrad[0] == "narrow"
-        # (forward?, backward?) on the narrow entry: the third optional argument (conv3x3_split_train's ``narrow``)
-        fwd_narrow, ctx.bwd_narrow = wgrad[1] if len(wgrad) > 1 else (False, False)
-        ctx.two = two = dict(pieces=2) if len(wgrad) > 3 and wgrad[3] == 2 else {}      # the keyword only where it says 2
-        ctx.fp16 = len(wgrad) > 3 and wgrad[3] == "fp16"
-        if ctx.fp16:
-            return _conv3x3_launch(_TRAIN2H_FWD, x, pack_fwd, int(weight.shape[0]), dilation, bias)
-        if len(wgrad) > 2 and wgrad[2]:
-            y, partials = _conv3x3_stats_launch(fwd_narrow, x, pack_fwd, int(weight.shape[0]), dilation, bias)
+        ctx.pack_bwd, ctx.dilation, ctx.has_bias, ctx.cfg = pack_bwd, int(dilation), bias is not None, cfg
+        if cfg.stats:
+            y, partials = _conv3x3_stats_launch(cfg.fwd, x, pack_fwd, int(weight.shape[0]), dilation, bias)
             ctx.mark_non_differentiable(partials)
             return y, partials
-        if fwd_narrow:
-            return _conv3x3_narrow_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias)
-        return _conv3x3_split_launch(x, pack_fwd, int(weight.shape[0]), dilation, bias, **two)
+        return _conv3x3_raw_launch(cfg.fwd, x, pack_fwd, int(weight.shape[0]), dilation, bias)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *_partials_grad):
         x, weight = ctx.saved_tensors         # a weight written since the forward raises autograd's version error here
-        d = ctx.dilation
+        d, bwd, wg = ctx.dilation, ctx.cfg.bwd, ctx.cfg.wgrad
         g = _cl(g.to(torch.float32))
         if g.data_ptr() % 16:
             g = g.clone(memory_format=torch.channels_last)
         dx = dw = db = None
-        # (the entries the branch below launches: the fp16 form does not depend on skd_wgrad.h)
-        wgrad_entries = ((_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD) if ctx.fp16 else _NARROW_WGRAD_ENTRIES if ctx.narrow_wgrad
-                         else _WGRAD_ENTRIES)
-        split_w = ctx.wgrad and ctx.needs_input_grad[1] and all(_lib.has_entry(n) for n in wgrad_entries)
-        # fp16 pieces: ONE scale word of g for both gradient products
-        word = fp16_scale_word(g) if ctx.fp16 and (ctx.needs_input_grad[0] or split_w) else None
+        # (the entries of the op launched below: its geometry query where it has one, its plan and launch entries)
+        split_w = (wg is not None and ctx.needs_input_grad[1]
+                   and _has(*((wg.wgrad_query,) if wg.wgrad_query else ()), *wg.wgrad))
+        # a form with a scaled entry: ONE scale word of g for both gradient products
+        scaled_w = split_w and wg.scaled is not None
+        word = fp16_scale_word(g) if (ctx.needs_input_grad[0] and bwd.scaled) or scaled_w else None
         if ctx.needs_input_grad[0]:
-            if ctx.fp16:
-                dx = _conv3x3_scaled_launch(g, ctx.pack_bwd, int(weight.shape[1]), d, word)
-            elif ctx.bwd_narrow:
-                dx = _conv3x3_narrow_launch(g, ctx.pack_bwd, int(weight.shape[1]), d)
+            if bwd.scaled:
+                dx = _conv3x3_scaled_launch(g, ctx.pack_bwd, int(weight.shape[1]), d, word, bwd)
             else:
-                dx = _conv3x3_split_launch(g, ctx.pack_bwd, int(weight.shape[1]), d, **ctx.two)
+                dx = _conv3x3_raw_launch(bwd, g, ctx.pack_bwd, int(weight.shape[1]), d)
         need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         if split_w:
-            if ctx.fp16:
-                dw = conv3x3_split_wgrad_fp16(x, g, weight, d, word=word)
-            elif ctx.narrow_wgrad:
-                dw = conv3x3_narrow_wgrad(x, g, weight, d)
-            else:
-                dw = (conv3x3_split_wgrad2 if ctx.two else conv3x3_split_wgrad)(x, g, weight, d)
+            # (the public op, by its name on this module at call time)
+            dw = globals()[wg.wgrad_op](x, g, weight, d, **(dict(word=word) if scaled_w else {}))
             need_w = False
         if need_w or need_b:
             _, lw, db = torch.ops.aten.convolution_backward(g, x, weight, [int(weight.shape[0])] if ctx.has_bias else None,
                                                             [1, 1], [d, d], [d, d], False, [0, 0], 1, (False, need_w, need_b))
             dw, db = lw if need_w else dw, db if need_b else None
-        return (dx, dw, db) + (None,) * (ctx.n_inputs - 3)
+        return dx, dw, db, None, None, None, None      # dilation, the two packs and cfg take no gradient
 
 
 def _conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False,
@@ -1740,27 +1686,27 @@ def _conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=Fa
     cached apart from the three-piece pair.  A direction ``narrow`` puts on the 64-column form and a call with
     ``stats`` have no two-piece form: they keep three pieces.  The library's weight gradient (``wgrad=False``) and the bias gradient
     are what they were.  A back-end without the entries raises NotImplementedError."""
-    pieces = _check_pieces(pieces)
-    if stats and not conv3x3_bnstats_supported():
-        raise NotImplementedError("this back-end has no include/skd_bnstats.h entries")
-    if pieces == 2:
-        for name in (_TRAIN2_PACK_PAIR, _SPLIT2_ENTRY, _PACK2_BYTES) + ((_TRAIN2_WGRAD_PLAN, _TRAIN2_WGRAD) if wgrad else ()):
-            _need_train2_entry(name)
-    if narrow:
-        pack_fwd, pack_bwd, fwd_narrow, bwd_narrow = _conv3x3_narrow_train_packs(weight, owner)
-        if fwd_narrow or bwd_narrow:
-            tail = (True,) if stats else ()
-            return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, "narrow" if narrow_wgrad else False,
-                                            (fwd_narrow, bwd_narrow), *tail)
-    if pieces == 2 and not stats:
-        pack_fwd, pack_bwd = conv3x3_train_packs2(weight, owner)
-        return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), False, 2)
-    pack_fwd, pack_bwd = conv3x3_train_packs(weight, owner)
+    form = _WIDE[check_pieces(pieces)]
     if stats:
-        return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), True)
-    if wgrad:
-        return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, True)
-    return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd)
+        _need(*_BNSTATS_ENTRIES)
+    if form is not _WIDE3:      # never downgraded -- while a three-piece call without skd_wgrad.h leaves the weight gradient on the library
+        _need(form.pack_pair, form.conv, form.bytes, *(form.wgrad if wgrad else ()))
+    if narrow:
+        pack_fwd, pack_bwd, fwd, bwd = _conv3x3_narrow_train_packs(weight, owner)
+        if _NARROW3 in (fwd, bwd):
+            return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd,
+                                            _TrainForms(fwd, bwd, _NARROW3 if narrow_wgrad else None, bool(stats)))
+    if stats and form.stats is None:
+        form = _WIDE3
+    return _conv3x3_train_apply(form, x, weight, dilation, bias, owner, wgrad, stats)
+
+
+def _conv3x3_train_apply(form, x, weight, dilation, bias, owner, wgrad, stats=False):
+    """_Conv3x3SplitTrain with both directions on the wide ``form``, its pack pair from the form's public pack op (by its name on
+    this module at call time)."""
+    pack_fwd, pack_bwd = globals()[form.packs_op](weight, owner)
+    return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd,
+                                    _TrainForms(form, form, form if wgrad else None, bool(stats)))
 
 
 def conv3x3_split_train(x, weight, dilation, bias=None, owner=None, *, wgrad=False, narrow=False, narrow_wgrad=False, stats=False):
@@ -1787,14 +1733,13 @@ def conv3x3_split_train_fp16(x, weight, dilation, bias=None, owner=None, *, wgra
     non-finite.  A direction ``narrow`` puts on the 64-column form and a call with ``stats`` have no fp16 form: they keep three
     bf16 pieces, as under conv3x3_split_train2.  The library's weight gradient (``wgrad=False``) and the bias gradient are what
     they were.  A back-end without the entries raises NotImplementedError."""
-    _need_train2h_entry(_TRAIN2H_PACK_PAIR, _TRAIN2H_PACK_BYTES, _TRAIN2H_FWD, _TRAIN2H_WORD_BYTES, _TRAIN2H_WORD, _TRAIN2H_SCALED,
-                        *((_TRAIN2H_WGRAD_PLAN, _TRAIN2H_WGRAD) if wgrad else ()))
+    form = _WIDE2H
+    _need(form.pack_pair, form.bytes, form.conv, *_SCALE_WORD, form.scaled, *(form.wgrad if wgrad else ()))
     # (a 64-channel side, decided from the shape as _conv3x3_narrow_train_packs decides it, in front of any pack launch)
     if stats or (narrow and (int(weight.shape[0]) % 128 != 0 or int(weight.shape[1]) % 128 != 0)):
         return _conv3x3_split_train(x, weight, dilation, bias, owner, wgrad=wgrad, narrow=narrow, narrow_wgrad=narrow_wgrad,
                                     stats=stats)
-    pack_fwd, pack_bwd = conv3x3_train_packs_fp16(weight, owner)
-    return _Conv3x3SplitTrain.apply(x, weight, bias, int(dilation), pack_fwd, pack_bwd, bool(wgrad), (False, False), False, "fp16")
+    return _conv3x3_train_apply(form, x, weight, dilation, bias, owner, wgrad)
 
 
 # ---- the training student's 1x1 down-sample (shortcut) convolutions on the split core (include/skd_shortcut.h) ----
@@ -1964,8 +1909,7 @@ def seg_sliding(logits, tiles, tile_size, out_size, target=None, ignore_index=25
     ``tiles``: a host sequence of 4-tuples (checked, then uploaded) or a (T, 4) int32 tensor on the logits' device.
     Returns (pred (H, W) uint8 or None, probs (H, W, C) float64 or None, confusion [None without target and confusion])."""
     _lib.require_device(logits, target, confusion, remap)
-    if not _lib.has_entry("skd_seg_sliding"):
-        raise NotImplementedError("the active back-end does not provide skd_seg_sliding (include/skd_eval.h)")
+    _need("skd_seg_sliding")
     lg = _f32c(logits.detach(), "seg_sliding")
     if lg.dim() != 4:
         raise ValueError("seg_sliding: logits (T, C, h, w) expected (got %s)" % (tuple(lg.shape),))
@@ -2010,11 +1954,6 @@ def seg_sliding(logits, tiles, tile_size, out_size, target=None, ignore_index=25
     return pred, probs, confusion
 
 
-def _require_ms_entry(name):
-    if not _lib.has_entry(name):
-        raise NotImplementedError("the active back-end does not provide %s (include/skd_eval_ms.h)" % name)
-
-
 def zoom_size(n, scale):
     """Output length of ``scipy.ndimage.zoom`` for an axis of ``n`` at ``scale``: Python's ``round``, half to even
     (30 x 0.75 = 22.5 gives 22, 50 x 0.75 = 37.5 gives 38)."""
@@ -2027,7 +1966,7 @@ def zoom_linear(image, scale, mirror=False, channels_last=False):
     where the last coordinate rounds above ``n - 1``.  ``image``: (1, C, H, W) or (C, H, W) fp32.  Returns (F, C, Ho, Wo) with
     F = 1 + mirror; element 1 is element 0 mirrored in X.  ``channels_last``: the result has channels-last memory."""
     _lib.require_device(image)
-    _require_ms_entry("skd_zoom_linear")
+    _need("skd_zoom_linear")
     img = _f32c(image.detach(), "zoom_linear")
     if img.dim() == 4 and img.shape[0] == 1:
         img = img[0]
@@ -2055,7 +1994,7 @@ def seg_multiscale(logits, out_size, target=None, ignore_index=255, confusion=No
     Returns (pred (H, W) uint8 or None, probs (H, W, C) float64 or None, confusion [None without target and confusion])."""
     logits = list(logits)
     _lib.require_device(target, confusion, remap, *logits)
-    _require_ms_entry("skd_seg_multiscale")
+    _need("skd_seg_multiscale")
     if not logits:
         raise ValueError("seg_multiscale: at least one scale expected")
     maps = [_f32c(lg.detach(), "seg_multiscale") for lg in logits]

@@ -94,8 +94,6 @@ WGRAD_ROUTING_EXCLUDED = frozenset()
 # Measured on the MI355X at batch 8, 65 x 65: all seven shapes are ahead -- forward + data gradient + pack pair 1.57 - 1.67 x, the
 # weight gradient 1.35 - 1.48 x, spreads of at most 3.2 % -- so the set is empty and the weight gradient needs no set of its own.
 STUDENT_PIECES_ROUTING_EXCLUDED = frozenset()
-_TRAIN2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_nhwc", "skd_conv3x3_split2_pack_pair",
-                   "skd_conv3x3_split2_wgrad_plan", "skd_conv3x3_split2_wgrad_nhwc")
 # The same 13 convolutions on two FP16 pieces per operand with a power-of-two scale per gradient tensor
 # (route_training_convs(pieces=2, piece_format="fp16"); NOT an accuracy trade: include/skd_train2h.h): forward on
 # skd_conv3x3_split2h_nhwc, data gradient and -- with ``wgrad`` -- weight gradient on the scaled entries.  A shape that does not
@@ -197,10 +195,6 @@ PLANES_ROUTING_EXCLUDED = frozenset({(512, 256, 2), (1024, 256, 2), (1024, 512, 
 INFER2H_ROUTING_EXCLUDED = frozenset()
 _TEACHER_EARLY_ENTRIES = ("skd_conv3x3_split_s2_supported", "skd_conv3x3_split_s2_nhwc", "skd_conv3x3_split_supported",
                           "skd_conv3x3_split_nhwc", "skd_conv3x3_narrow_supported", "skd_conv3x3_narrow_nhwc")
-_SPLIT2_ENTRIES = ("skd_conv3x3_split2_pack_bytes", "skd_conv3x3_split2_pack_weights", "skd_conv3x3_split2_nhwc",
-                   "skd_conv1x1_abn2_nhwc", "skd_conv1x1_abn2_pro_nhwc")
-_SPLIT2H_ENTRIES = ("skd_conv3x3_split2h_pack_bytes", "skd_conv3x3_split2h_pack_weights", "skd_conv3x3_split2h_nhwc",
-                    "skd_conv1x1_abn2h_nhwc", "skd_conv1x1_abn2h_pro_nhwc")
 
 
 def _piece_route(module, *shape, fp16_form=True):
@@ -302,7 +296,7 @@ def _student_pieces(module, cin, cout, dilation):
     back-end has the entries of include/skd_train2.h (and the two of skd_split2.h they build on) and the shape is outside
     STUDENT_PIECES_ROUTING_EXCLUDED; 3 otherwise."""
     if (getattr(module, "_skd_train_pieces", 3) == 2 and (cin, cout, dilation) not in STUDENT_PIECES_ROUTING_EXCLUDED
-            and all(_lib.has_entry(n) for n in _TRAIN2_ENTRIES)):
+            and SF.train2_supported()):
         return 2
     return 3
 
@@ -902,8 +896,7 @@ def fuse_for_inference(model, enable=True, min_cin=FUSED_EVAL_MIN_CIN, narrow=Fa
     (RuntimeWarning, naming skd_infer2h.h) and the student stays on three pieces.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag
     is set and changes nothing."""
-    if piece_format not in ("bf16", "fp16"):
-        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
+    SF.check_piece_format(piece_format)
     if enable and piece_format == "fp16" and not SF.infer2h_supported():
         import warnings
         warnings.warn("fuse_for_inference: this back-end lacks the fp16 two-piece entries (include/skd_infer2h.h); the student "
@@ -1013,17 +1006,11 @@ def set_teacher_pieces(model, pieces=2, piece_format="bf16"):
     ValueError, not a silent three-piece run.
     ``pieces=3`` clears the marks and drops the two-plane packs of both formats.  On a back-end without the entries ``pieces=2``
     warns (RuntimeWarning) and leaves three pieces."""
-    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
-        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
-    if piece_format not in ("bf16", "fp16"):
-        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
-    if piece_format == "fp16" and pieces != 2:
-        raise ValueError("piece_format='fp16' requires pieces=2, not pieces=%r" % (pieces,))
-    entries, header = (_SPLIT2H_ENTRIES, "include/skd_split2h.h") if piece_format == "fp16" else (_SPLIT2_ENTRIES, "include/skd_split2.h")
-    if pieces == 2 and not all(_lib.has_entry(n) for n in entries):
+    SF.check_pieces(pieces, piece_format)
+    if pieces == 2 and not SF.split2_supported(piece_format):
         import warnings
-        warnings.warn("set_teacher_pieces: this back-end lacks the two-piece entries (%s); the teacher stays on "
-                      "three pieces" % header, RuntimeWarning, stacklevel=2)
+        warnings.warn("set_teacher_pieces: this back-end lacks the two-piece entries (include/%s); the teacher stays on "
+                      "three pieces" % ("skd_split2h.h" if piece_format == "fp16" else "skd_split2.h"), RuntimeWarning, stacklevel=2)
         pieces = 3
     teacher = any(isinstance(m, Bottleneck) for m in model.modules())      # a BasicBlock network (the student) is left untouched
     for m in model.modules():
@@ -1100,12 +1087,7 @@ def route_training_convs(model, enable=True, min_cin=TRAIN_SPLIT_MIN_CIN, wgrad=
     changes nothing.
     ``enable=False`` clears the flags and drops the packs.  On a back-end without the entries (the tests' C double) the flag is
     set and changes nothing."""
-    if type(pieces) is not int or pieces not in (2, 3):      # 2.0, True, "2": anything but the integers 2 and 3
-        raise ValueError("pieces must be 2 or 3, not %r" % (pieces,))
-    if piece_format not in ("bf16", "fp16"):
-        raise ValueError("piece_format must be 'bf16' or 'fp16', not %r" % (piece_format,))
-    if piece_format == "fp16" and pieces != 2:
-        raise ValueError("piece_format='fp16' requires pieces=2 (include/skd_train2h.h), not pieces=%r" % (pieces,))
+    SF.check_pieces(pieces, piece_format)
     fp16 = bool(enable) and piece_format == "fp16"
     if fp16 and not SF.train2h_supported():
         import warnings

@@ -129,6 +129,76 @@ def test_predicate_table(form):
             assert not ask(x, conv)
 
 
+def _row_entries(form):
+    """{field: entry} of every C entry a row of functional's form table names (the weight gradient's pair under two keys)."""
+    named = {f: v for f, v in zip(form._fields, form) if isinstance(v, str) and not f.endswith(("_slot", "_op"))}
+    if form.wgrad is not None:
+        named["wgrad_plan"], named["wgrad_run"] = form.wgrad
+    return named
+
+
+def test_form_table_names_real_entries_of_one_signature_per_kind():
+    """What the single launcher of functional.py rests on.  Every entry a row names is in _lib.ABI under one of the headers the
+    row states (and every stated header declares one); the rows' entries of one kind have ONE C signature, up to the three
+    differences the launch code handles and this test spells out: the residual pointer, the scale word, the stride-2 piece
+    count; and drop_conv3x3_packs forgets every slot a row names."""
+    P, I, L = _lib._P, _lib._I, _lib._L
+    assert len(SF._FORMS) == 5 and set(SF._WIDE.values()) == set(SF._FORMS[:3])
+    for form in SF._FORMS:
+        named = _row_entries(form)
+        for field, entry in named.items():
+            assert any(entry in _lib.ABI[h] for h in form.headers), (field, entry, form.headers)
+        assert all(any(e in _lib.ABI[h] for e in named.values()) for h in form.headers), form.headers
+        assert named["conv"] in _lib.ABI[form.headers[0]], "the convolution entry's header comes first"
+        for op in (form.wgrad_op, form.packs_op):
+            assert op is None or callable(getattr(SF, op))
+
+    def sigs(kind, pick=lambda form, entry: True):
+        return {e: _lib.signature(e) for form in SF._FORMS for f, e in _row_entries(form).items() if f == kind and pick(form, e)}
+
+    def one(table):
+        assert table and len({(res, tuple(args)) for res, args in table.values()}) == 1, table
+        return next(iter(table.values()))[1]
+
+    # conv: the entries without the residual pointer agree; those with it (a row's ``res``, or its ``conv`` where ``res_arg``) agree
+    # too, and are the former with ONE pointer more, behind the output pointer
+    plain = one(sigs("conv", lambda form, e: not form.res_arg))
+    with_res = one({**sigs("res"), **sigs("conv", lambda form, e: form.res_arg)})
+    assert len(sigs("res")) == 2 and with_res == plain[:9] + [P] + plain[9:]
+    # the piece-plane entry: the plain arguments with dilation moved from in front of the input pointer to in front of geometry
+    assert one(sigs("planes")) == plain[:5] + plain[6:17] + [I] + plain[17:]
+    # stride 2: no dilation; the entry that serves both bf16 piece counts takes the count in front of geometry, the fp16 one does not
+    s2 = sigs("s2")
+    assert set(s2) == {SF._WIDE3.s2, SF._WIDE2H.s2} and SF._WIDE2.s2 == SF._WIDE3.s2
+    assert s2[SF._WIDE2H.s2][1] == plain[:5] + plain[6:] and s2[SF._WIDE3.s2][1] == plain[:5] + plain[6:17] + [I] + plain[17:]
+    assert (SF._WIDE3.s2_pieces, SF._WIDE2.s2_pieces, SF._WIDE2H.s2_pieces) == (True, True, False)
+    # statistics and the scaled data gradient: raw (no normalisation arguments), one signature each
+    assert len(sigs("stats")) == 2 and one(sigs("stats")) == plain[:10] + [I, P, L, P]
+    assert one(sigs("scaled")) == plain[:9] + [P, I, P]
+    # packs, sizes, queries: one signature per kind
+    assert len(sigs("pack")) == 4 and len(sigs("pack_pair")) == 4 and len(sigs("bytes")) == 5
+    assert one(sigs("pack_pair")) == one(sigs("pack"))[:-1] + [P, L, P]
+    one(sigs("bytes"))
+    assert one({**sigs("query"), **sigs("s2_query"), **sigs("train_query"), **sigs("wgrad_query")}) == [I] * 6
+    # the weight gradient: one plan signature; the launch entry of the form with a scaled entry takes the scale word, one pointer
+    # in front of the slice count, and is otherwise the others'
+    assert len(sigs("wgrad_plan")) == 4 and one(sigs("wgrad_plan"))
+    run = one(sigs("wgrad_run", lambda form, e: form.scaled is None))
+    assert one(sigs("wgrad_run", lambda form, e: form.scaled is not None)) == run[:15] + [P] + run[15:]
+    # every slot a row names is dropped, from a module and from a dict
+    slots = [s for form in SF._FORMS for s in (form.pack_slot, form.train_slot, form.mixed_slot) if s is not None]
+    assert len(slots) == len(set(slots)) == 10 and set(slots) == set(SF._conv3x3_slots())
+    conv, cache = torch.nn.Conv2d(16, 16, 3), {"mats": 1}
+    for s in slots:
+        setattr(conv, s, (None,))
+        cache[s] = (None,)
+    for key in ("pack3x3", "pack3x3_2", "pack3x3_2h", "pack3x3_train"):
+        cache[key] = {}
+    SF.drop_conv3x3_packs(conv)
+    SF.drop_conv3x3_packs(cache)
+    assert not any(hasattr(conv, s) for s in slots) and cache == {"mats": 1}
+
+
 def test_conv2d_square_geometry():
     assert SF.conv2d_square_geometry(torch.nn.Conv2d(8, 8, 3, 1, 2, 2)) == (1, 2, 2)
     assert SF.conv2d_square_geometry(torch.nn.Conv2d(8, 8, 3, (2, 2), (1, 1))) == (2, 1, 1)

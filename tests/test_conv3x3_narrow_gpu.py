@@ -509,13 +509,14 @@ def test_step_config1_with_the_narrow_form(monkeypatch):
     channels), the data gradient of stem conv2, stem conv3 (128 -> 64) and the three 64 -> 64 of layer1 -- layer1.0.conv1's has
     N = 128 and runs on the wide entry; with SKD_SPLIT_NARROW=0, none."""
     import test_step_gpu as TS
-    real = SF._conv3x3_narrow_launch
+    real = SF._conv3x3_raw_launch
     seen = []
 
-    def shim(x, pack, cout, dilation, conv_bias=None):
-        seen.append((int(x.shape[1]), int(cout)))
-        return real(x, pack, cout, dilation, conv_bias)
-    monkeypatch.setattr(SF, "_conv3x3_narrow_launch", shim)
+    def shim(form, x, pack, cout, dilation, conv_bias=None):      # training's one raw launcher: the narrow launches by their entry
+        if form.conv == NARROW:
+            seen.append((int(x.shape[1]), int(cout)))
+        return real(form, x, pack, cout, dilation, conv_bias)
+    monkeypatch.setattr(SF, "_conv3x3_raw_launch", shim)
 
     monkeypatch.setenv("SKD_SPLIT_TRAIN", "1")
     monkeypatch.setenv("SKD_SPLIT_NARROW", "0")

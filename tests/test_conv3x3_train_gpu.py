@@ -361,7 +361,7 @@ def test_step_config1_with_the_training_form(monkeypatch):
     same fixtures at exactly the bounds of test_step_config1_vs_reference_golden: that test's own body runs, with the switch set
     where its ``default_args`` reads it.  A counting shim sees 13 forward calls and 13 data-gradient launches; off, none."""
     import test_step_gpu as TS
-    real_op, real_launch = SF.conv3x3_split_train, SF._conv3x3_split_launch
+    real_op, real_launch = SF.conv3x3_split_train, SF._conv3x3_raw_launch
     seen = {"forward": 0, "bwd_packs": set(), "fwd_packs": set(), "launch_fwd": 0, "launch_bwd": 0}
 
     def op(x, weight, dilation, bias=None, owner=None, **kw):
@@ -372,11 +372,12 @@ def test_step_config1_with_the_training_form(monkeypatch):
         seen["bwd_packs"].add(pb.data_ptr())
         return out
 
-    def launch_(x, pack, cout, dilation, conv_bias=None):
-        seen["launch_bwd" if pack.data_ptr() in seen["bwd_packs"] else "launch_fwd"] += 1
-        return real_launch(x, pack, cout, dilation, conv_bias)
+    def launch_(form, x, pack, cout, dilation, conv_bias=None):      # training's one raw launcher: the wide launches by their entry
+        if form.conv != "skd_conv3x3_narrow_nhwc":
+            seen["launch_bwd" if pack.data_ptr() in seen["bwd_packs"] else "launch_fwd"] += 1
+        return real_launch(form, x, pack, cout, dilation, conv_bias)
     monkeypatch.setattr(SF, "conv3x3_split_train", op)
-    monkeypatch.setattr(SF, "_conv3x3_split_launch", launch_)
+    monkeypatch.setattr(SF, "_conv3x3_raw_launch", launch_)
 
     monkeypatch.setenv("SKD_SPLIT_TRAIN", "0")
     model, _, _ = TS._config1_step(pa=True)

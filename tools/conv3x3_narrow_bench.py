@@ -104,15 +104,13 @@ def main():
             x = cl(torch.relu(torch.randn(a.batch, cin, hw, hw, device=dev)))
             g = cl(torch.randn(a.batch, cout, hw, hw, device=dev))
             w = torch.nn.Conv2d(cin, cout, 3, 1, 1, bias=False).to(dev).to(memory_format=torch.channels_last).weight.detach()
-            pf, pb, fn, bn_ = SF._conv3x3_narrow_train_packs(w, None)
-            fwd = SF._conv3x3_narrow_launch if fn else SF._conv3x3_split_launch
-            bwd = SF._conv3x3_narrow_launch if bn_ else SF._conv3x3_split_launch
+            pf, pb, fwd_form, bwd_form = SF._conv3x3_narrow_train_packs(w, None)
             sides = {
                 "fp": lambda: F.conv2d(x, w, None, 1, 1, 1),
-                "fn": lambda: fwd(x, pf, cout, 1),
+                "fn": lambda: SF._conv3x3_raw_launch(fwd_form, x, pf, cout, 1),
                 "bp": lambda: torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
                                                                   (True, False, False)),
-                "bn": lambda: bwd(g, pb, cin, 1),
+                "bn": lambda: SF._conv3x3_raw_launch(bwd_form, g, pb, cin, 1),
                 "pk": lambda: SF._conv3x3_narrow_train_packs(w, None),        # no owner: no cache, every call packs
             }
             runs = {k: [] for k in sides}

@@ -69,10 +69,10 @@ def main():
             nbytes, (sn, sc, sy, sx), st = pf.numel(), w.stride(), _lib.stream_of(x)
             sides = {
                 "fp": lambda: F.conv2d(x, w, bs, 1, d, d),
-                "fs": lambda: SF._conv3x3_split_launch(x, pf, cout, d, bs),
+                "fs": lambda: SF._conv3x3_raw_launch(SF._WIDE3, x, pf, cout, d, bs),
                 "bp": lambda: torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [d, d], [d, d], False, [0, 0], 1,
                                                                   (True, False, False)),
-                "bs": lambda: SF._conv3x3_split_launch(g, pb, cin, d),
+                "bs": lambda: SF._conv3x3_raw_launch(SF._WIDE3, g, pb, cin, d),
                 "pk": lambda: lib.skd_conv3x3_split_pack_pair(cin, cout, w.data_ptr(), sn, sc, sy, sx, pf.data_ptr(), nbytes,
                                                               pb.data_ptr(), nbytes, st),
             }
@@ -82,8 +82,8 @@ def main():
                 n2 = pf2.numel()
                 sides = {
                     "fp": sides["fs"], "bp": sides["bs"], "pp": sides["pk"],
-                    "fs": lambda: SF._conv3x3_split_launch(x, pf2, cout, d, bs, pieces=2),
-                    "bs": lambda: SF._conv3x3_split_launch(g, pb2, cin, d, pieces=2),
+                    "fs": lambda: SF._conv3x3_raw_launch(SF._WIDE2, x, pf2, cout, d, bs),
+                    "bs": lambda: SF._conv3x3_raw_launch(SF._WIDE2, g, pb2, cin, d),
                     "pk": lambda: lib.skd_conv3x3_split2_pack_pair(cin, cout, w.data_ptr(), sn, sc, sy, sx, pf2.data_ptr(), n2,
                                                                    pb2.data_ptr(), n2, st),
                 }
